@@ -1,9 +1,15 @@
 #!/usr/bin/env python
 """NAF forward benchmark on MI355X -- the driver's contract.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line: `value`, `ms_per_step` and the workload.  `--full` adds
+everything else the line can carry, each taking time of its own: the reading from idle (`ms_per_step_no_settle`), per-step
+device clocks (`step_ms`), per-phase and attention-kernel events (`phases_ms`, `roofline`, with the kernel's HBM traffic from
+two rocprofv3 --pmc sub-runs), the CPU baseline, and on several GPUs the weak-scaling leg and rank 0's solo run of the batch.
+`--dump-outputs DIR` writes what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 
 A "step" is one whole NAF forward (conv stem -> RoPE + key pooling -> cross-scale neighbourhood
 attention) over one batch of synthetic inputs that are resident in HBM before the timed region.
@@ -61,6 +67,8 @@ WORKLOADS = {
     "G3-k9": (1024, 64, 1024, 9),
 }
 PUBLISHED_MPIX = {"REF448": 3.57}   # BASELINE.md numbers for the exact configuration (other hardware)
+DUMP_MAX_VALUES = 8 << 20           # --dump-outputs: float32 values written in all (32 MiB)
+DUMP_SEED = 1234
 
 
 class EventTimer:
@@ -130,6 +138,30 @@ class StepClock:
 
 def algorithmic_bytes(B, C, lr, out, elt=2, cq=256):
     return elt * B * (cq * out * out + (cq + C) * lr * lr + C * out * out)
+
+
+def dump_outputs(result, out_dir, max_values=DUMP_MAX_VALUES):
+    """--dump-outputs: the tensors one step returned (a tensor, or a list of micro-batch outputs: out0, out1, ...) as
+    out_dir/<name>.npy in float32.  A tensor within its share of `max_values` is written whole, in its logical (NCHW) shape;
+    a larger one as a fixed sample: sorted flat indices into its logical order drawn from a generator seeded with DUMP_SEED,
+    the same for every run with the same arguments.  Returns {name: (shape, values written)}."""
+    import numpy as np
+    tensors = [result] if isinstance(result, torch.Tensor) else list(result)
+    names = ["out"] if isinstance(result, torch.Tensor) else [f"out{i}" for i in range(len(tensors))]
+    share = max_values // max(1, len(tensors))
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for i, (name, t) in enumerate(zip(names, tensors)):
+        t = t.detach()
+        if t.numel() <= share:
+            arr = t.float().cpu().numpy()
+        else:
+            g = torch.Generator().manual_seed(DUMP_SEED + i)
+            idx = torch.randint(0, t.numel(), (share,), generator=g).sort().values
+            arr = t.reshape(-1)[idx.to(t.device)].float().cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name] = (list(t.shape), int(arr.size))
+    return written
 
 
 def cpu_baseline(C, ksz, lr, out, budget_s=25.0):
@@ -286,7 +318,15 @@ def main():
                     "naf_forward's single call")
     ap.add_argument("--graph", action="store_true", help="replay the forward from a hipGraph (NAF.capture); no per-kernel "
                     "event timing is possible inside a graph, so `roofline` is null in this mode")
+    ap.add_argument("--full", action="store_true", help="measure everything beyond value / ms_per_step: the reading from idle, "
+                    "per-step clocks, per-phase and attention-kernel events with the roofline (and its rocprofv3 --pmc sub-runs), the "
+                    "CPU baseline, and on several GPUs the weak-scaling leg and rank 0's solo run; the --no-* options above apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one returned as "
+                    "DIR/<name>.npy (float32; rank 0's shard on several GPUs; a fixed seeded sample of at most "
+                    f"{DUMP_MAX_VALUES >> 20} Mi values in all where the output is larger)")
     args = ap.parse_args()
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -388,7 +428,7 @@ def main():
         # --steps timed the same way, BEFORE any settle phase -- reported as ms_per_step_no_settle so that driver numbers stay
         # comparable across rounds.  Reading 2 (ms_per_step, `value`): after the settle phase below.
         el_cold = clock_cold = None
-        if args.settle_seconds > 0 and not args.no_cold_reading:
+        if args.full and args.settle_seconds > 0 and not args.no_cold_reading:
             for _ in range(args.warmup):
                 o = step()
             del o
@@ -427,19 +467,24 @@ def main():
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
-        timer.enabled = True
-        clock = StepClock(args.steps)
+        timer.enabled = args.full                               # the kernel / phase events and the step clock: --full only
+        clock = StepClock(args.steps) if args.full else None
         t0 = time.perf_counter()
         for i in range(args.steps):
-            clock.mark(i)
+            if clock:
+                clock.mark(i)
             o = step()
-        clock.close()
+        if clock:
+            clock.close()
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         torch.cuda.synchronize()
         el = time.perf_counter() - t0
         timer.enabled = False
+        if args.dump_outputs and rank == 0:
+            for name, (shape, n) in dump_outputs(o, args.dump_outputs).items():
+                print(f"bench.py: wrote {n} values of {name} {shape} to {os.path.join(args.dump_outputs, name)}.npy", file=sys.stderr)
 
     ranks_info = weak = None
     if world > 1:
@@ -470,7 +515,7 @@ def main():
         wbt = torch.tensor([min(args.micro_batch, B)], dtype=torch.int64, device=dev)
         dist.all_reduce(wbt, op=dist.ReduceOp.MIN)
         wb = int(wbt.item())
-        if wb > 0:
+        if args.full and wb > 0:
             with torch.no_grad():
                 for rep in range(2):
                     torch.cuda.synchronize()
@@ -499,7 +544,7 @@ def main():
                     "mpix_per_s_all_ranks": round(world * wb * out * out / float(tt.item()) / 1e6, 2)}
 
     one_gpu_ms = None
-    if world > 1 and not args.no_single_gpu_reference:
+    if world > 1 and args.full and not args.no_single_gpu_reference:
         # the same `total` images on ONE GPU (rank 0 alone, outputs dropped as it goes: 64 outputs are 137 GB)
         del o
         torch.cuda.empty_cache()
@@ -576,7 +621,7 @@ def main():
             # the same W warm-ups + K steps taken BEFORE the settle phase (the protocol of rounds 1-3): comparable across rounds
             "ms_per_step_no_settle": round(el_cold * 1e3 / args.steps, 4) if el_cold else None,
             # where the time of each reading went, step by step (a clock ramp shows as a falling `head`, a slow first launch as `first`)
-            "step_ms": clock.summary(args.steps),
+            "step_ms": clock.summary(args.steps) if clock else None,
             "step_ms_no_settle": clock_cold.summary(args.steps) if clock_cold else None,
             "settle": {"seconds": args.settle_seconds, "steps": settle_steps,
                        "what": "untimed set-up before the warm-up steps: the step is run for this long so that the device has left its idle power state"},
@@ -614,7 +659,7 @@ def main():
             line["scatter_ms"] = round(scatter_ms, 3)
             line["one_gpu_ms"] = round(one_gpu_ms, 3) if one_gpu_ms else None
             line["speedup_vs_1"] = round(one_gpu_ms / ms_step, 3) if one_gpu_ms else None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(C, ksz, lr, out, budget_s=args.cpu_baseline_budget)
         else:
             line["cpu_baseline"] = None

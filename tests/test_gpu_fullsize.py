@@ -330,7 +330,7 @@ def test_bench_multi_rank_path_dry_run(dev, launcher, world, total):
     s = socket.socket(); s.bind(("127.0.0.1", 0)); port = s.getsockname()[1]; s.close()
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NAF_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    tail = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--total-batch", str(total)]
+    tail = [os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1", "--total-batch", str(total), "--full"]
     if launcher == "plain":
         cmd = [sys.executable, *tail]
         env = {k: v for k, v in env.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
@@ -361,6 +361,42 @@ def test_bench_multi_rank_path_dry_run(dev, launcher, world, total):
     assert ph["stem"] > 0 and ph["rope_pool"] > 0 and ph["attention"] > 0 and ph["stem_conv3"] > 0
     # (<=: with eight processes time-slicing one GPU the attention launch takes so long that the 5 us pre-pass vanishes in the fourth decimal)
     assert 0 < j["roofline"]["frac_with_prepass"] <= j["roofline"]["frac"]
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(dev, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` (no --full) times exactly K steps and carries the headline only: no CPU
+    baseline, roofline, reading from idle or step clock.  With --dump-outputs it writes a float32 sample of the last step's
+    output, within the size cap; two runs with the same arguments get the same inputs, so their samples agree up to the
+    stem's fp32 summation order (as in test_forward_with_and_without_key_fusion_agree)."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    C, lr, out_sz, _ = bench.WORKLOADS["S256"]
+    dumps = []
+    for run in ("a", "b"):
+        d = tmp_path / run
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "S256",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        j = json.loads(lines[0])
+        assert j["steps"] == 3 and j["warmup"] == 1 and j["ms_per_step"] > 0 and j["value"] > 0
+        assert j["unit"] == "Mpix/s" and j["higher_is_better"] is True and j["dtype"] == "bf16" and j["metric"].startswith("upsampled")
+        assert abs(j["value"] - out_sz * out_sz / (j["ms_per_step"] * 1e-3) / 1e6) <= 2e-3 * j["value"] + 0.05
+        assert j["cpu_baseline"] is None and j["roofline"] is None and j["ms_per_step_no_settle"] is None and j["step_ms"] is None
+        files = sorted(os.listdir(d))
+        assert files == ["out.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 10 ** 6
+        a = np.load(d / "out.npy")
+        assert a.dtype == np.float32 and a.shape == (bench.DUMP_MAX_VALUES,) and bool(np.isfinite(a).all())
+        dumps.append(torch.from_numpy(a))
+    assert float(dumps[0].abs().mean()) > 1e-3                   # an output, not zeros
+    err = (dumps[0] - dumps[1]).abs()
+    assert float(err.max()) <= 1.2e-2 and float(err.mean()) <= 2e-4, (float(err.max()), float(err.mean()))
 
 
 @pytest.mark.parametrize("amp", ["auto", False])

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 out=gpurun_out/profiles_raw
 rm -rf $out; mkdir -p $out
 # 1) the bench line itself (un-profiled)
-python bench.py > $out/bench_line.json 2> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 tail -1 $out/bench_line.json
 # 2) kernel trace + stats of the same command
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python bench.py --no-cpu-baseline > $out/trace.log 2>&1

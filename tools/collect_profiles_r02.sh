@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 R=$PWD
 out=$R/gpurun_out/r02prof
 rm -rf $out; mkdir -p $out
-python bench.py > $out/bench_line.json 2> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 tail -1 $out/bench_line.json | cut -c1-400
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --no-cpu-baseline > $out/trace.log 2>&1)
 grep '^{"metric"' $out/trace.log | tail -1 > $out/bench_line_under_rocprof.json

@@ -10,8 +10,8 @@ export TMPDIR=/tmp
 R=$PWD
 out=$R/gpurun_out/r03prof
 rm -rf $out; mkdir -p $out
-python bench.py > $out/bench_line.json 2> $out/bench.err
-python bench.py --no-cpu-baseline --no-live-traffic --phase-every 1 > $out/bench_line_all_phases.json 2>> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
+python bench.py --full --no-cpu-baseline --no-live-traffic --phase-every 1 > $out/bench_line_all_phases.json 2>> $out/bench.err
 tail -1 $out/bench_line.json | cut -c1-400
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --no-cpu-baseline --no-live-traffic > $out/trace.log 2>&1)
 grep '^{"metric"' $out/trace.log | tail -1 > $out/bench_line_under_rocprof.json

@@ -10,12 +10,12 @@ export TMPDIR=/tmp
 R=$PWD
 out=$R/gpurun_out/r05prof
 rm -rf $out; mkdir -p $out
-python bench.py > $out/bench_line.json 2> $out/bench.err
-python bench.py --no-cpu-baseline --no-live-traffic --phase-every 1 > $out/bench_line_all_phases.json 2>> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
+python bench.py --full --no-cpu-baseline --no-live-traffic --phase-every 1 > $out/bench_line_all_phases.json 2>> $out/bench.err
 tail -1 $out/bench_line.json | cut -c1-400
 # the same step replayed from a hipGraph (launch gaps on record), and the A/B lines of this round's two changes to the forward:
 # key pooling on the last stem layers vs the separate pre-pass, two streams vs one (interleaved, one lease)
-python bench.py --graph --no-cpu-baseline --no-live-traffic > $out/bench_line_graph.json 2>> $out/bench.err
+python bench.py --full --graph --no-cpu-baseline --no-live-traffic > $out/bench_line_graph.json 2>> $out/bench.err
 {
   echo "# interleaved A/B on one lease (bench.py --steps 300 --no-phase-events): stream layout of the one-call forward -- 0 = the library's plan"
   echo "# (naf_forward_streams), 1 = one stream, 2 = the branches side by side on the stream the host lends; ms per step, Mpix/s, streams used"
@@ -31,7 +31,7 @@ cat $out/ab_streams.txt
 {
   echo "# bench.py --workload W --steps 100 (one lease): Mpix/s, ms per step, attention kernel ms, fraction of the 8 TB/s HBM roof, of the 2.5 PFLOP/s MFMA roof"
   for w in G2-k7 G2-k11 G2-k15 G3 G4 REF448 S256; do
-    python bench.py --workload $w --steps 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-8s %8.2f Mpix/s  %.4f ms/step  attention %.4f ms  hbm %.4f  mfma %.4f  stem %.4f' % ('$w', d['value'], d['ms_per_step'], r['kernel_ms'], r['frac'], r['mfma_frac'], d['phases_ms']['stem']))"
+    python bench.py --full --workload $w --steps 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-8s %8.2f Mpix/s  %.4f ms/step  attention %.4f ms  hbm %.4f  mfma %.4f  stem %.4f' % ('$w', d['value'], d['ms_per_step'], r['kernel_ms'], r['frac'], r['mfma_frac'], d['phases_ms']['stem']))"
   done
 } > $out/other_workloads.txt
 cat $out/other_workloads.txt

@@ -7,12 +7,12 @@ export TMPDIR=/tmp
 R=$PWD
 out=$R/gpurun_out/r05final
 rm -rf $out; mkdir -p $out
-python bench.py > $out/bench_line.json 2> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 tail -1 $out/bench_line.json | cut -c1-400
 {
   echo "# bench.py --workload W --steps 100 (one lease, final tree of round 5): Mpix/s, ms per step, attention kernel ms, fraction of the 8 TB/s HBM roof, of the 2.5 PFLOP/s MFMA roof"
   for w in G2-k7 G2-k11 G2-k15 G3 G4 REF448 S256; do
-    python bench.py --workload $w --steps 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-8s %8.2f Mpix/s  %.4f ms/step  attention %.4f ms  hbm %.4f  mfma %.4f  stem %.4f' % ('$w', d['value'], d['ms_per_step'], r['kernel_ms'], r['frac'], r['mfma_frac'], d['phases_ms']['stem']))"
+    python bench.py --full --workload $w --steps 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('%-8s %8.2f Mpix/s  %.4f ms/step  attention %.4f ms  hbm %.4f  mfma %.4f  stem %.4f' % ('$w', d['value'], d['ms_per_step'], r['kernel_ms'], r['frac'], r['mfma_frac'], d['phases_ms']['stem']))"
   done
 } > $out/other_workloads.txt
 cat $out/other_workloads.txt

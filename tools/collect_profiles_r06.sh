@@ -20,7 +20,7 @@ for r in rows[:int(sys.argv[2])]:
 PY
 }
 # ---- 1
-python bench.py > $out/bench_line.json 2> $out/bench.err
+python bench.py --full > $out/bench_line.json 2> $out/bench.err
 tail -1 $out/bench_line.json | cut -c1-300
 (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -- python $R/bench.py --no-cpu-baseline --no-live-traffic > $out/trace.log 2>&1)
 grep '^{"metric"' $out/trace.log | tail -1 > $out/bench_line_under_rocprof.json
@@ -31,12 +31,12 @@ line() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofl
 {
   echo "# bench.py --workload W --steps 100 (one lease, final tree of round 6): Mpix/s, ms per step, attention kernel ms, fraction of the 8 TB/s HBM roof, of the 2.5 PFLOP/s MFMA roof"
   for w in G2-k7 G2-k11 G2-k15 G3 G4 REF448 S256; do
-    python bench.py --workload $w --steps 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | line $w
+    python bench.py --full --workload $w --steps 100 --no-cpu-baseline --no-live-traffic 2>/dev/null | tail -1 | line $w
   done
   echo "# the sliding-window kernel's tail hand-over (xna_slide_kernel.h STEAL; VERDICT r05 item 2) against the static split, interleaved, 400 steps each"
   for i in 1 2 3; do
     for st in 0 1; do
-      NAF_HIP_KNOBS=1 NAF_XNA_STEAL=$st python bench.py --workload G2-k11 --steps 400 --no-cpu-baseline --no-live-traffic --no-cold-reading 2>/dev/null | tail -1 | line "G2-k11 steal=$st"
+      NAF_HIP_KNOBS=1 NAF_XNA_STEAL=$st python bench.py --full --workload G2-k11 --steps 400 --no-cpu-baseline --no-live-traffic --no-cold-reading 2>/dev/null | tail -1 | line "G2-k11 steal=$st"
     done
   done
 } > $out/other_workloads.txt

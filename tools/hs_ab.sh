@@ -8,7 +8,7 @@ line() { python3 -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofl
 for rep in 1 2 3; do
   for w in G2-k7 G3 G1-k9 G3-k9 G1; do
     for hs in 1 0; do
-      NAF_HIP_KNOBS=1 NAF_XNA_HS=$hs python bench.py --workload $w --steps 300 --no-cpu-baseline --no-live-traffic --no-cold-reading 2>/dev/null | tail -1 | line "$w hs=$hs"
+      NAF_HIP_KNOBS=1 NAF_XNA_HS=$hs python bench.py --full --workload $w --steps 300 --no-cpu-baseline --no-live-traffic --no-cold-reading 2>/dev/null | tail -1 | line "$w hs=$hs"
     done
   done
 done | tee $out/ab.txt

@@ -14,7 +14,7 @@ for step in "$@"; do
     tests)       # the whole GPU suite with per-test durations
       timeout 1400 python -m pytest tests -m gpu -x -q --durations=70 > $out/tests.log 2>&1; echo "rc=$?" >> $out/tests.log; tail -90 $out/tests.log | cut -c1-220 ;;
     bench)       # the driver's line
-      python bench.py > $out/bench.json 2> $out/bench.err; tail -c 3000 $out/bench.json ;;
+      python bench.py --full > $out/bench.json 2> $out/bench.err; tail -c 3000 $out/bench.json ;;
     train)       # round 6: the training path on the HIP stem (every width), the device-evaluated oracle cases, the 8-rank rehearsal
       timeout 1400 python -m pytest tests/test_gpu_train_stem.py tests/test_gpu_fuzz_train.py tests/test_gpu_fullsize.py tests/test_gpu_parity.py -m gpu -q -s --durations=25 \
         -k "train or backward or oracle_on_the_device or F8 or denoising or G4 or G3 or dry_run or differentiable or plain_convolution or act_ or weight_gradient or first_convolution or strided" > $out/tests.log 2>&1; echo "rc=$?" >> $out/tests.log
@@ -25,7 +25,7 @@ for step in "$@"; do
         [ $w = G2-k13x ] && continue
         for i in 1 2 3; do
           for st in 1 0; do
-            NAF_HIP_KNOBS=1 NAF_XNA_STEAL=$st python bench.py --workload $w --steps 400 --no-cpu-baseline --no-live-traffic --no-cold-reading 2>/dev/null | python -c "
+            NAF_HIP_KNOBS=1 NAF_XNA_STEAL=$st python bench.py --full --workload $w --steps 400 --no-cpu-baseline --no-live-traffic --no-cold-reading 2>/dev/null | python -c "
 import sys, json
 j = json.loads(sys.stdin.readline()); r = j['roofline']
 print('$w steal=$st  step %.4f ms  attention %.4f ms  frac %.4f  mfma_frac %.4f' % (j['ms_per_step'], r['kernel_ms'], r['frac'], r['mfma_frac']))"
@@ -47,7 +47,7 @@ print('$w steal=$st  step %.4f ms  attention %.4f ms  frac %.4f  mfma_frac %.4f'
     driver)      # what the driver does at round end: smoke(), the GPU suite, the default bench line
       python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -2
       timeout 1400 python -m pytest tests -m gpu -x -q > $out/tests.log 2>&1; echo "rc=$?" >> $out/tests.log; tail -4 $out/tests.log | cut -c1-200
-      python bench.py --steps 20 > $out/bench20.json 2> $out/bench20.err; python3 -c "
+      python bench.py --full --steps 20 > $out/bench20.json 2> $out/bench20.err; python3 -c "
 import json; j = json.load(open('$out/bench20.json')); r = j['roofline']
 print('bench --steps 20: %.2f Mpix/s  %.4f ms (from idle %.4f)  attention %.4f ms = %.4f of the roof; first steps settled %s | from idle %s' % (j['value'], j['ms_per_step'], j['ms_per_step_no_settle'], r['kernel_ms'], r['frac'], j['step_ms']['head'][:4], j['step_ms_no_settle']['head'][:6]))" ;;
     bwdpt)       # round 6: partial row tiles in the cell backward (patch-14 cells) -- parity, then the patch-14 training point's backward
