@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define NAF_HIP_VERSION 402 /* major*10000 + minor*100 + patch */
+#define NAF_HIP_VERSION 403 /* major*10000 + minor*100 + patch */
 /* Binary compatibility: the argument structs carry no size field, so a host must be BUILT against the header of the library it
  * loads whenever the minor version differs (compare naf_version() / 100 with NAF_HIP_VERSION / 100 at start-up, as
  * examples/c_host.c does).  0.1.x appended fields to naf_xna_bwd_args (workspace) and naf_forward_args (phase_events): hosts
@@ -56,7 +56,9 @@ extern "C" {
  * padding (a zero-initialised struct of an older host reads 0 = 128, struct sizes and all other offsets unchanged), the plain mode
  * of naf_stem_conv_fwd and naf_stem_act_fwd / _bwd lose their 128- / 64-multiple restrictions; naf_forward_workspace_bytes_ex; the cell
  * backward takes cells of 14 / 15 / 28 / 30 ... pixels per row at windows up to 9 x 9 (naf_xna_bwd_supported then says NAF_XNA_MFMA where
- * 0.4.1 said NAF_XNA_ROWS: no tables / workspace needed any more). */
+ * 0.4.1 said NAF_XNA_ROWS: no tables / workspace needed any more).
+ * 0.4.3 (binary compatible with 0.4.x: a new entry point only): naf_xna_bwd_scores / naf_xna_bwd_scores_supported -- the attention backward
+ * with a gradient of the scaled scores naf_xna_fwd returns in `logits` (naf_xna_bwd_scores_args), so that a loss on the scores trains q and k. */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -512,6 +514,25 @@ size_t naf_xna_bwd_workspace_bytes(const naf_xna_bwd_args* a);
  * backward per chunk itself with fp32-accumulating glue, or uses windows / widths that run whole (k <= 9, or Dv <= 128 at 11 x 11). */
 int naf_xna_bwd_chunk_plan(const naf_xna_bwd_args* a, int32_t* out, int cap);
 int naf_xna_bwd(const naf_xna_bwd_args* a, naf_stream_t stream);
+
+/* 0.4.3: the backward with a gradient of the scores.  naf_xna_fwd's `logits` are L[i, j] = scale * q_i . k_j (window slot j = ty * kx + tx,
+ * the taps of idx_y / idx_x); a loss that uses them as well as the output gives, with G = dL,
+ *     dS[i, j] = scale * (P[i, j] * (dP[i, j] - delta[i]) + G[i, j])      dQ[i] = sum_j dS[i, j] k_j      dK[j] += sum_i dS[i, j] q_i
+ * (P, delta and dV do not depend on G).  Every kernel adds G with one fma onto the dS it already forms, so a zero G gives naf_xna_bwd's
+ * results bit for bit.  The kernel is chosen as naf_xna_bwd chooses it, except that non-integer ratios (repeated taps: a (query, key) pair is
+ * several slots) run the table-driven kernel instead of NAF_XNA_ROWS, and so do cell shapes whose dlogits_stride[3] * (Wo / w) + ky * kx
+ * reaches 2^29; naf_xna_bwd_scores_supported says which, and the caller brings tables / workspace accordingly (naf_xna_bwd_workspace_bytes
+ * may name bytes for a shape that then runs the table-driven kernel, which needs none).  Any non-negative strides serve (0 included: a
+ * gradient expanded over an axis).  The chunked cell backward adds G in its first channel chunk only.  s == NULL or s->dlogits == NULL: exactly naf_xna_bwd. */
+typedef struct naf_xna_bwd_scores_args {
+    const float* dlogits;        /* device fp32 [B, heads, Ho, Wo, ky*kx], slot axis contiguous, 4-byte aligned: the gradient of `logits` */
+    int64_t dlogits_stride[4];   /* {b, head, y, x} in elements, any non-negative values */
+} naf_xna_bwd_scores_args;
+/* NAF_XNA_MFMA / NAF_XNA_ROWS / NAF_XNA_GENERIC: the kernel naf_xna_bwd_scores would run under a->path, negative naf_status on invalid
+ * arguments (of either struct; -NAF_ERR_UNSUPPORTED where a->path insists on a kernel that does not serve the request).  A pure host-side
+ * query (no device call); pointers are only checked, not read. */
+int naf_xna_bwd_scores_supported(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* s);
+int naf_xna_bwd_scores(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* s, naf_stream_t stream);
 
 /* ---- whole forward in one call ----------------------------------------------------------------------
  * Replaces NAF.forward (src/model/naf.py:104-116) for the default architecture (dim 256 = two 128-channel

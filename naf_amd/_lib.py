@@ -15,7 +15,7 @@ import torch  # noqa: F401  (must be imported before the HIP library is dlopen'e
 # NAF_HIP_LIB lets an experiment point at an alternative build of the SAME library (A/B kernel variants)
 LIB_PATH = os.environ.get("NAF_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libnaf_hip.so")
 
-HEADER_VERSION = 402          # NAF_HIP_VERSION of the include/naf_hip.h these ctypes mirrors were written against
+HEADER_VERSION = 403          # NAF_HIP_VERSION of the include/naf_hip.h these ctypes mirrors were written against
 NAF_BF16, NAF_F32 = 0, 1
 XNA_AUTO, XNA_MFMA, XNA_GENERIC, XNA_UNION, XNA_ROWS = 0, 1, 2, 3, 4
 
@@ -133,6 +133,11 @@ class XnaBwdArgs(C.Structure):
     ]
 
 
+class XnaBwdScoresArgs(C.Structure):
+    """naf_xna_bwd_scores_args (0.4.3): the gradient of naf_xna_fwd's logits for naf_xna_bwd_scores."""
+    _fields_ = [("dlogits", C.c_void_p), ("dlogits_stride", I64x4)]
+
+
 MAX_STEM_LAYERS = 8
 
 
@@ -206,6 +211,8 @@ SIGNATURES = {
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),
     "naf_xna_bwd": (C.c_int, [C.POINTER(XnaBwdArgs), C.c_void_p]),
+    "naf_xna_bwd_scores_supported": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(XnaBwdScoresArgs)]),
+    "naf_xna_bwd_scores": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(XnaBwdScoresArgs), C.c_void_p]),
     "naf_forward_workspace_bytes": (C.c_size_t, [C.POINTER(ForwardArgs)]),
     "naf_forward_workspace_bytes_ex": (C.c_size_t, [C.POINTER(ForwardArgs), C.c_uint32]),
     "naf_forward_supported": (C.c_int, [C.POINTER(ForwardArgs)]),

@@ -431,6 +431,70 @@ int naf_xna_bwd(const naf_xna_bwd_args* a, naf_stream_t stream) {
     return naf_launch_xna_generic_bwd(a, scale, static_cast<hipStream_t>(stream));
 }
 
+// ---- 0.4.3: the backward with a gradient of the scores ------------------------------------------------------
+static bool scores_given(const naf_xna_bwd_scores_args* s) { return s != nullptr && s->dlogits != nullptr; }
+
+static int xna_bwd_scores_validate(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* s) {
+    const int rc = xna_bwd_validate(a);
+    if (rc != NAF_OK || !scores_given(s)) return rc;
+    NAF_REQUIRE((reinterpret_cast<uintptr_t>(s->dlogits) & 3) == 0, "naf_xna_bwd_scores: dlogits must be 4-byte aligned (fp32)");
+    static const char* const axis[4] = {"b", "head", "y", "x"};
+    // read only, so any non-negative strides serve: 0 (a gradient expanded over an axis, e.g. of a loss on scores.sum(dim=(2, 3))) and rows
+    // that overlap included; the slot axis itself is contiguous by definition (there is no stride for it)
+    for (int i = 0; i < 4; ++i)
+        NAF_REQUIRE(s->dlogits_stride[i] >= 0, "naf_xna_bwd_scores: dlogits_stride[%d] (%s) is negative (%lld)", i, axis[i],
+                    (long long)s->dlogits_stride[i]);
+    return NAF_OK;
+}
+
+// As xna_bwd_pick, with two exceptions under a score gradient: the row-streaming kernel takes it at integer ratios only (a (query, key) pair
+// is then one slot; with repeated taps it would be a sum over slots), so non-integer ratios run the table-driven kernel; and the cell kernels
+// gather G with 32-bit offsets within a cell, so a G whose x stride puts a cell's queries 2^29 elements apart or more (no layout torch makes
+// for these shapes) runs the table-driven kernel too.
+static int xna_bwd_scores_pick(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* s) {
+    const int sel = xna_bwd_pick(a);
+    if (sel < 0 || !scores_given(s)) return sel;
+    if (sel == NAF_XNA_ROWS && !(a->Ho % a->h == 0 && a->Wo % a->w == 0)) {
+        if (a->path == NAF_XNA_ROWS) {
+            naf_set_error("naf_xna_bwd_scores: path NAF_XNA_ROWS takes a score gradient at integer ratios only (%dx%d -> %dx%d)", a->h, a->w, a->Ho, a->Wo);
+            return -NAF_ERR_UNSUPPORTED;
+        }
+        return NAF_XNA_GENERIC;
+    }
+    if (sel == NAF_XNA_MFMA && (int64_t)(a->Wo / a->w) * s->dlogits_stride[3] + (int64_t)a->ky * a->kx >= ((int64_t)1 << 29)) {
+        if (a->path == NAF_XNA_MFMA) {
+            naf_set_error("naf_xna_bwd_scores: path NAF_XNA_MFMA needs dlogits_stride[3] * (Wo / w) + ky * kx < 2^29");
+            return -NAF_ERR_UNSUPPORTED;
+        }
+        return NAF_XNA_GENERIC;
+    }
+    return sel;
+}
+
+int naf_xna_bwd_scores_supported(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* s) {
+    const int rc = xna_bwd_scores_validate(a, s);
+    if (rc != NAF_OK) return -rc;
+    return xna_bwd_scores_pick(a, s);
+}
+
+int naf_xna_bwd_scores(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* s, naf_stream_t stream) {
+    if (!scores_given(s)) return naf_xna_bwd(a, stream);
+    const int rc = xna_bwd_scores_validate(a, s);
+    if (rc != NAF_OK) return rc;
+    const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
+    const int sel = xna_bwd_scores_pick(a, s);
+    if (sel < 0) return -sel;
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    if (sel == NAF_XNA_MFMA) return naf_launch_xna_bwd(a, scale, st, s);
+    NAF_REQUIRE(a->workspace == nullptr || al16(a->workspace), "naf_xna_bwd_scores: workspace must be 16-byte aligned");
+    if (sel == NAF_XNA_ROWS) {
+        if (a->idx_y && a->idx_x && a->workspace && (size_t)a->workspace_bytes >= naf_xna_rows_bwd_workspace(a))
+            return naf_launch_xna_rows_bwd(a, scale, st, s);
+        NAF_REQUIRE(a->path == NAF_XNA_AUTO, "naf_xna_bwd_scores: path NAF_XNA_ROWS needs idx_y / idx_x and a workspace of naf_xna_bwd_workspace_bytes()");
+    }
+    return naf_launch_xna_generic_bwd(a, scale, st, s);
+}
+
 // ---- whole forward in one call ---------------------------------------------------------------------------
 namespace {
 // Two streams (round 4; since 0.4.0 the second one is the CALLER's, naf_forward_aux): the two branches' block layers run side by

@@ -1,7 +1,8 @@
 // Eligibility + dispatcher of the attention backward (see xna_bwd_kernel.h).
 #include "xna_bwd_kernel.h"
 
-#define NAF_DECL(K) int naf_xna_bwd_launch_k##K(const XnaBwdParams& p, int Dv, hipStream_t s);
+#define NAF_DECL(K) int naf_xna_bwd_launch_k##K(const XnaBwdParams& p, int Dv, hipStream_t s); \
+    int naf_xna_bwd_scores_launch_k##K(const XnaBwdScoresParams& p, int Dv, hipStream_t s);
 NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
 #undef NAF_DECL
 
@@ -69,7 +70,7 @@ int naf_xna_bwd_chunks(const naf_xna_bwd_args* a, int32_t* out, int cap) {
     return n;
 }
 
-int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s) {
+int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, const naf_xna_bwd_scores_args* sg) {
     if (!naf_xna_bwd_eligible(a)) {
         naf_set_error(
             "naf_xna_bwd: needs square odd kernel 3..15, Dq=64, integer ratio with row tiles (Wo/w %% 16 == 0, or 14 / 15 / 28 ... up to 9x9), h,w >= kernel, "
@@ -102,6 +103,9 @@ int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s) {
     }
     p.dv_pitch = a->Dv;
     p.dq_accum = 0;
+    // a gradient of the scores (naf_xna_bwd_scores) enters dQ / dK once: in the first chunk, which runs the SG instantiation
+    const bool scores = sg != nullptr && sg->dlogits != nullptr;
+    XnaBwdScoresParams ps;
     // channel chunks (one launch where the whole Dv fits): v, dout and dv move to the chunk's first channel of every head
     for (int c0 = 0; c0 < a->Dv;) {
         const int dvc = bwd_next_chunk(a->ky, a->Dv, a->Dv - c0);
@@ -110,6 +114,20 @@ int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s) {
         p.dv = a->dv_lr + c0;
         p.dq_accum = c0 > 0;
         int rc = NAF_ERR_UNSUPPORTED;
+        if (scores && c0 == 0) {
+            static_cast<XnaBwdParams&>(ps) = p;
+            ps.dl = sg->dlogits;
+            for (int i = 0; i < 4; ++i) ps.dls[i] = sg->dlogits_stride[i];
+            switch (a->ky) {
+                case 3: rc = naf_xna_bwd_scores_launch_k3(ps, dvc, s); break;
+                case 5: rc = naf_xna_bwd_scores_launch_k5(ps, dvc, s); break;
+                case 7: rc = naf_xna_bwd_scores_launch_k7(ps, dvc, s); break;
+                case 9: rc = naf_xna_bwd_scores_launch_k9(ps, dvc, s); break;
+                case 11: rc = naf_xna_bwd_scores_launch_k11(ps, dvc, s); break;
+                case 13: rc = naf_xna_bwd_scores_launch_k13(ps, dvc, s); break;
+                case 15: rc = naf_xna_bwd_scores_launch_k15(ps, dvc, s); break;
+            }
+        } else
         switch (a->ky) {
             case 3: rc = naf_xna_bwd_launch_k3(p, dvc, s); break;
             case 5: rc = naf_xna_bwd_launch_k5(p, dvc, s); break;

@@ -76,8 +76,11 @@ struct XnaBwd2Geom {
 // their Q / dO row copies go to the LDS as zeros (so the key waves' contractions over queries see nothing of them) and their dQ is not stored.
 // Those shapes ran the row-streaming kernel until now (32^2 -> 448^2, C = 384, window 9: 1.54 ms against 0.13 ms for 28^2 -> 448^2 here).
 // A template parameter so that the whole-tile instantiations keep their code and registers; whole heads only (no channel chunks).
-template <int KS, int DV, bool CH = false, bool PT = false>
-__global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) {
+// SG (0.4.3, naf_xna_bwd_scores): dS^T += scale G (XnaBwdScoresParams) in the query waves, before the bf16 rounding -- the key waves get dS from
+// them through the LDS, so both contractions see the same G.  A lane reads its query's G of the round's key tiles from global memory at the top
+// of the round (in front of the S / dP MFMAs, which hide the latency); nothing of it is staged (15 x 15 fills the LDS).
+template <int KS, int DV, bool CH = false, bool PT = false, bool SG = false>
+__global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParamsT<SG> p) {
     static_assert(!(CH && PT), "partial row tiles: whole heads only");
     using G = XnaBwdGeom<KS, DV>;
     using G2 = XnaBwd2Geom<KS, DV>;
@@ -86,9 +89,12 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) 
     // key tiles that hold a key: 13 x 13 (169 slots) and 15 x 15 (225) leave the LAST tile of their 192 / 256 padded slots empty -- its S / dP MFMAs,
     // its K / V fragment reads and its dK / dV accumulators are skipped (P and dS of its slots stay 0: sT = -inf below the mask, gT = 0)
     constexpr int MTR = KS >= 13 ? (NSLOT + 15) / 16 : MT;
-    constexpr bool KV2 = G2::kv_bufs == 2, KRES = G2::k_resident, PS2 = G2::ps_bufs == 2;
+    constexpr bool KV2 = G2::kv_bufs == 2, KRES = G2::k_resident && !(SG && KS >= 11), PS2 = G2::ps_bufs == 2;
     constexpr bool KTILE = !KRES && ((KS == 9 && DV >= 256) || KS >= 11);   // K fragments one key tile at a time (elsewhere: all of the window's at the top of a round, or resident)
-    constexpr int VRES = G2::v_res_mt;
+    // SG: the query waves hold G's values and offsets at the dS formation -- the resident V fragments (and, from 11 x 11, the resident K
+    // fragments) give their registers up for them, one LDS read per key tile and round more, so that no SG instantiation with a scratch-free
+    // plain twin spills
+    constexpr int VRES = SG ? 0 : G2::v_res_mt;
     static_assert(DV % 32 == 0, "Dv must be a multiple of 32");
 
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -192,6 +198,12 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) 
         auto dq_of = [&](const Run& c) __attribute__((always_inline)) {
             return p.dq + c.b * p.dqs[0] + c.head * p.dqs[1] + (int64_t)(c.cy0 * p.dy) * p.dqs[2] + (int64_t)(c.xs * p.dx) * p.dqs[3];
         };
+        // SG: G of the cell's first query, and the cell's first window column mod KS (a key's slot here is (column mod KS) * KS + row,
+        // the scores' slot is row * KS + column - x0)
+        auto dl_of = [&](const Run& c) __attribute__((always_inline)) {
+            if constexpr (SG) return p.dl + c.b * p.dls[0] + c.head * p.dls[1] + (int64_t)(c.cy0 * p.dy) * p.dls[2] + (int64_t)(c.xs * p.dx) * p.dls[3];
+            else return static_cast<const float*>(nullptr);
+        };
         // the walker: the round that is requested next (one ahead of the round in hand)
         int a_run = first, a_pos = 0, a_len = r0.len, a_r = 0, a_ty = ty_first, a_tx = tx_first;
         const bf16_t* a_q = q_of(r0);
@@ -239,6 +251,8 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) 
         bf16x8_t kfr[KTILE ? 1 : MT][2], vfr[VRES > 0 ? VRES : 1][DKS];
         int c_run = first, c_pos = 0, c_len = r0.len;
         bf16_t* dq_cell = dq_of(r0);
+        const float* dl_cell = dl_of(r0);
+        [[maybe_unused]] int c_cx = r0.xs, x0m = SG ? x0_of(r0.xs) % KS : 0;   // SG: the cell's column
         int g = 0;   // rounds since the kernel started: round buffer g & 1, row set g & 1
         int kc = 0;  // cells since the kernel started: window buffer kc & 1
         int ty_cur = ty_first, tx_cur = tx_first;   // this wave's tile of the round in hand
@@ -383,6 +397,52 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) 
                     }
                 delta = naf_rows_sum(delta);
                 bf16x8_t dsf[KST];
+                bf16x4_t pkv[MT];        // P in its stored form (with one P / dS buffer it waits in registers for the first barrier; sT is dead from here)
+                if constexpr (SG) {
+                    // P and scale P (dP - delta) first (into gT), so that sT is dead before G's registers are needed: G of the round's key tiles
+                    // held across the S / dP MFMAs spilled every instantiation from 9 x 9 up.  Then this lane's query's G, gathered in the
+                    // scores' slot order (the window's slot here is (column mod KS) * KS + row), and dS^T = bf16(scale G + scale P (dP - delta)).
+#pragma unroll
+                    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                        for (int rr = 0; rr < 4; ++rr) {
+                            gT[mt][rr] = p.scale * sT[mt][rr] * (gT[mt][rr] - delta);
+                            pkv[mt][rr] = (live && lane_on) ? (bf16_t)sT[mt][rr] : (bf16_t)0.f;
+                        }
+                    const int qx = tx0 + (PT ? min(col, cols_of(tx_cur) - 1) : col);     // idle lanes read the row's last query
+                    // a wave-uniform row base and ONE 32-bit byte offset per load (the saddr form; the host keeps dx * x-stride + KS^2 below
+                    // 2^29 elements for this kernel), both laundered in every round: left alone hipcc hoists the gather's per-lane slot offsets and
+                    // 64-bit addresses (loop-invariant within a cell) out of the round loop and spills them (+108 registers at 9 x 9)
+                    const char* gq = reinterpret_cast<const char*>(dl_cell + (int64_t)ty * p.dls[2]);
+                    uint32_t lb = (uint32_t)(qx * (int32_t)p.dls[3]) * 4u;
+                    int x0l = x0m;
+                    asm volatile("" : "+s"(gq), "+v"(lb), "+s"(x0l));
+                    // in batches of GB key tiles at 13 x 13 / 15 x 15 (a batch's loads, then its dS; sched_barrier keeps the next batch's loads
+                    // behind): G of all twelve / sixteen key tiles at once does not fit beside S^T / dP^T
+                    constexpr int GB = KS >= 13 ? 4 : MT;
+#pragma unroll
+                    for (int g0 = 0; g0 < MT; g0 += GB) {
+                        float glv[GB][4];
+#pragma unroll
+                        for (int u = 0; u < GB; ++u)
+#pragma unroll
+                            for (int rr = 0; rr < 4; ++rr) {
+                                const int mt = g0 + u;
+                                const int sl = mt * 16 + grp * 4 + rr;
+                                const int xm = sl / KS, ry = sl - xm * KS;
+                                const int rx = xm - x0l + (xm < x0l ? KS : 0);
+                                glv[u][rr] = (mt < MTR) ? *reinterpret_cast<const float*>(gq + (lb + (uint32_t)(sl < NSLOT ? ry * KS + rx : 0) * 4u)) : 0.f;
+                            }
+#pragma unroll
+                        for (int ks = g0 / 2; ks < (g0 + GB) / 2; ++ks)
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) {
+                                const int mt = 2 * ks + (j >> 2), rr = j & 3;
+                                dsf[ks][j] = (bf16_t)fmaf(p.scale, mt * 16 + grp * 4 + rr < NSLOT ? glv[mt - g0][rr] : 0.f, gT[mt][rr]);
+                            }
+                        if constexpr (GB < MT) __builtin_amdgcn_sched_barrier(0);
+                    }
+                } else {
 #pragma unroll
                 for (int ks = 0; ks < KST; ++ks)
 #pragma unroll
@@ -390,16 +450,18 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) 
                         const int mt = 2 * ks + (j >> 2), rr = j & 3;
                         dsf[ks][j] = (bf16_t)(p.scale * sT[mt][rr] * (gT[mt][rr] - delta));
                     }
+                }
 
                 // P and dS for the key waves: row-major [query][slot] -- a lane holds four consecutive slots of ITS query per key tile, one
                 // 8-byte store each; the key waves read them back transposed (ds_read_tr) as the A operands of the contractions over queries.
                 // (The four-wave kernel evaluated S and dP a second time with the operands swapped to get that layout out of the MFMA: 32
                 // more MFMAs, 16 more exponentials and a statistics exchange per tile.)
-                bf16x4_t pkv[MT];        // P in its stored form (with one P / dS buffer it waits in registers for the first barrier; sT is dead from here)
+                if constexpr (!SG) {
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                     for (int rr = 0; rr < 4; ++rr) pkv[mt][rr] = (live && lane_on) ? (bf16_t)sT[mt][rr] : (bf16_t)0.f;
+                }
                 auto write_ps = [&]() __attribute__((always_inline)) {
                     bf16_t* prow = Pq + (wave * 16 + col) * PROW + grp * 4;
                     bf16_t* srow = Sq + (wave * 16 + col) * PROW + grp * 4;
@@ -489,12 +551,21 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParams p) 
             if (c_pos + 1 < c_len) {
                 ++c_pos;
                 dq_cell += (int64_t)p.dx * p.dqs[3];
+                if constexpr (SG) {
+                    dl_cell += (int64_t)p.dx * p.dls[3];
+                    x0m = x0_of(++c_cx) % KS;
+                }
             } else {
                 c_run += nwg;
                 if (c_run < nrun) {
                     const Run c = decode(c_run);
                     c_pos = 0; c_len = c.len;
                     dq_cell = dq_of(c);
+                    if constexpr (SG) {
+                        dl_cell = dl_of(c);
+                        c_cx = c.xs;
+                        x0m = x0_of(c.xs) % KS;
+                    }
                 }
             }
             if constexpr (!KV2) {
@@ -781,16 +852,16 @@ constexpr bool xna_bwd2_serves() {
     return (KS <= 11 || (KS == 13 && DV <= 64) || (KS == 15 && DV <= 64)) && XnaBwd2Geom<KS, DV>::lds_bytes() <= 160 * 1024;
 }
 
-template <int KS, int DV>
-static int xna_bwd2_launch_one(const XnaBwdParams& p, hipStream_t s) {
+template <int KS, int DV, bool SG = false>
+static int xna_bwd2_launch_one(const XnaBwdParamsT<SG>& p, hipStream_t s) {
     if constexpr (!xna_bwd2_serves<KS, DV>()) {
-        return xna_bwd_launch_one<KS, DV>(p, s);
+        return xna_bwd_launch_one<KS, DV, SG>(p, s);
     } else {
         constexpr size_t lds = XnaBwd2Geom<KS, DV>::lds_bytes();
-        auto kern = xna_bwd2_kernel<KS, DV>;
+        auto kern = xna_bwd2_kernel<KS, DV, false, false, SG>;
         if ((p.dx & 15) != 0) {      // partial row tiles (patch-14 cells ...): windows up to 9 x 9, whole heads (naf_xna_bwd_eligible)
             if constexpr (KS <= 9) {
-                if (p.dv_pitch == DV) kern = xna_bwd2_kernel<KS, DV, false, true>;
+                if (p.dv_pitch == DV) kern = xna_bwd2_kernel<KS, DV, false, true, SG>;
             }
             if (KS > 9 || p.dv_pitch != DV) {
                 naf_set_error("xna_bwd2: cells of %d pixels per row (not a multiple of 16) need a window <= 9 x 9 and the whole head", p.dx);
@@ -798,7 +869,7 @@ static int xna_bwd2_launch_one(const XnaBwdParams& p, hipStream_t s) {
             }
         } else
         if constexpr ((KS == 11 && DV <= 128) || (KS == 13 && DV <= 64) || (KS == 15 && DV <= 64)) {
-            if (p.dv_pitch != DV) kern = xna_bwd2_kernel<KS, DV, true>;     // a channel chunk of a wider head
+            if (p.dv_pitch != DV) kern = xna_bwd2_kernel<KS, DV, true, false, SG>;     // a channel chunk of a wider head
         } else if (p.dv_pitch != DV) {
             naf_set_error("xna_bwd2: no channel-chunk instantiation for window %d, chunk %d of %d", KS, DV, p.dv_pitch);
             return NAF_ERR_UNSUPPORTED;
@@ -819,7 +890,7 @@ static int xna_bwd2_launch_one(const XnaBwdParams& p, hipStream_t s) {
             const double cost = (double)((runs + ncu - 1) / ncu) * (len + 1.5);
             if (cost < best * 0.999) { best = cost; best_len = len; }
         }
-        XnaBwdParams q = p;
+        XnaBwdParamsT<SG> q = p;
         q.seg_len = best_len;
         q.nseg = (p.w + best_len - 1) / best_len;
         const int64_t runs = rows * q.nseg;
@@ -830,17 +901,17 @@ static int xna_bwd2_launch_one(const XnaBwdParams& p, hipStream_t s) {
 }
 
 // NAF_BWD_V1=1 (with NAF_HIP_KNOBS=1): the four-wave kernel for every shape (A/B measurements)
-template <int KS>
-static int xna_bwd2_launch_ks(const XnaBwdParams& p, int Dv, hipStream_t s) {
+template <int KS, bool SG = false>
+static int xna_bwd2_launch_ks(const XnaBwdParamsT<SG>& p, int Dv, hipStream_t s) {
     static const bool v1 = [] { const char* e = naf_knob("NAF_BWD_V1"); return e != nullptr && atoi(e) != 0; }();
-    if (v1 && (p.dx & 15) == 0) return xna_bwd_launch_ks<KS>(p, Dv, s);      // (the four-wave kernel has whole row tiles only)
+    if (v1 && (p.dx & 15) == 0) return xna_bwd_launch_ks<KS, SG>(p, Dv, s);      // (the four-wave kernel has whole row tiles only)
     switch (Dv) {
-        case 32: return xna_bwd2_launch_one<KS, 32>(p, s);
-        case 64: return xna_bwd2_launch_one<KS, 64>(p, s);
-        case 96: return xna_bwd2_launch_one<KS, 96>(p, s);
-        case 128: return xna_bwd2_launch_one<KS, 128>(p, s);
-        case 192: return xna_bwd2_launch_one<KS, 192>(p, s);
-        case 256: return xna_bwd2_launch_one<KS, 256>(p, s);
+        case 32: return xna_bwd2_launch_one<KS, 32, SG>(p, s);
+        case 64: return xna_bwd2_launch_one<KS, 64, SG>(p, s);
+        case 96: return xna_bwd2_launch_one<KS, 96, SG>(p, s);
+        case 128: return xna_bwd2_launch_one<KS, 128, SG>(p, s);
+        case 192: return xna_bwd2_launch_one<KS, 192, SG>(p, s);
+        case 256: return xna_bwd2_launch_one<KS, 256, SG>(p, s);
     }
     naf_set_error("naf_xna_bwd: no kernel for Dv = %d (32, 64, 96, 128, 192, 256)", Dv);
     return NAF_ERR_UNSUPPORTED;

@@ -12,3 +12,12 @@ int naf_xna_bwd_launch_k15(const XnaBwdParams& p, int Dv, hipStream_t s) {
     naf_set_error("naf_xna_bwd: 15 x 15 windows run in channel chunks of 32 or 64, got %d", Dv);
     return NAF_ERR_UNSUPPORTED;
 }
+int naf_xna_bwd_scores_launch_k15(const XnaBwdScoresParams& p, int Dv, hipStream_t s) {
+    static const bool big8 = [] { const char* e = naf_knob("NAF_BWD_BIG8"); return !(e != nullptr && atoi(e) == 0); }();
+    switch (Dv) {
+        case 32: return big8 ? xna_bwd2_launch_one<15, 32, true>(p, s) : xna_bwd_launch_one<15, 32, true>(p, s);
+        case 64: return big8 ? xna_bwd2_launch_one<15, 64, true>(p, s) : xna_bwd_launch_one<15, 64, true>(p, s);
+    }
+    naf_set_error("naf_xna_bwd_scores: 15 x 15 windows run in channel chunks of 32 or 64, got %d", Dv);
+    return NAF_ERR_UNSUPPORTED;
+}

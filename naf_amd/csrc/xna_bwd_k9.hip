@@ -2,3 +2,4 @@
 #include "xna_bwd2_kernel.h"
 
 int naf_xna_bwd_launch_k9(const XnaBwdParams& p, int Dv, hipStream_t s) { return xna_bwd2_launch_ks<9>(p, Dv, s); }
+int naf_xna_bwd_scores_launch_k9(const XnaBwdScoresParams& p, int Dv, hipStream_t s) { return xna_bwd2_launch_ks<9, true>(p, Dv, s); }

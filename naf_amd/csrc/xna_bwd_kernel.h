@@ -50,6 +50,17 @@ struct XnaBwdParams {
 #endif
 };
 
+// 0.4.3 (naf_xna_bwd_scores): G, the gradient of the scaled scores L[i, j] = scale q_i . k_j that naf_xna_fwd returns as `logits`, enters as
+// dS[i, j] += scale G[i, j] -- one fma onto the dS each form below already makes, so a zero G gives the plain kernel's dS bit for bit.  The
+// kernels that take it are separate instantiations (SG = true): the plain ones keep their code.  A chunked launch (xna_bwd.hip) runs the SG
+// instantiation for its first channel chunk only, so G enters dQ / dK once.
+struct XnaBwdScoresParams : XnaBwdParams {
+    const float* dl;   // [B, heads, Ho, Wo, KS*KS] fp32, slot axis contiguous (slot = window row * KS + window column)
+    int64_t dls[4];    // {b, head, y, x} element strides
+};
+template <bool SG>
+using XnaBwdParamsT = std::conditional_t<SG, XnaBwdScoresParams, XnaBwdParams>;
+
 #ifdef NAF_BWD_TIMING
 #define BWD_T(i) do { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); tacc[i] += now_ - tlast; tlast = now_; } while (0)
 #else
@@ -75,8 +86,8 @@ struct XnaBwdGeom {
 
 // Windows of 11 x 11 and more are compiled for one wave per SIMD: their k^2 x (64 + Dv) accumulators need more than 256
 // registers per lane (and at the larger Dv their K/V tiles leave room for one workgroup per CU anyway).
-template <int KS, int DV>
-__global__ __launch_bounds__(256, (KS >= 11 ? 1 : 2)) void xna_bwd_kernel(const XnaBwdParams p) {
+template <int KS, int DV, bool SG = false>
+__global__ __launch_bounds__(256, (KS >= 11 ? 1 : 2)) void xna_bwd_kernel(const XnaBwdParamsT<SG> p) {
     using G = XnaBwdGeom<KS, DV>;
     constexpr int NSLOT = G::NSLOT, MT = G::MT, KST = G::KST, KROW = G::KROW, VROW = G::VROW, NVT = G::NVT, NVW = G::NVW;
     constexpr int DKS = DV / 32;   // 32-channel k-steps of the dP contraction
@@ -159,6 +170,9 @@ __global__ __launch_bounds__(256, (KS >= 11 ? 1 : 2)) void xna_bwd_kernel(const 
     const bf16_t* q_cell = p.q + b * p.qs[0] + head * p.qs[1] + (int64_t)(cy0 * p.dy) * p.qs[2] + (int64_t)(cx0 * p.dx) * p.qs[3];
     const bf16_t* g_cell = p.dout + b * p.gs[0] + head * p.gs[1] + (int64_t)(cy0 * p.dy) * p.gs[2] + (int64_t)(cx0 * p.dx) * p.gs[3];
     bf16_t* dq_cell = p.dq + b * p.dqs[0] + head * p.dqs[1] + (int64_t)(cy0 * p.dy) * p.dqs[2] + (int64_t)(cx0 * p.dx) * p.dqs[3];
+    // SG: G of the cell's first query; the window's slot order here is the scores' (key = ry * KS + rx, rows / columns from y0 / x0)
+    const float* gl_cell = nullptr;
+    if constexpr (SG) gl_cell = p.dl + b * p.dls[0] + head * p.dls[1] + (int64_t)(cy0 * p.dy) * p.dls[2] + (int64_t)(cx0 * p.dx) * p.dls[3];
 
     // K / V rows this lane reads as an operand fragment: row mt*16 + col (pad slots clamp to the last real key)
     auto krow = [&](int mt) __attribute__((always_inline)) { return min(mt * 16 + col, NSLOT - 1); };
@@ -351,8 +365,18 @@ __global__ __launch_bounds__(256, (KS >= 11 ? 1 : 2)) void xna_bwd_kernel(const 
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
             const f32x4_t g = gT_of(mt);
+            if constexpr (SG) {   // + scale G of this lane's query, slots mt*16 + grp*4 + r
+                const float* gq = gl_cell + (int64_t)ty * p.dls[2] + (int64_t)(tx0 + col) * p.dls[3];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) dsf[mt >> 1][(mt & 1) * 4 + r] = (bf16_t)(p.scale * sT[mt][r] * (g[r] - delta));
+                for (int r = 0; r < 4; ++r) {
+                    const int key = mt * 16 + grp * 4 + r;
+                    const float gv = gq[min(key, NSLOT - 1)];
+                    dsf[mt >> 1][(mt & 1) * 4 + r] = (bf16_t)fmaf(p.scale, key < NSLOT ? gv : 0.f, p.scale * sT[mt][r] * (g[r] - delta));
+                }
+            } else {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) dsf[mt >> 1][(mt & 1) * 4 + r] = (bf16_t)(p.scale * sT[mt][r] * (g[r] - delta));
+            }
         }
 
         BWD_T(2);   // softmax, delta, dS^T
@@ -443,7 +467,12 @@ __global__ __launch_bounds__(256, (KS >= 11 ? 1 : 2)) void xna_bwd_kernel(const 
                 for (int r = 0; r < 4; ++r) {
                     const float pr = kvalid ? __builtin_amdgcn_exp2f(fmaf(sSm[r], p.scale_log2e, -mcq[r])) * invq[r] : 0.f;
                     pk[r] = (bf16_t)pr;
-                    sk[r] = (bf16_t)(p.scale * pr * (gSm[r] - dlq[r]));
+                    if constexpr (SG) {   // + scale G of query grp*4 + r of the tile, slot mt*16 + col (the same G as dS^T above)
+                        const float gv = gl_cell[(int64_t)ty * p.dls[2] + (int64_t)(tx0 + grp * 4 + r) * p.dls[3] + min(mt * 16 + col, NSLOT - 1)];
+                        sk[r] = (bf16_t)fmaf(p.scale, kvalid ? gv : 0.f, p.scale * pr * (gSm[r] - dlq[r]));
+                    } else {
+                        sk[r] = (bf16_t)(p.scale * pr * (gSm[r] - dlq[r]));
+                    }
                 }
                 Pl[(wave * MT + mt) * 64 + lane] = pk;
                 Sl[(wave * MT + mt) * 64 + lane] = sk;
@@ -526,14 +555,14 @@ __global__ __launch_bounds__(256, (KS >= 11 ? 1 : 2)) void xna_bwd_kernel(const 
         }
 }
 
-template <int KS, int DV>
-static int xna_bwd_launch_one(const XnaBwdParams& p, hipStream_t s) {
+template <int KS, int DV, bool SG = false>
+static int xna_bwd_launch_one(const XnaBwdParamsT<SG>& p, hipStream_t s) {
     constexpr size_t lds = XnaBwdGeom<KS, DV>::lds_bytes();
     if constexpr (lds > 160 * 1024) {   // the windows of (KS, DV) do not fit the LDS: eligibility excludes it (table-driven kernel)
         naf_set_error("naf_xna_bwd: window %d with Dv = %d needs %zu bytes of LDS", KS, DV, lds);
         return NAF_ERR_UNSUPPORTED;
     } else {
-        auto kern = xna_bwd_kernel<KS, DV>;
+        auto kern = xna_bwd_kernel<KS, DV, SG>;
         if (lds > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) {
@@ -552,15 +581,15 @@ inline size_t xna_bwd_lds_for(int ks, int dv) {
     return nslot * (72 + dv + 8) * 2 + 2 * 4 * mt * 64 * 8 + (size_t)4 * 16 * (72 + dv + 8) * 2;
 }
 
-template <int KS>
-static int xna_bwd_launch_ks(const XnaBwdParams& p, int Dv, hipStream_t s) {
+template <int KS, bool SG = false>
+static int xna_bwd_launch_ks(const XnaBwdParamsT<SG>& p, int Dv, hipStream_t s) {
     switch (Dv) {
-        case 32: return xna_bwd_launch_one<KS, 32>(p, s);
-        case 64: return xna_bwd_launch_one<KS, 64>(p, s);
-        case 96: return xna_bwd_launch_one<KS, 96>(p, s);
-        case 128: return xna_bwd_launch_one<KS, 128>(p, s);
-        case 192: return xna_bwd_launch_one<KS, 192>(p, s);
-        case 256: return xna_bwd_launch_one<KS, 256>(p, s);
+        case 32: return xna_bwd_launch_one<KS, 32, SG>(p, s);
+        case 64: return xna_bwd_launch_one<KS, 64, SG>(p, s);
+        case 96: return xna_bwd_launch_one<KS, 96, SG>(p, s);
+        case 128: return xna_bwd_launch_one<KS, 128, SG>(p, s);
+        case 192: return xna_bwd_launch_one<KS, 192, SG>(p, s);
+        case 256: return xna_bwd_launch_one<KS, 256, SG>(p, s);
     }
     naf_set_error("naf_xna_bwd: no kernel for Dv = %d (32, 64, 96, 128, 192, 256)", Dv);
     return NAF_ERR_UNSUPPORTED;

@@ -9,6 +9,8 @@
 //
 // One wave per (batch, head, query): lanes split the Dq contraction, wave-reduce per key, logits go
 // to LDS, wave softmax, lanes split Dv for the weighted sum.  Correctness path, not a speed path.
+#include <type_traits>
+
 #include "naf_common.h"
 
 struct XnaGenericParams {
@@ -142,6 +144,7 @@ int naf_launch_xna_generic(const naf_xna_args* a, float scale, hipStream_t s) {
 // serve the shapes.  One wave per (batch, head, query): recompute the scores and P, dP[key] = dO . v[key],
 // delta = sum P dP, dS = scale P (dP - delta); dq = sum_key dS k[key] is written, dk[key] += dS q and
 // dv[key] += P dO go to the fp32 accumulators with atomics.  Correctness path, not a speed path.
+// SG (0.4.3, naf_xna_bwd_scores): dS += scale G with G the gradient of the scores, slot by slot (repeated taps are separate slots here).
 struct XnaGenericBwdParams {
     const bf16_t* q;
     const bf16_t* k;
@@ -157,8 +160,13 @@ struct XnaGenericBwdParams {
     int64_t qs[4], ks[4], vs[4], gs[4], dqs[4];
     int64_t nquery;
 };
+struct XnaGenericBwdScoresParams : XnaGenericBwdParams {
+    const float* dl;   // [B, heads, Ho, Wo, ky*kx], slot axis contiguous
+    int64_t dls[4];
+};
 
-__global__ __launch_bounds__(256) void xna_generic_bwd_kernel(const XnaGenericBwdParams p) {
+template <bool SG>
+__global__ __launch_bounds__(256) void xna_generic_bwd_kernel(const std::conditional_t<SG, XnaGenericBwdScoresParams, XnaGenericBwdParams> p) {
     extern __shared__ __attribute__((aligned(16))) float lg_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int KK = p.ky * p.kx;
@@ -214,7 +222,12 @@ __global__ __launch_bounds__(256) void xna_generic_bwd_kernel(const XnaGenericBw
     delta = wave_sum(delta);
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xc07f);
-    for (int key = lane; key < KK; key += 64) ds[key] = p.scale * pr[key] * (ds[key] - delta);
+    if constexpr (SG) {
+        const float* glp = p.dl + b * p.dls[0] + head * p.dls[1] + (int64_t)y * p.dls[2] + (int64_t)x * p.dls[3];
+        for (int key = lane; key < KK; key += 64) ds[key] = fmaf(p.scale, glp[key], p.scale * pr[key] * (ds[key] - delta));
+    } else {
+        for (int key = lane; key < KK; key += 64) ds[key] = p.scale * pr[key] * (ds[key] - delta);
+    }
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_s_waitcnt(0xc07f);
 
@@ -239,7 +252,7 @@ __global__ __launch_bounds__(256) void xna_generic_bwd_kernel(const XnaGenericBw
     }
 }
 
-int naf_launch_xna_generic_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s) {
+int naf_launch_xna_generic_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, const naf_xna_bwd_scores_args* sg) {
     if (!a->idx_y || !a->idx_x) {
         naf_set_error("naf_xna_bwd: the table-driven path needs idx_y and idx_x (naf_axis_index_table)");
         return NAF_ERR_INVALID;
@@ -272,6 +285,14 @@ int naf_launch_xna_generic_bwd(const naf_xna_bwd_args* a, float scale, hipStream
         naf_set_error("naf_xna_bwd: kernel %dx%d too large for the table-driven kernel", a->ky, a->kx);
         return NAF_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(xna_generic_bwd_kernel, dim3((uint32_t)nb), dim3(256), lds, s, p);
+    if (sg != nullptr && sg->dlogits != nullptr) {
+        XnaGenericBwdScoresParams ps;
+        static_cast<XnaGenericBwdParams&>(ps) = p;
+        ps.dl = sg->dlogits;
+        for (int i = 0; i < 4; ++i) ps.dls[i] = sg->dlogits_stride[i];
+        hipLaunchKernelGGL(xna_generic_bwd_kernel<true>, dim3((uint32_t)nb), dim3(256), lds, s, ps);
+        return naf_check_launch("xna_generic_bwd_kernel<scores>");
+    }
+    hipLaunchKernelGGL(xna_generic_bwd_kernel<false>, dim3((uint32_t)nb), dim3(256), lds, s, p);
     return naf_check_launch("xna_generic_bwd_kernel");
 }

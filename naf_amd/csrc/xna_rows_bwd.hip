@@ -58,6 +58,13 @@ struct XnaRowsBwdParams {
     float scale, scale_log2e;
     int64_t qs[4], kst[4], vs[4], gs[4], dqs[4];
 };
+// 0.4.3 (naf_xna_bwd_scores): G, the gradient of the scaled scores, enters pass 2 of both launches as dS += scale G (SG instantiations; integer
+// ratios only -- a (query, key) pair is then ONE slot, (key row - idx_y[y][0]) * ks + (key column - idx_x[x][0]); with repeated taps it would be
+// a sum over slots, and those shapes run the table-driven kernel)
+struct XnaRowsBwdScoresParams : XnaRowsBwdParams {
+    const float* dl;   // [B, heads, Ho, Wo, ks*ks], slot axis contiguous
+    int64_t dls[4];
+};
 
 namespace {
 // first i in [0, L) with tab[i * ks] + ks - 1 >= target (L when there is none); tab[i * ks] is non-decreasing in i
@@ -102,8 +109,10 @@ __device__ __forceinline__ void overlapping_range(const int32_t* tab, int L, int
 constexpr int rb_regs_heavy(int ndq, int ndv) { return ndq >= 12 || ndv >= 6; }
 }  // namespace
 
-template <int NDQ, int NDV, bool KEYS, bool MULT, int NH>
-__global__ __launch_bounds__(256, (rb_regs_heavy(NDQ, NDV) ? 1 : 2)) void xna_rows_bwd_kernel(const XnaRowsBwdParams p) {
+template <int NDQ, int NDV, bool KEYS, bool MULT, int NH, bool SG = false>
+__global__ __launch_bounds__(256, (rb_regs_heavy(NDQ, NDV) ? 1 : 2)) void xna_rows_bwd_kernel(
+    const std::conditional_t<SG, XnaRowsBwdScoresParams, XnaRowsBwdParams> p) {
+    static_assert(!(SG && MULT), "a score gradient at repeated taps is a sum over slots: the table-driven kernel serves it");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_rb[];
     constexpr int ROWLEN = NDQ * 32 + 8;   // elements; +16 B per row keeps the transposing reads off one bank group
     constexpr int VROW = NDV * 32 + 8;
@@ -375,6 +384,29 @@ __global__ __launch_bounds__(256, (rb_regs_heavy(NDQ, NDV) ? 1 : 2)) void xna_ro
                 const int wyi = row_weight(ry);
                 if (wyi == 0) continue;
                 const float wy = (float)wyi;
+                // SG: G of this lane's 8 (query, key) pairs of the row, requested in front of the row's products (0 where they are not neighbours)
+                float glv[SG ? 8 : 1];
+                if constexpr (SG) {
+#pragma unroll
+                    for (int hh = 0; hh < 2; ++hh)
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int xs = xa + hh * 16 + grp * 4 + i;
+                            const float* gp;
+                            int j;
+                            if constexpr (KEYS) {   // key (row, c_true), streamed query (ry, xs)
+                                const int xq = min(xs, p.Wo - 1);
+                                j = (row - p.idx_y[(int64_t)ry * KS]) * KS + (c_lane - p.idx_x[(int64_t)xq * KS]);
+                                gp = p.dl + b * p.dls[0] + head * p.dls[1] + (int64_t)ry * p.dls[2] + (int64_t)xq * p.dls[3];
+                            } else {                // query (row, c_lane), streamed key (ry, xs)
+                                j = (ry - p.idx_y[(int64_t)row * KS]) * KS + (xs - p.idx_x[(int64_t)c_lane * KS]);
+                                gp = p.dl + b * p.dls[0] + head * p.dls[1] + (int64_t)row * p.dls[2] + (int64_t)c_lane * p.dls[3];
+                            }
+                            const bool nb = wx[hh][i] > 0.f;
+                            const float g = gp[nb ? j : 0];
+                            glv[hh * 4 + i] = nb ? g : 0.f;
+                        }
+                }
                 f32x4_t s[2], dp[2];
                 row_products(xa, ry, true, s, dp);
                 bf16x8_t dsa, pa;
@@ -390,7 +422,8 @@ __global__ __launch_bounds__(256, (rb_regs_heavy(NDQ, NDV) ? 1 : 2)) void xna_ro
                         }
                         const float pr = wx[hh][i] > 0.f ? wy * wx[hh][i] * __builtin_amdgcn_exp2f(fmaf(s[hh][i], p.scale_log2e, -qmc)) * qinv : 0.f;
                         pa[hh * 4 + i] = (bf16_t)pr;
-                        dsa[hh * 4 + i] = (bf16_t)(p.scale * pr * (dp[hh][i] - qdel));
+                        if constexpr (SG) dsa[hh * 4 + i] = (bf16_t)fmaf(p.scale, glv[hh * 4 + i], p.scale * pr * (dp[hh][i] - qdel));
+                        else dsa[hh * 4 + i] = (bf16_t)(p.scale * pr * (dp[hh][i] - qdel));
                     }
 #pragma unroll
                 for (int nt = 0; nt < 2 * NDQ; ++nt) {
@@ -457,16 +490,16 @@ __global__ __launch_bounds__(256, (rb_regs_heavy(NDQ, NDV) ? 1 : 2)) void xna_ro
 namespace {
 bool rb_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
 
-template <int NDQ, int NDV, bool MULT, int NH>
-int launch_rows_bwd_mh(const XnaRowsBwdParams& p, hipStream_t s) {
+template <int NDQ, int NDV, bool MULT, int NH, bool SG = false>
+int launch_rows_bwd_mh(const std::conditional_t<SG, XnaRowsBwdScoresParams, XnaRowsBwdParams>& p, hipStream_t s) {
     const size_t ldsq = (size_t)4 * 32 * (NDQ * 32 + 8) * sizeof(bf16_t);
     const size_t ldsk = ldsq + (NDV > 0 ? (size_t)4 * 32 * (NDV * 32 + 8) * sizeof(bf16_t) : 0);
     static bool configured_on[64] = {};   // per instantiation and device; the attribute is idempotent, so a race only repeats it
     int devid = -1;
     const bool cacheable = hipGetDevice(&devid) == hipSuccess && devid >= 0 && devid < 64;
     if (!cacheable || !configured_on[devid]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(xna_rows_bwd_kernel<NDQ, NDV, false, MULT, NH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq) != hipSuccess ||
-            hipFuncSetAttribute(reinterpret_cast<const void*>(xna_rows_bwd_kernel<NDQ, NDV, true, MULT, 2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsk) != hipSuccess) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(xna_rows_bwd_kernel<NDQ, NDV, false, MULT, NH, SG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsq) != hipSuccess ||
+            hipFuncSetAttribute(reinterpret_cast<const void*>(xna_rows_bwd_kernel<NDQ, NDV, true, MULT, 2, SG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsk) != hipSuccess) {
             naf_set_error("naf_xna_bwd: cannot reserve %zu bytes of LDS", ldsk);
             return NAF_ERR_LAUNCH;
         }
@@ -476,15 +509,26 @@ int launch_rows_bwd_mh(const XnaRowsBwdParams& p, hipStream_t s) {
     int64_t gq = (p.ntiles[0] + 3) / 4, gk = (p.ntiles[1] * p.nsplit + 3) / 4;
     gq = gq > cap ? cap : gq;
     gk = gk > cap ? cap : gk;
-    hipLaunchKernelGGL((xna_rows_bwd_kernel<NDQ, NDV, false, MULT, NH>), dim3((uint32_t)gq), dim3(256), ldsq, s, p);   // statistics + dQ
+    hipLaunchKernelGGL((xna_rows_bwd_kernel<NDQ, NDV, false, MULT, NH, SG>), dim3((uint32_t)gq), dim3(256), ldsq, s, p);   // statistics + dQ
     const int rc = naf_check_launch("xna_rows_bwd_kernel<queries>");
     if (rc != NAF_OK) return rc;
-    hipLaunchKernelGGL((xna_rows_bwd_kernel<NDQ, NDV, true, MULT, 2>), dim3((uint32_t)gk), dim3(256), ldsk, s, p);    // dK, dV
+    hipLaunchKernelGGL((xna_rows_bwd_kernel<NDQ, NDV, true, MULT, 2, SG>), dim3((uint32_t)gk), dim3(256), ldsk, s, p);    // dK, dV
     return naf_check_launch("xna_rows_bwd_kernel<keys>");
 }
 
 template <int NDQ, int NDV>
-int launch_rows_bwd(const XnaRowsBwdParams& p, hipStream_t s) {
+int launch_rows_bwd(const XnaRowsBwdParams& p, hipStream_t s, const naf_xna_bwd_scores_args* sg) {
+    if (sg != nullptr && sg->dlogits != nullptr) {
+        if (p.mult) {
+            naf_set_error("naf_xna_bwd_scores: the row-streaming kernel takes a score gradient at integer ratios only");
+            return NAF_ERR_UNSUPPORTED;
+        }
+        XnaRowsBwdScoresParams ps;
+        static_cast<XnaRowsBwdParams&>(ps) = p;
+        ps.dl = sg->dlogits;
+        for (int i = 0; i < 4; ++i) ps.dls[i] = sg->dlogits_stride[i];
+        return p.narrow ? launch_rows_bwd_mh<NDQ, NDV, false, 1, true>(ps, s) : launch_rows_bwd_mh<NDQ, NDV, false, 2, true>(ps, s);
+    }
     if (p.mult) return launch_rows_bwd_mh<NDQ, NDV, true, 2>(p, s);
     return p.narrow ? launch_rows_bwd_mh<NDQ, NDV, false, 1>(p, s) : launch_rows_bwd_mh<NDQ, NDV, false, 2>(p, s);
 }
@@ -523,7 +567,7 @@ int naf_xna_rows_bwd_eligible(const naf_xna_bwd_args* a) {
     return 1;
 }
 
-int naf_launch_xna_rows_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s) {
+int naf_launch_xna_rows_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, const naf_xna_bwd_scores_args* sg) {
     if (!naf_xna_rows_bwd_eligible(a)) {
         naf_set_error("naf_xna_bwd: the row-streaming MFMA backward needs a square odd kernel <= 15 (<= h, w at integer ratios; 16 queries within 32 low-res columns otherwise), "
                       "Dq in {64,96,128,192,256,384,512} with Dv <= 32, or Dq = 64 with Dv in {32,64,96,128,192,256}, and 16-byte aligned "
@@ -572,22 +616,22 @@ int naf_launch_xna_rows_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t 
     const int form = rb_value_form(a);
     if (form > 0) {
         switch (form) {
-            case 1: return launch_rows_bwd<2, 1>(p, s);
-            case 2: return launch_rows_bwd<2, 2>(p, s);
-            case 3: return launch_rows_bwd<2, 3>(p, s);
-            case 4: return launch_rows_bwd<2, 4>(p, s);
-            case 6: return launch_rows_bwd<2, 6>(p, s);
-            case 8: return launch_rows_bwd<2, 8>(p, s);
+            case 1: return launch_rows_bwd<2, 1>(p, s, sg);
+            case 2: return launch_rows_bwd<2, 2>(p, s, sg);
+            case 3: return launch_rows_bwd<2, 3>(p, s, sg);
+            case 4: return launch_rows_bwd<2, 4>(p, s, sg);
+            case 6: return launch_rows_bwd<2, 6>(p, s, sg);
+            case 8: return launch_rows_bwd<2, 8>(p, s, sg);
         }
     }
     switch (a->Dq / 32) {
-        case 2: return launch_rows_bwd<2, 0>(p, s);
-        case 3: return launch_rows_bwd<3, 0>(p, s);
-        case 4: return launch_rows_bwd<4, 0>(p, s);
-        case 6: return launch_rows_bwd<6, 0>(p, s);
-        case 8: return launch_rows_bwd<8, 0>(p, s);
-        case 12: return launch_rows_bwd<12, 0>(p, s);
-        case 16: return launch_rows_bwd<16, 0>(p, s);
+        case 2: return launch_rows_bwd<2, 0>(p, s, sg);
+        case 3: return launch_rows_bwd<3, 0>(p, s, sg);
+        case 4: return launch_rows_bwd<4, 0>(p, s, sg);
+        case 6: return launch_rows_bwd<6, 0>(p, s, sg);
+        case 8: return launch_rows_bwd<8, 0>(p, s, sg);
+        case 12: return launch_rows_bwd<12, 0>(p, s, sg);
+        case 16: return launch_rows_bwd<16, 0>(p, s, sg);
     }
     naf_set_error("naf_xna_bwd: no row-streaming instantiation for Dq = %d, Dv = %d", a->Dq, a->Dv);
     return NAF_ERR_UNSUPPORTED;

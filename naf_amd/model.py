@@ -602,6 +602,14 @@ class GraphedForward:
         return self.out
 
 
+def _scores_mode(return_weights):
+    """``ops.XnaFunction``'s seventh argument for a ``return_weights`` value: "differentiable", or whether the scores are returned at all."""
+    if isinstance(return_weights, str):
+        if return_weights != "differentiable":
+            raise ValueError(f"return_weights must be a bool or 'differentiable', got {return_weights!r}")
+        return "differentiable"
+    return bool(return_weights)
+
 class NAF(nn.Module):
     """Drop-in for the reference's ``NAF`` (naf.py:72-116): same constructor, same ``state_dict``."""
 
@@ -698,14 +706,17 @@ class NAF(nn.Module):
     def forward_train(self, image, features, output_size, amp="auto", return_weights=False):
         """Differentiable forward for training (train.py:127-137): gradients reach the encoder parameters, the image
         and the features.  The attention and its backward are the HIP kernels (naf_xna_fwd / naf_xna_bwd through
-        ``ops.XnaFunction``); the conv stem, RoPE and key pooling run as torch ops so that autograd can
-        differentiate them (the fused inference stem has no backward).  In ``.train()`` mode the RoPE coordinates get the
+        ``ops.XnaFunction``); the conv stem runs as ``_HipStem`` (HIP forward and backward kernels) or, as the A/B arm, as torch ops
+        (``amp`` below); RoPE and key pooling run as HIP kernels with their own backward (``ops.RopePoolFunction``) where the stem is
+        ``_HipStem`` and the RoPE heads are the attention heads with a head dim that is a multiple of 32, as torch ops otherwise.  In ``.train()`` mode the RoPE coordinates get the
         reference's random rescale (rope.py:107-124, NAF's rope_rescale); in ``.eval()`` mode they are deterministic.  Every geometry
         has a backward kernel (``ops.xna_backward_select``): the MFMA cell kernel (integer ratio, Wo/w a multiple of 16, window <= 13
         with K/V windows inside the LDS), the row-streaming matrix-core kernel (every other integer ratio: the reference's own training
         geometry 16^2 -> 32^2, patch-14 backbones, the denoising call), the table-driven scalar kernel for the rest.
-        ``return_weights``: also returns the scaled pre-softmax scores [B, heads, Ho, Wo, k*k] of the q / k this step used, fp32, without a
-        gradient (the reference's ``return_weights`` under autograd, attentions.py:64-67; its callers only display them).
+        ``return_weights``: also returns the scaled pre-softmax scores [B, heads, Ho, Wo, k*k] of the q / k this step used, fp32.  True:
+        without a gradient (its callers only display them).  "differentiable": with a gradient that reaches q and k -- and through them the
+        stem, RoPE and the image -- as the reference's scores have one (legacy_attention, attentions.py:16-29): a loss on them (attention-map
+        regularisers, attention distillation) trains the encoder.  The backward then runs naf_xna_bwd_scores (C ABI 0.4.3).
         ``amp="auto"`` (the default, and what ``model(image, feats, size)`` uses when a gradient is wanted; round 6) trains through the
         library's own differentiable stem ``_HipStem`` whenever ``image_encoder.stem_impl == "hip"`` and the width has HIP training
         kernels -- with or without ``torch.autocast``: its contract (bf16 activations between layers, fp32 accumulation, fp64 GroupNorm
@@ -757,7 +768,7 @@ class NAF(nn.Module):
             B, C = features.shape[:2]
             v5 = features.reshape(B, heads, C // heads, h, w).permute(0, 1, 3, 4, 2).to(torch.bfloat16).contiguous()
             out_dtype = torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32
-            res = ops.XnaFunction.apply(q5, k5, v5, self.upsampler.kernel_size, self.upsampler.scale, out_dtype, bool(return_weights))
+            res = ops.XnaFunction.apply(q5, k5, v5, self.upsampler.kernel_size, self.upsampler.scale, out_dtype, _scores_mode(return_weights))
             out5, logits = res if return_weights else (res, None)
             # [B, heads, Ho, Wo, Dv] is a view of a [B, Ho, Wo, heads * Dv] buffer: hand it out as a logical NCHW view of that
             # (channels-last memory, no transpose copy of the largest tensor of the step)
@@ -787,13 +798,15 @@ class NAF(nn.Module):
         to5 = lambda t, d: t.reshape(B, heads, d, *t.shape[-2:]).permute(0, 1, 3, 4, 2).to(torch.bfloat16).contiguous()
         q5, k5, v5 = to5(xr, Dq), to5(k, Dq), to5(features, C // heads)
         out_dtype = torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32
-        res = ops.XnaFunction.apply(q5, k5, v5, self.upsampler.kernel_size, self.upsampler.scale, out_dtype, bool(return_weights))
+        res = ops.XnaFunction.apply(q5, k5, v5, self.upsampler.kernel_size, self.upsampler.scale, out_dtype, _scores_mode(return_weights))
         out5, logits = res if return_weights else (res, None)
         out = out5.permute(0, 1, 4, 2, 3).reshape(B, C, ho, wo)
         return (out, logits) if return_weights else out
 
     def forward(self, image, features, output_size, return_weights=False, *args, **kwargs):
-        """``naf(image, lr_features, target_size)`` (naf.py:104-116).  The reference's forward is always differentiable;
+        """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
+        without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
+        as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
         here the fused inference kernels run unless a gradient is actually wanted: autograd enabled AND (an input requires
         grad, or the module is in ``.train()`` mode with trainable parameters) -- then the call is ``forward_train``
         (train.py:127-137, denoising.py:213 work unchanged).  README usage (``naf.eval()`` then ``naf(...)``) and any call
@@ -803,7 +816,7 @@ class NAF(nn.Module):
                                         (self.training and any(p.requires_grad for p in self.parameters()))):
             # the library's own differentiable stem whenever it serves the width, with or without torch.autocast (round 6: the
             # bf16-activation contract is what the inference path computes); else the torch stem in the ambient precision.
-            # return_weights (attentions.py:64-67 under autograd): (out, scores) with the scores as a non-differentiable output
+            # return_weights (attentions.py:64-67 under autograd): (out, scores); True: scores without a gradient, "differentiable": with one
             return self.forward_train(image, features, output_size, amp="auto", return_weights=return_weights)
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)

@@ -20,7 +20,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import XnaArgs, XnaBwdArgs, RopePoolArgs, StemConv0Args, StemConvArgs, KeyPoolArgs, ForwardArgs, I64x3, I64x4
+from ._lib import XnaArgs, XnaBwdArgs, XnaBwdScoresArgs, RopePoolArgs, StemConv0Args, StemConvArgs, KeyPoolArgs, ForwardArgs, I64x3, I64x4
 
 _DT = {torch.bfloat16: _lib.NAF_BF16, torch.float32: _lib.NAF_F32}
 
@@ -583,6 +583,19 @@ def _fill_xna_bwd(q, k, v, dout, dq, dk, dv, ky, kx, scale) -> XnaBwdArgs:
 _BWD_PATHS = {"auto": _lib.XNA_AUTO, "mfma": _lib.XNA_MFMA, "rows": _lib.XNA_ROWS, "generic": _lib.XNA_GENERIC}
 
 
+def _scores_args(dlogits: torch.Tensor, q: torch.Tensor, ky: int, kx: int) -> XnaBwdScoresArgs:
+    """naf_xna_bwd_scores_args of a score gradient: fp32 [B, heads, Ho, Wo, ky*kx] with the slot axis contiguous (any other strides)."""
+    B, heads, Ho, Wo, _ = q.shape
+    if tuple(dlogits.shape) != (B, heads, Ho, Wo, ky * kx):
+        raise ValueError(f"xna_backward: dlogits shape {tuple(dlogits.shape)} != {(B, heads, Ho, Wo, ky * kx)}")
+    if dlogits.dtype != torch.float32 or dlogits.stride(4) != 1 or dlogits.device != q.device:
+        raise TypeError("xna_backward: dlogits must be a float32 tensor on q's device with the slot axis (the last) contiguous")
+    s = XnaBwdScoresArgs()
+    s.dlogits = dlogits.data_ptr()
+    s.dlogits_stride = _strides4(dlogits, (0, 1, 2, 3))
+    return s
+
+
 def xna_backward_supported(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size) -> bool:
     """True when ``xna_backward`` runs the MFMA cell kernel for these shapes (otherwise: the table-driven one)."""
     lib = _lib.load()
@@ -595,9 +608,10 @@ def xna_backward_supported(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tens
     return lib.naf_xna_bwd_supported(C.byref(a)) == _lib.XNA_MFMA
 
 
-def xna_backward_select(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size) -> str:
+def xna_backward_select(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size, *, dlogits: Optional[torch.Tensor] = None) -> str:
     """Which kernel ``xna_backward`` runs for these shapes: "mfma" (cell kernel), "rows" (row-streaming matrix-core kernel: the integer ratios
-    the cell kernel does not take -- the reference's denoising call, its own training geometry, patch-14 backbones) or "generic" (table-driven scalar kernel)."""
+    the cell kernel does not take -- the reference's denoising call, its own training geometry, patch-14 backbones) or "generic" (table-driven scalar kernel).
+    ``dlogits``: the score gradient ``xna_backward`` would get (``naf_xna_bwd_scores_supported``: non-integer ratios then run the table-driven kernel)."""
     lib = _lib.load()
     ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
     a = _fill_xna_bwd(q, k_lr, v_lr, q, q, q, q, ky, kx, None)      # shape / alignment query only
@@ -605,6 +619,11 @@ def xna_backward_select(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor,
     Dv = v_lr.shape[-1]
     a.dout_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
     a.dq_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
+    if dlogits is not None:
+        sel = lib.naf_xna_bwd_scores_supported(C.byref(a), C.byref(_scores_args(dlogits, q, ky, kx)))
+        if sel < 0:
+            _lib.check(-sel, "naf_xna_bwd_scores_supported")
+        return {_lib.XNA_MFMA: "mfma", _lib.XNA_ROWS: "rows"}.get(sel, "generic")
     sel = lib.naf_xna_bwd_supported(C.byref(a))
     if sel < 0:
         _lib.check(-sel, "naf_xna_bwd_supported")
@@ -629,13 +648,16 @@ def xna_backward_chunks(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor,
 
 
 def xna_backward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, dout: torch.Tensor, kernel_size, *,
-                 scale: Optional[float] = None, path: str = "auto"):
+                 scale: Optional[float] = None, path: str = "auto", dlogits: Optional[torch.Tensor] = None):
     """Gradients of ``xna_forward`` w.r.t. q, k_lr, v_lr given ``dout`` (5-D [B, heads, Ho, Wo, Dv], any strides with
     Dv contiguous; cast to bf16).  Returns (dq bf16 [B,heads,Ho,Wo,Dq] view of a channels-last buffer,
     dk_lr fp32 [B,heads,h,w,Dq] view, dv_lr fp32 [B,heads,h,w,Dv] view).  ``path`` (naf_xna_bwd_args.path): "auto", or insist on "mfma"
     (cell kernels), "rows" (row-streaming matrix-core kernel) or "generic" -- the table-driven scalar kernel, which serves EVERY shape and
     is the independent reference of the parity tests (until 0.4.1 "generic" only withheld the row-streaming kernel's workspace: shapes the
-    cell kernels take ran the cell kernel again, and the tests that compared the two compared it with itself)."""
+    cell kernels take ran the cell kernel again, and the tests that compared the two compared it with itself).
+    ``dlogits`` (C ABI 0.4.3, naf_xna_bwd_scores): the gradient of the scaled scores ``xna_forward(..., return_logits=True)`` returns, fp32
+    [B, heads, Ho, Wo, ky*kx] with the slot axis contiguous; it adds scale * dlogits to dS, so it reaches dq and dk_lr (dv_lr does not depend on
+    it).  None issues exactly the plain backward."""
     for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
         _gpu(t, n)
         if t.dtype != torch.bfloat16 or t.dim() != 5 or t.stride(4) != 1:
@@ -656,6 +678,22 @@ def xna_backward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, dout: 
         raise ValueError(f"xna_backward: path must be one of {sorted(_BWD_PATHS)}, got {path!r}")
     a = _fill_xna_bwd(q, k_lr, v_lr, dout, dq, dk, dv, ky, kx, scale)
     a.path = _BWD_PATHS[path]
+    if dlogits is not None:
+        sa = _scores_args(dlogits, q, ky, kx)
+        sel = lib.naf_xna_bwd_scores_supported(C.byref(a), C.byref(sa))
+        if sel < 0:
+            _lib.check(-sel, "naf_xna_bwd_scores_supported")
+        if sel in (_lib.XNA_GENERIC, _lib.XNA_ROWS):
+            iy = device_index_table(Ho, h, ky, dev)
+            ix = device_index_table(Wo, w, kx, dev)
+            a.idx_y, a.idx_x = iy.data_ptr(), ix.data_ptr()
+        if sel == _lib.XNA_ROWS:
+            ws = torch.empty(int(lib.naf_xna_bwd_workspace_bytes(C.byref(a))), dtype=torch.uint8, device=dev)
+            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        with torch.cuda.device(dev), _Timed("xna_bwd_scores"):
+            rc = lib.naf_xna_bwd_scores(C.byref(a), C.byref(sa), _stream(q))
+        _lib.check(rc, "naf_xna_bwd_scores")
+        return dq, dk.permute(0, 3, 1, 2, 4), dv.permute(0, 3, 1, 2, 4)
     sel = lib.naf_xna_bwd_supported(C.byref(a))
     if sel < 0:
         _lib.check(-sel, "naf_xna_bwd_supported")
@@ -715,28 +753,49 @@ class RopePoolFunction(torch.autograd.Function):
 
 
 class XnaFunction(torch.autograd.Function):
-    """Differentiable ``xna_forward``: forward = naf_xna_fwd, backward = naf_xna_bwd (MFMA or table-driven kernels)."""
+    """Differentiable ``xna_forward``: forward = naf_xna_fwd, backward = naf_xna_bwd (MFMA or table-driven kernels).  Optional seventh
+    argument: True = also return the scaled scores, without a gradient; "differentiable" = also return them as a differentiable output, whose
+    gradient the backward hands to naf_xna_bwd_scores (it reaches q and k_lr)."""
 
     @staticmethod
     def forward(ctx, q, k_lr, v_lr, kernel_size, scale, out_dtype, *rest):
-        return_logits = bool(rest[0]) if rest else False       # optional seventh argument
+        mode = rest[0] if rest else False
+        return_logits = mode == "differentiable" or (not isinstance(mode, str) and bool(mode))
         ctx.nrest = len(rest)
+        ctx.differentiable = mode == "differentiable"
+        # an unused output's gradient arrives as None instead of zeros: a loss on `out` alone runs the plain backward, one on the scores
+        # alone a zero dout
+        ctx.set_materialize_grads(False)
         ctx.save_for_backward(q, k_lr, v_lr)
         ctx.kernel_size, ctx.scale = kernel_size, scale
         if return_logits:
             # return_weights on a gradient-enabled call (attentions.py:64-67 works under autograd): the scaled pre-softmax scores of the
-            # very q / k this differentiable step uses, as a second output WITHOUT a gradient (nothing in the reference's callers
-            # differentiates through them: notebooks/attention_maps.ipynb reads them for display)
+            # very q / k this differentiable step uses.  True: WITHOUT a gradient (notebooks/attention_maps.ipynb reads them for display);
+            # "differentiable": with one, as legacy_attention's scores have (attentions.py:16-29) -- losses on the attention maps
             out, logits = xna_forward(q, k_lr, v_lr, kernel_size, out_dtype=out_dtype, path="auto", scale=scale, return_logits=True)
-            ctx.mark_non_differentiable(logits)
+            if not ctx.differentiable:
+                ctx.mark_non_differentiable(logits)
             return out, logits
         return xna_forward(q, k_lr, v_lr, kernel_size, out_dtype=out_dtype, path="auto", scale=scale)
 
     @staticmethod
-    def backward(ctx, dout, *unused):
+    def backward(ctx, dout, *rest):
+        if not any(ctx.needs_input_grad[:3]):
+            return (None,) * (6 + ctx.nrest)
         q, k_lr, v_lr = ctx.saved_tensors
-        dq, dk, dv = xna_backward(q, k_lr, v_lr, dout, ctx.kernel_size, scale=ctx.scale)
-        return (dq, dk.to(k_lr.dtype), dv.to(v_lr.dtype), None, None, None) + (None,) * ctx.nrest
+        dlogits = rest[0] if ctx.differentiable and rest else None
+        if dout is None and dlogits is None:
+            return (None,) * (6 + ctx.nrest)
+        if dout is None:
+            B, heads, Ho, Wo, _ = q.shape
+            dout = torch.zeros((B, heads, Ho, Wo, v_lr.shape[-1]), dtype=torch.bfloat16, device=q.device)
+        if dlogits is not None and dlogits.stride(-1) != 1:   # any other strides (0 where a loss reduced over an axis) serve as they are
+            dlogits = dlogits.contiguous()
+        dq, dk, dv = xna_backward(q, k_lr, v_lr, dout, ctx.kernel_size, scale=ctx.scale,
+                                  dlogits=None if dlogits is None else dlogits.float())
+        need = ctx.needs_input_grad
+        return ((dq if need[0] else None), (dk.to(k_lr.dtype) if need[1] else None), (dv.to(v_lr.dtype) if need[2] else None),
+                None, None, None) + (None,) * ctx.nrest
 
 
 def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables, out_dtype=torch.bfloat16,
