@@ -58,7 +58,10 @@ extern "C" {
  * backward takes cells of 14 / 15 / 28 / 30 ... pixels per row at windows up to 9 x 9 (naf_xna_bwd_supported then says NAF_XNA_MFMA where
  * 0.4.1 said NAF_XNA_ROWS: no tables / workspace needed any more).
  * 0.4.3 (binary compatible with 0.4.x: a new entry point only): naf_xna_bwd_scores / naf_xna_bwd_scores_supported -- the attention backward
- * with a gradient of the scaled scores naf_xna_fwd returns in `logits` (naf_xna_bwd_scores_args), so that a loss on the scores trains q and k. */
+ * with a gradient of the scaled scores naf_xna_fwd returns in `logits` (naf_xna_bwd_scores_args), so that a loss on the scores trains q and k.
+ * After 0.4.3, same version number (binary compatible: new entry points with a struct of their own, nothing else moves): naf_xna_head_select /
+ * naf_xna_head_fwd / naf_xna_head_workspace_bytes -- the attention with a linear head folded in (naf_xna_head_args).  A host detects them by symbol
+ * (dlsym), not by naf_version(). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -445,6 +448,55 @@ int naf_xna_union_plan(const naf_xna_args* a, int32_t out[7]);
 /* Scratch bytes the call needs (currently always 0; kept so callers need not change later). */
 size_t naf_workspace_bytes(const naf_xna_args* a);
 int naf_xna_fwd(const naf_xna_args* a, naf_stream_t stream);
+
+/* ---- attention with a linear head folded in (added after 0.4.3; detect by symbol) -----------------------
+ * What the reference's users put on the upsampled features is a 1x1 convolution (evaluation/eval_seg_probing.py:56,104-111:
+ * nn.Conv2d(embed_dim, num_classes, 1) on model(image, feats, (H, W))).  The attention is linear in the values and its weights sum to
+ * one, so with W [N, C], b [N] and attention head g owning channels [g*Dv, (g+1)*Dv):
+ *     head(naf(V))[n, px] = b[n] + sum_g sum_slot P_g[px, slot] * PV_g[n, cell(slot)],      PV_g = W[:, g*Dv:(g+1)*Dv] @ V_g
+ * PV lives on the low-res grid; this entry runs the attention of every head on it and SUMS the heads into one N-channel output, so the
+ * [B, C, Ho, Wo] tensor is never written.
+ *   q, k_lr   as in naf_xna_args (bf16, strides {b, head, y, x}, last dim contiguous, Dq = 64)
+ *   pv_lr     device bf16 [B, heads, h, w, Npad], Npad = N rounded up to a multiple of 16, strides {b, head, y, x}, last dim contiguous;
+ *             channels N .. Npad-1 are read and must be finite (the caller zeroes them); they are never stored
+ *   bias      device float [N] added in fp32, or NULL
+ *   out       device [B, Ho, Wo, N] of out_dtype (NAF_BF16 / NAF_F32), element strides {b, y, x}, channel axis contiguous
+ *   rope_tab_y / rope_tab_x   rotate-on-load exactly as in naf_xna_args (q is then the un-rotated channels-last guidance)
+ * Kernel (xna_head_kernel.h): one workgroup per (batch, low-res cell) loops over the heads; each head's softmax is normalised in fp32
+ * BEFORE its weights are rounded to bf16 (what naf_xna_fwd's cell kernel does per head), and the heads add up in fp32 accumulators.
+ * Served: square odd window 3 .. 15, Dq = 64, integer ratio whose cell rows are row tiles (Wo/w a multiple of 16, or 14, 15, 28, 30 ...),
+ * h, w >= window, any head count, 1 <= N <= 256, 16-byte aligned q / k_lr / pv_lr with strides that are multiples of 8 elements.
+ * naf_xna_head_select: NAF_XNA_HEAD_FUSED when naf_xna_head_fwd serves the arguments, else a negative naf_status (with naf_last_error):
+ * -NAF_ERR_INVALID for arguments no kernel could serve (NULL, N outside 1 .. 256, even window ...), -NAF_ERR_UNSUPPORTED for a valid
+ * request outside the list above -- the caller then composes naf_xna_fwd on pv_lr (fp32 output) with a sum over the heads.  A pure
+ * host-side query: pointers are checked, never read.  path: NAF_XNA_HEAD_AUTO or NAF_XNA_HEAD_FUSED (the same answer today; AUTO is where a
+ * measured "the composition is faster here" would go).  scale <= 0 selects Dq^-0.5.  Caller-owned memory and stream; capturable. */
+enum naf_xna_head_path {
+    NAF_XNA_HEAD_AUTO = 0,
+    NAF_XNA_HEAD_FUSED = 1
+};
+typedef struct naf_xna_head_args {
+    const void* q;
+    const void* k_lr;
+    const void* pv_lr;
+    const float* bias;
+    void* out;
+    const float* rope_tab_y;
+    const float* rope_tab_x;
+    int32_t B, heads, Ho, Wo, h, w, Dq, N, ky, kx;
+    int32_t out_dtype; /* naf_dtype */
+    int32_t path;      /* naf_xna_head_path */
+    float scale;
+    int32_t reserved;
+    int64_t q_stride[4];
+    int64_t k_stride[4];
+    int64_t pv_stride[4];
+    int64_t o_stride[3];
+} naf_xna_head_args;
+int naf_xna_head_select(const naf_xna_head_args* a);
+/* Scratch bytes the call needs (0 today; kept so callers need not change later). */
+size_t naf_xna_head_workspace_bytes(const naf_xna_head_args* a);
+int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream);
 
 /* ---- cross-scale neighbourhood attention backward --------------------------------------------------
  * Replaces what autograd runs through legacy_attention (attentions.py:16-29: the backward of na2d_qk, the

@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("NAF_HIP_LIB") or os.path.join(os.path.dirname(os.path
 HEADER_VERSION = 403          # NAF_HIP_VERSION of the include/naf_hip.h these ctypes mirrors were written against
 NAF_BF16, NAF_F32 = 0, 1
 XNA_AUTO, XNA_MFMA, XNA_GENERIC, XNA_UNION, XNA_ROWS = 0, 1, 2, 3, 4
+XNA_HEAD_AUTO, XNA_HEAD_FUSED = 0, 1            # naf_xna_head_path
 
 I64x4 = C.c_int64 * 4
 
@@ -43,6 +44,18 @@ class XnaArgs(C.Structure):
 
 
 I64x3 = C.c_int64 * 3
+
+
+class XnaHeadArgs(C.Structure):
+    """naf_xna_head_args (added after 0.4.3, detected by symbol): the attention with a linear head folded in."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k_lr", C.c_void_p), ("pv_lr", C.c_void_p), ("bias", C.c_void_p), ("out", C.c_void_p),
+        ("rope_tab_y", C.c_void_p), ("rope_tab_x", C.c_void_p),
+        ("B", C.c_int32), ("heads", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("h", C.c_int32),
+        ("w", C.c_int32), ("Dq", C.c_int32), ("N", C.c_int32), ("ky", C.c_int32), ("kx", C.c_int32),
+        ("out_dtype", C.c_int32), ("path", C.c_int32), ("scale", C.c_float), ("reserved", C.c_int32),
+        ("q_stride", I64x4), ("k_stride", I64x4), ("pv_stride", I64x4), ("o_stride", I64x3),
+    ]
 
 
 class StemConv0Args(C.Structure):
@@ -207,6 +220,9 @@ SIGNATURES = {
     "naf_xna_union_plan": (C.c_int, [C.POINTER(XnaArgs), C.POINTER(C.c_int32)]),
     "naf_workspace_bytes": (C.c_size_t, [C.POINTER(XnaArgs)]),
     "naf_xna_fwd": (C.c_int, [C.POINTER(XnaArgs), C.c_void_p]),
+    "naf_xna_head_select": (C.c_int, [C.POINTER(XnaHeadArgs)]),
+    "naf_xna_head_workspace_bytes": (C.c_size_t, [C.POINTER(XnaHeadArgs)]),
+    "naf_xna_head_fwd": (C.c_int, [C.POINTER(XnaHeadArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -351,6 +351,46 @@ int naf_xna_fwd(const naf_xna_args* a, naf_stream_t stream) {
     return naf_launch_xna_generic(a, scale, static_cast<hipStream_t>(stream));
 }
 
+// ---- attention with a linear head folded in (after 0.4.3) ----------------------------------------------------
+static int xna_head_validate(const naf_xna_head_args* a) {
+    NAF_REQUIRE(a != nullptr, "naf_xna_head_fwd: args is NULL");
+    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && a->out, "naf_xna_head_fwd: NULL tensor pointer");
+    NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 && a->Dq > 0, "naf_xna_head_fwd: non-positive size");
+    NAF_REQUIRE(a->N >= 1 && a->N <= 256, "naf_xna_head_fwd: N must be in 1 .. 256, got %d", a->N);
+    NAF_REQUIRE(a->out_dtype == NAF_BF16 || a->out_dtype == NAF_F32, "naf_xna_head_fwd: out_dtype %d", a->out_dtype);
+    NAF_REQUIRE(a->ky > 0 && a->kx > 0 && (a->ky & 1) && (a->kx & 1), "naf_xna_head_fwd: kernel size must be odd, got %dx%d", a->ky, a->kx);
+    NAF_REQUIRE(a->Ho >= a->h && a->Wo >= a->w, "naf_xna_head_fwd: output %dx%d smaller than feature grid %dx%d (dilation 0)", a->Ho, a->Wo, a->h, a->w);
+    NAF_REQUIRE((int64_t)a->ky * (a->Ho / a->h) <= a->Ho && (int64_t)a->kx * (a->Wo / a->w) <= a->Wo,
+                "naf_xna_head_fwd: kernel_size * dilation exceeds the output extent (k=%dx%d, dilation=%dx%d, out=%dx%d)",
+                a->ky, a->kx, a->Ho / a->h, a->Wo / a->w, a->Ho, a->Wo);
+    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "naf_xna_head_fwd: path %d", a->path);
+    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_head_fwd: rope_tab_y and rope_tab_x must be given together");
+    NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "naf_xna_head_fwd: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)",
+                (long long)a->pv_stride[3], a->N);
+    NAF_REQUIRE(a->o_stride[2] >= a->N, "naf_xna_head_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
+    return NAF_OK;
+}
+
+int naf_xna_head_select(const naf_xna_head_args* a) {
+    int rc = xna_head_validate(a);
+    if (rc != NAF_OK) return -rc;
+    rc = naf_xna_head_eligible(a);
+    if (rc != NAF_OK) return -rc;
+    return NAF_XNA_HEAD_FUSED;
+}
+
+size_t naf_xna_head_workspace_bytes(const naf_xna_head_args* a) {
+    (void)a;
+    return 0;
+}
+
+int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_head_select(a);
+    if (sel < 0) return -sel;
+    const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
+    return naf_launch_xna_head(a, scale, static_cast<hipStream_t>(stream));
+}
+
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_bwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->dout && a->dq && a->dk_lr && a->dv_lr, "naf_xna_bwd: NULL tensor pointer");

@@ -1,0 +1,304 @@
+// Cross-scale neighbourhood attention with a linear head folded in, head-summed MFMA cell kernel (gfx950 / CDNA4).
+//
+// out[b, y, x, n] = bias[n] + sum_g sum_slot P_g[px, slot] * PV_g[cell(slot), n]       (include/naf_hip.h: naf_xna_head_args)
+// PV_g = W[:, g*Dv:(g+1)*Dv] @ V_g is formed by the host on the low-res grid; the [B, C, Ho, Wo] tensor never exists.
+//
+// The per-head arithmetic is xna_mfma_kernel.h's (read its header comment first): S^T = K . Q on v_mfma_f32_16x16x32_bf16 with K rows
+// from LDS and Q straight from memory, fp32 softmax over the key slots, O^T += PV^T . P^T with PV^T through ds_read_b64_tr_b16.  What the
+// head sum changes:
+//   * one workgroup (8 waves) = one (batch, low-res cell); it LOOPS OVER THE HEADS.  Per head it stages that head's K window
+//     [slots][64 (+8)] and PV window [slots][NCT*16 (+16)] in LDS (pad channels up to NCT*16 are zero-filled, never stored) and every wave
+//     runs the head on its TPW 16-query row tiles.  The O^T accumulators of a tile are NOT cleared between heads.
+//   * so 1/sum of a head cannot be applied to the accumulators at the end.  P is normalised in fp32 BEFORE it is packed to bf16 -- the
+//     choice the per-head kernel already makes (softmax, then attn . V, as the reference orders it): every head's contribution then
+//     carries exactly the rounding of one naf_xna_fwd call, the head sum adds nothing but fp32 additions, and no second set of
+//     accumulators (a per-head partial to scale and add) is needed.  sum >= 1 (the max slot contributes exp2(0)), so a peaked softmax
+//     normalises as safely as a flat one.
+//   * per head: the head's queries are requested, then barrier, window staging (one L2 round trip), barrier, tiles.  Requesting the NEXT
+//     head's queries and windows into registers before the current head's tiles (software pipelining) was built and measured: 146
+//     registers instead of 120 (one workgroup per CU instead of two), G1 / N = 21 0.224 -> 0.266 ms, N = 151 0.667 -> 0.644 ms; not kept
+//     (profiles/head_fused.txt).  The kernel is bound by instruction issue per (tile, head), not by memory latency.
+//   * a round covers NW * TPW tiles of the cell (16 x 16 pixels at the default 8 x 2: the whole cell); larger cells take several rounds
+//     and re-stage the windows per round (L2 hits).
+//   * all heads of a pixel are read by the same workgroup: with channels-last guidance a workgroup reads, head by head, every 128-byte run of
+//     its pixels' 512-byte (heads x 64 x bf16) rows: whole rows in the end, from one CU.  Rotate-on-load as in the cell kernel: the tile's RoPE table rows are fetched once per round (they
+//     do not depend on the head) and applied with naf_rope_rotate, the same arithmetic and rounding as naf_rope_pool_fwd's.
+//   * the bias is added in the epilogue in fp32; a lane stores its 4 consecutive channels of its own pixel, channels >= N masked.
+#pragma once
+#include "xna_mfma_kernel.h"
+
+struct XnaHeadParams {
+    const bf16_t* q;
+    const bf16_t* k;
+    const bf16_t* pv;
+    const float* bias;   // [N] or nullptr
+    void* out;
+    const float* tab_y;  // rotate-on-load: RoPE tables [Ho][2][16] / [Wo][2][16], or nullptr
+    const float* tab_x;
+    int32_t B, heads, Ho, Wo, h, w, dy, dx;
+    int32_t N;           // stored channels
+    int32_t npad;        // channels a pv row holds (N rounded up to 16)
+    uint32_t nblocks;
+    float scale_log2e;
+    int64_t qs[4], ks[4], vs[4];  // {b, head, y, x} element strides
+    int64_t os[3];                // {b, y, x}
+};
+
+constexpr int XNA_HEAD_NW = 8;   // waves per workgroup
+// channel tiles (16 channels each) a workgroup accumulates: the smallest of these that holds Npad
+constexpr int xna_head_nct(int npad) { return npad <= 32 ? 2 : npad <= 64 ? 4 : npad <= 160 ? 10 : 16; }
+// 16-query tiles a wave carries through the head loop (accumulators: TPW * NCT * 4 registers)
+constexpr int xna_head_tpw(int ks, int nct) { return (nct >= 10 && ks >= 11) ? 1 : 2; }
+constexpr size_t xna_head_lds_for(int ks, int nct) { return (size_t)(ks * ks) * (72 + nct * 16 + 16) * 2; }
+
+template <int KS, int NCT, typename OutT>
+__global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHeadParams p) {
+    constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
+    constexpr int TPW = xna_head_tpw(KS, NCT);
+    using G = XnaGeom<KS, 1>;
+    constexpr int NSLOT = G::NSLOT, MT = G::MT, KST = G::KST, KROW = G::KROW;
+    constexpr int DVT = NCT * 16, VROW = XnaVRow<DVT>::VROW, VCH = DVT / 8;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
+    bf16_t* Vs = Ks + NSLOT * KROW;
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15;  // MFMA column (query within the tile) / A-row index (key or channel)
+    const int grp = lane >> 4;  // MFMA k-group / result row group
+
+    uint32_t L = xna_block_order(blockIdx.x, p.nblocks, 16, 1u);
+    const int cx = L % p.w;
+    L /= p.w;
+    const int cy = L % p.h;
+    const int b = L / p.h;
+    const int y0 = min(max(cy - KS / 2, 0), p.h - KS);   // the cell's clamped window
+    const int x0 = min(max(cx - KS / 2, 0), p.w - KS);
+
+    const int tpr = (p.dx + 15) >> 4;      // row tiles per cell row (host: xna_row_tiles_ok(dx))
+    const int ntile = p.dy * tpr;          // <= 1024 (host)
+    const uint32_t tmagic = (1u << 20) / (uint32_t)tpr + 1u;   // t / tpr for t, tpr <= 1024
+    const bool rope = p.tab_y != nullptr;
+    const bf16_t* q_cell = p.q + b * p.qs[0] + (int64_t)(cy * p.dy) * p.qs[2] + (int64_t)(cx * p.dx) * p.qs[3];
+    OutT* o_cell = reinterpret_cast<OutT*>(p.out) + b * p.os[0] + (int64_t)(cy * p.dy) * p.os[1] + (int64_t)(cx * p.dx) * p.os[2];
+    const bf16_t* kb = p.k + b * p.ks[0];
+    const bf16_t* vb = p.pv + b * p.vs[0];
+
+    // key slots >= NSLOT are not stored: their reads are clamped to the last real row, their logits masked, P = 0
+    auto ka_of = [&](int mt) __attribute__((always_inline)) {
+        const int row = (mt * 16 + 15 < NSLOT) ? mt * 16 + col : min(mt * 16 + col, NSLOT - 1);
+        return Ks + row * KROW + grp * 8;
+    };
+    auto va_of = [&](int blk) __attribute__((always_inline)) {
+        const int r = blk * 16 + grp * 4 + (col >> 2);
+        const int row = (blk * 16 + 15 < NSLOT) ? r : min(r, NSLOT - 1);
+        return Vs + row * VROW + (col & 3) * 4;
+    };
+
+    for (int t0 = 0; t0 < ntile; t0 += NW * TPW) {
+        // this wave's tiles of the round: t0 + u * NW + wave (wave-uniform); a tile past the cell is computed on clamped
+        // addresses and never stored
+        int tyv[TPW], tx0v[TPW];
+        bool livev[TPW];
+        const bf16_t* qpv[TPW];
+        f32x4_t cs[TPW][4] = {};
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            const int tt = t0 + u * NW + wave;
+            livev[u] = tt < ntile;
+            const int ttc = min(tt, ntile - 1);
+            tyv[u] = (int)(((uint32_t)ttc * tmagic) >> 20);
+            tx0v[u] = (ttc - tyv[u] * tpr) * 16;
+            const int xl = min(tx0v[u] + col, p.dx - 1);   // lanes past a partial last tile re-read its last pixel
+            qpv[u] = q_cell + (int64_t)tyv[u] * p.qs[2] + (int64_t)xl * p.qs[3] + grp * 8;
+            if (rope) {
+                // head dims [grp*8, +8) and their partners +32: dims < 16 turn with the row angle, dims >= 16 with the column angle
+                const float* tr = ((grp >> 1) ? p.tab_x + (int64_t)(cx * p.dx + xl) * 32 : p.tab_y + (int64_t)(cy * p.dy + tyv[u]) * 32) + (grp & 1) * 8;
+                cs[u][0] = *reinterpret_cast<const f32x4_t*>(tr);
+                cs[u][1] = *reinterpret_cast<const f32x4_t*>(tr + 4);
+                cs[u][2] = *reinterpret_cast<const f32x4_t*>(tr + 16);
+                cs[u][3] = *reinterpret_cast<const f32x4_t*>(tr + 20);
+            }
+        }
+        f32x4_t acc[TPW][NCT];
+#pragma unroll
+        for (int u = 0; u < TPW; ++u)
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) acc[u][ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+        for (int head = 0; head < p.heads; ++head) {
+            // the head's queries are requested first: their latency hides under the window staging and the barrier
+            bf16x8_t qf[TPW][2];
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                const bf16_t* qp = qpv[u] + head * p.qs[1];
+                qf[u][0] = *reinterpret_cast<const bf16x8_t*>(qp);
+                qf[u][1] = *reinterpret_cast<const bf16x8_t*>(qp + 32);
+            }
+            __syncthreads();   // every wave is done with the previous head's windows
+            {
+                // ---- stage the K and PV windows (L2 -> registers -> LDS): all loads of a batch before its first LDS write
+                const bf16_t* kh = kb + head * p.ks[1];
+                const bf16_t* vh = vb + head * p.vs[1];
+                constexpr int KTOT = NSLOT * 8, VTOT = NSLOT * VCH;
+                constexpr int KIT = (KTOT + NT - 1) / NT, VIT = (VTOT + NT - 1) / NT;
+                constexpr int BATCH = 8;
+                const int vch_mem = p.npad >> 3;   // 16-byte chunks a pv row holds in memory; the rest of the LDS row is zero
+#pragma unroll
+                for (int j0 = 0; j0 < KIT + VIT; j0 += BATCH) {
+                    u32x4_t val[BATCH];
+#pragma unroll
+                    for (int e = 0; e < BATCH; ++e) {
+                        const int j = j0 + e;
+                        if (j < KIT) {
+                            const int i = min(j * NT + tid, KTOT - 1);
+                            const int key = i >> 3, c = i & 7;
+                            const int ry = key / KS, rx = key - ry * KS;
+                            val[e] = *reinterpret_cast<const u32x4_t*>(kh + (int64_t)(y0 + ry) * p.ks[2] + (int64_t)(x0 + rx) * p.ks[3] + c * 8);
+                        } else if (j < KIT + VIT) {
+                            const int i = min((j - KIT) * NT + tid, VTOT - 1);
+                            const int key = i / VCH, c = i - key * VCH;
+                            const int ry = key / KS, rx = key - ry * KS;
+                            const u32x4_t ld = *reinterpret_cast<const u32x4_t*>(vh + (int64_t)(y0 + ry) * p.vs[2] + (int64_t)(x0 + rx) * p.vs[3] + min(c, vch_mem - 1) * 8);
+                            val[e] = c < vch_mem ? ld : u32x4_t{0u, 0u, 0u, 0u};
+                        }
+                    }
+#pragma unroll
+                    for (int e = 0; e < BATCH; ++e) {
+                        const int j = j0 + e;
+                        if (j < KIT) {
+                            const int i = j * NT + tid;
+                            if ((KTOT % NT == 0) || i < KTOT) *reinterpret_cast<u32x4_t*>(Ks + (i >> 3) * KROW + (i & 7) * 8) = val[e];
+                        } else if (j < KIT + VIT) {
+                            const int i = (j - KIT) * NT + tid;
+                            const int key = i / VCH, c = i - key * VCH;
+                            if ((VTOT % NT == 0) || i < VTOT) *reinterpret_cast<u32x4_t*>(Vs + key * VROW + c * 8) = val[e];
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u]) continue;   // wave-uniform
+                if (rope) {
+#pragma unroll
+                    for (int i = 0; i < 8; ++i) {
+                        float o1, o2;
+                        naf_rope_rotate((float)qf[u][0][i], (float)qf[u][1][i], cs[u][i >> 2][i & 3], cs[u][2 + (i >> 2)][i & 3], o1, o2);
+                        qf[u][0][i] = (bf16_t)o1;
+                        qf[u][1][i] = (bf16_t)o2;
+                    }
+                }
+                // ---- S^T = K . Q^T: lane (col, grp) gets key slots mt*16 + grp*4 + r of query col ----
+                f32x4_t s[MT];
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt) {
+                    s[mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                    for (int ks = 0; ks < 2; ++ks) {
+                        const bf16x8_t ka = *reinterpret_cast<const bf16x8_t*>(ka_of(mt) + ks * 32);
+                        s[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[u][ks], s[mt], 0, 0, 0);
+                    }
+                }
+                // ---- softmax over the key slots, fp32; P is normalised before it is rounded to bf16 (see the header comment) ----
+                float m = -INFINITY;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        if (mt * 16 + 15 >= NSLOT) {   // tile contains pad slots: mask them
+                            const bool valid = (mt * 16 + r + grp * 4) < NSLOT;
+                            s[mt][r] = valid ? s[mt][r] : -INFINITY;
+                        }
+                        m = fmaxf(m, s[mt][r]);
+                    }
+                m = naf_rows_max(m);
+                float sum = 0.f;
+                const float mc = m * p.scale_log2e;
+#pragma unroll
+                for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float e = __builtin_amdgcn_exp2f(fmaf(s[mt][r], p.scale_log2e, -mc));
+                        s[mt][r] = e;
+                        sum += e;
+                    }
+                sum = naf_rows_sum(sum);
+                const float inv = __builtin_amdgcn_rcpf(sum);   // sum >= 1
+                // pack P to bf16 B-fragments: k index (g, j) <-> slot ks*32 + (j>>2)*16 + g*4 + (j&3)
+                bf16x8_t pf[KST];
+#pragma unroll
+                for (int ks = 0; ks < KST; ++ks)
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) pf[ks][j] = (bf16_t)(s[2 * ks + (j >> 2)][j & 3] * inv);
+                // ---- O^T += PV^T . P^T: lane (col, grp) owns channels ct*16 + grp*4 + r of query col ----
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                    for (int ks = 0; ks < KST; ++ks) {
+                        const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((NAF_LDS bf16x4_t*)(va_of(ks * 2) + ct * 16));
+                        const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((NAF_LDS bf16x4_t*)(va_of(ks * 2 + 1) + ct * 16));
+                        bf16x8_t a;
+                        a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
+                        a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
+                        acc[u][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pf[ks], acc[u][ct], 0, 0, 0);
+                    }
+                    // wide heads: keep the scheduler from hoisting every channel tile's PV^T fragments above the first MFMA (it spills)
+                    if constexpr (NCT * KST >= 40) __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+        }
+
+        // ---- epilogue: + bias (fp32), store the N real channels of this lane's pixel ----
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            if (!livev[u] || tx0v[u] + col >= p.dx) continue;
+            OutT* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + col) * p.os[2];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ch = ct * 16 + grp * 4 + r;
+                    if (ch < p.N) op[ch] = (OutT)(acc[u][ct][r] + (p.bias != nullptr ? p.bias[ch] : 0.f));
+                }
+            }
+        }
+    }
+}
+
+template <int KS, int NCT, typename OutT>
+static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s) {
+    constexpr size_t lds = xna_head_lds_for(KS, NCT);
+    static_assert(lds <= 160 * 1024, "LDS budget");
+    auto kern = xna_head_kernel<KS, NCT, OutT>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+            return NAF_ERR_LAUNCH;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p);
+    return naf_check_launch("xna_head_kernel");
+}
+
+template <int KS>
+static int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s) {
+    const int nct = xna_head_nct(p.npad);
+#define NAF_HEAD_CASE(C)                                                            \
+    if (nct == C) {                                                                 \
+        if (out_dtype == NAF_BF16) return xna_head_launch_one<KS, C, bf16_t>(p, s); \
+        return xna_head_launch_one<KS, C, float>(p, s);                             \
+    }
+    NAF_HEAD_CASE(2)
+    NAF_HEAD_CASE(4)
+    NAF_HEAD_CASE(10)
+    NAF_HEAD_CASE(16)
+#undef NAF_HEAD_CASE
+    naf_set_error("xna_head: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
+    return NAF_ERR_UNSUPPORTED;
+}

@@ -610,6 +610,51 @@ def _scores_mode(return_weights):
         return "differentiable"
     return bool(return_weights)
 
+_HEAD_FORMS = "an nn.Conv2d with a 1x1 kernel, an nn.Linear, or a (weight, bias_or_None) pair with weight [N, C] or [N, C, 1, 1]"
+
+
+def _linear_head(head, channels: int):
+    """(weight [N, C], bias [N] or None) of a linear head on ``channels`` features; TypeError for anything that is not one of the accepted
+    forms, ValueError for an accepted form that is not a plain linear map of those channels.  Host-side checks only."""
+    if isinstance(head, nn.Conv2d):
+        pad = head.padding
+        pad_ok = pad in ("valid", "same") if isinstance(pad, str) else all(int(v) == 0 for v in pad)
+        if tuple(head.kernel_size) != (1, 1) or tuple(head.stride) != (1, 1) or head.groups != 1 or tuple(head.dilation) != (1, 1) or not pad_ok:
+            raise ValueError(f"head: the convolution must be a plain 1x1 one (kernel 1, stride 1, no padding, dilation 1, groups 1), got {head}")
+        weight, bias = head.weight[:, :, 0, 0], head.bias
+    elif isinstance(head, nn.Linear):
+        weight, bias = head.weight, head.bias
+    elif isinstance(head, (tuple, list)) and len(head) == 2 and isinstance(head[0], torch.Tensor) and (head[1] is None or isinstance(head[1], torch.Tensor)):
+        weight, bias = head
+        if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+            weight = weight[:, :, 0, 0]
+        if weight.dim() != 2:
+            raise ValueError(f"head: weight must be [N, C] or [N, C, 1, 1], got {tuple(weight.shape)}")
+    else:
+        raise TypeError(f"head must be {_HEAD_FORMS}; got {type(head).__name__}")
+    if weight.shape[1] != channels:
+        raise ValueError(f"head: it reads {weight.shape[1]} channels, the features have {channels}")
+    if weight.shape[0] < 1:
+        raise ValueError("head: no output channels")
+    if bias is not None and tuple(bias.shape) != (weight.shape[0],):
+        raise ValueError(f"head: bias must be [{weight.shape[0]}], got {tuple(bias.shape)}")
+    if weight.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"head: weight must be float32 or bfloat16, got {weight.dtype}")
+    return weight, bias
+
+
+def _apply_head(head, x: torch.Tensor) -> torch.Tensor:
+    """``head(x)`` for the accepted forms of ``head`` on [B, C, H, W] features (the unfused composition)."""
+    if isinstance(head, nn.Conv2d):
+        return head(x.to(head.weight.dtype))
+    if isinstance(head, nn.Linear):
+        return head(x.to(head.weight.dtype).permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+    weight, bias = head
+    if weight.dim() == 2:
+        weight = weight[:, :, None, None]
+    return F.conv2d(x.to(weight.dtype), weight, None if bias is None else bias.to(weight.dtype))
+
+
 class NAF(nn.Module):
     """Drop-in for the reference's ``NAF`` (naf.py:72-116): same constructor, same ``state_dict``."""
 
@@ -626,11 +671,12 @@ class NAF(nn.Module):
         self.fuse_rope = True      # rotate queries inside the attention kernel when the shapes allow it
         self.single_call = True    # issue the whole forward through naf_forward (one foreign call) when possible
 
-    def guidance_qk(self, image, lr_size, output_size, fuse_for=None):
+    def guidance_qk(self, image, lr_size, output_size, fuse_for=None, fusable=None):
         """bf16 queries and pooled RoPE'd keys (5-D views) for ``image``.  Returns (q5, k5, rope_tables):
         rope_tables is None when q5 is already rotated, or the (tab_y, tab_x) pair when q5 is the un-rotated
         guidance that the attention kernel rotates on load (``fuse_for`` = (Dv, out_dtype) of the attention call
-        asks for that; it is granted when the shapes allow it, see ops.xna_rope_fusable)."""
+        asks for that; it is granted when the shapes allow it, see ops.xna_rope_fusable).  ``fusable``: a predicate
+        ``(q5, (tab_y, tab_x)) -> bool`` that decides it instead (the head-summed attention asks its own kernel, ``ops.xna_head_select``)."""
         ho, wo = int(output_size[0]), int(output_size[1])
         enc = self.image_encoder
         with ops._Timed("stem"):
@@ -638,13 +684,17 @@ class NAF(nn.Module):
         tab_y, tab_x = enc.rope.tables(ho, wo)
         heads_rope, heads_attn = enc.rope.num_heads, self.upsampler.num_heads
         same = heads_attn == heads_rope
-        if fuse_for is not None and self.fuse_rope and same and x.dtype == torch.bfloat16:
+        if (fuse_for is not None or fusable is not None) and self.fuse_rope and same and x.dtype == torch.bfloat16:
             B, Cq = x.shape[:2]
             xq = x.permute(0, 2, 3, 1)                                            # [B, Ho, Wo, C] view
             if xq.stride(3) == 1:
                 q5 = xq.unflatten(3, (heads_rope, Cq // heads_rope)).permute(0, 3, 1, 2, 4)
-                if ops.xna_rope_fusable(q5, lr_size, fuse_for[0], self.upsampler.kernel_size, (tab_y, tab_x),
-                                        out_dtype=fuse_for[1], path=self.xna_path):
+                if fusable is not None:
+                    ok = fusable(q5, (tab_y, tab_x))
+                else:
+                    ok = ops.xna_rope_fusable(q5, lr_size, fuse_for[0], self.upsampler.kernel_size, (tab_y, tab_x),
+                                              out_dtype=fuse_for[1], path=self.xna_path)
+                if ok:
                     _, k5 = ops.rope_pool(x, tab_y, tab_x, heads_rope, lr_size, write_q=False)
                     return q5, k5, (tab_y, tab_x)
         q5, k5 = ops.rope_pool(x, tab_y, tab_x, heads_rope, lr_size, q_layout="head_major" if same else "channels_last")
@@ -803,7 +853,7 @@ class NAF(nn.Module):
         out = out5.permute(0, 1, 4, 2, 3).reshape(B, C, ho, wo)
         return (out, logits) if return_weights else out
 
-    def forward(self, image, features, output_size, return_weights=False, *args, **kwargs):
+    def forward(self, image, features, output_size, return_weights=False, *args, head=None, **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -811,7 +861,24 @@ class NAF(nn.Module):
         grad, or the module is in ``.train()`` mode with trainable parameters) -- then the call is ``forward_train``
         (train.py:127-137, denoising.py:213 work unchanged).  README usage (``naf.eval()`` then ``naf(...)``) and any call
         under ``torch.no_grad()`` take the inference path; that path always uses the deterministic eval-mode RoPE
-        coordinates (the reference's train-mode coordinate jitter only exists on the differentiable path here)."""
+        coordinates (the reference's train-mode coordinate jitter only exists on the differentiable path here).
+
+        ``head`` (keyword only): a linear probe on the upsampled features -- an ``nn.Conv2d`` with a 1x1 kernel, an ``nn.Linear`` or a
+        ``(weight, bias_or_None)`` pair (weight [N, C] or [N, C, 1, 1]) -- what evaluation/eval_seg_probing.py:56,104-111 puts on
+        ``model(image, feats, (H, W))``.  The call then returns the logits ``head(naf(image, features, size))`` as a logical
+        [B, N, Ho, Wo] tensor in the head weight's dtype (float32 / bfloat16) whose memory is a dense channels-last [B, Ho, Wo, N] buffer
+        (strides (Ho*Wo*N, 1, Wo*N, N)), WITHOUT forming the [B, C, Ho, Wo] features: the attention is linear in the values and its
+        weights sum to one, so the head is applied on the low-res grid (``ops.project_head_values``) and the head-summed attention
+        kernel (``ops.xna_head_forward``) writes N channels per pixel.  With a frozen upsampler (``torch.no_grad()``, or no trainable
+        upsampler parameter in ``.train()`` mode and no input that requires grad) the call is differentiable WITH RESPECT TO THE HEAD when
+        its parameters require grad (probe training): the stem, RoPE and key pooling run on the inference kernels without a graph, only
+        the projection and ``ops.XnaHeadFunction`` are recorded.  A call that wants a gradient for the upsampler, the image or the
+        features runs the unfused composition ``head(self.forward_train(...))`` -- correct, not fused.  ``return_weights`` together with
+        ``head`` is rejected (ValueError): the scores belong to the features' call.  Anything that is not one of the three forms raises
+        TypeError; a 3x3 / strided / grouped / dilated convolution or a channel mismatch raises ValueError (no silent fallback).
+        ``head=None`` is the call above, untouched."""
+        if head is not None:
+            return self._forward_head(image, features, output_size, return_weights, head)
         if torch.is_grad_enabled() and (image.requires_grad or features.requires_grad or
                                         (self.training and any(p.requires_grad for p in self.parameters()))):
             # the library's own differentiable stem whenever it serves the width, with or without torch.autocast (round 6: the
@@ -820,6 +887,40 @@ class NAF(nn.Module):
             return self.forward_train(image, features, output_size, amp="auto", return_weights=return_weights)
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)
+
+    def _forward_head(self, image, features, output_size, return_weights, head):
+        """``forward(..., head=head)``: see ``forward``."""
+        if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
+        weight, bias = _linear_head(head, features.shape[1])      # host-side validation first: nothing has touched the device yet
+        if return_weights:
+            raise ValueError("naf(..., head=...) does not return attention scores: call naf(image, features, size, return_weights=True) for them")
+        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
+            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
+                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        N = weight.shape[0]
+        if image.shape[0] == 0:
+            return torch.empty((0, ho, wo, N), dtype=weight.dtype, device=features.device).permute(0, 3, 1, 2)
+        grad = torch.is_grad_enabled()
+        if grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+            # a gradient for the upsampler or its inputs: today's differentiable forward, then the head (unfused)
+            return _apply_head(head, self.forward_train(image, features, output_size, amp="auto"))
+        heads = self.upsampler.num_heads
+        if features.shape[1] % heads:
+            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
+        head_grad = grad and (weight.requires_grad or (bias is not None and bias.requires_grad))
+        ksz, lr = self.upsampler.kernel_size, features.shape[-2:]
+        with torch.no_grad():
+            # rotate-on-load only without a graph: the backward kernels read materialised (rotated) queries
+            fusable = None if head_grad else (lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, out_dtype=weight.dtype, rope_tables=tabs) == "fused")
+            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
+        pv5, b32 = ops.project_head_values(weight, bias, features, heads)
+        with ops._Timed("attention"):
+            if head_grad:
+                return ops.XnaHeadFunction.apply(q5, k5, pv5, b32, ksz, N, weight.dtype, "auto", self.upsampler.scale)
+            with torch.no_grad():
+                return ops.xna_head_forward(q5, k5, pv5, b32, ksz, n_out=N, out_dtype=weight.dtype, scale=self.upsampler.scale, rope_tables=tabs)
 
     def _forward_inference(self, image, features, output_size, return_weights=False):
         if not (image.is_cuda and features.is_cuda):

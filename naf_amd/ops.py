@@ -9,6 +9,7 @@ Reference counterparts (paths relative to the reference repo):
   rope_pool          RoPE.forward rotation + KeyEncoder pooling         src/layers/rope.py:147-174, src/model/naf.py:63-69
   pack_values        CrossAttention._resize layout/dtype part           src/layers/attentions.py:50-51
   xna_forward        legacy_attention / na2d                            src/layers/attentions.py:16-29,72
+  xna_head_forward   the same with the probe's 1x1 convolution folded in  evaluation/eval_seg_probing.py:56,104-111
 """
 from __future__ import annotations
 
@@ -20,7 +21,7 @@ from typing import Dict, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import XnaArgs, XnaBwdArgs, XnaBwdScoresArgs, RopePoolArgs, StemConv0Args, StemConvArgs, KeyPoolArgs, ForwardArgs, I64x3, I64x4
+from ._lib import XnaArgs, XnaHeadArgs, XnaBwdArgs, XnaBwdScoresArgs, RopePoolArgs, StemConv0Args, StemConvArgs, KeyPoolArgs, ForwardArgs, I64x3, I64x4
 
 _DT = {torch.bfloat16: _lib.NAF_BF16, torch.float32: _lib.NAF_F32}
 
@@ -796,6 +797,183 @@ class XnaFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         return ((dq if need[0] else None), (dk.to(k_lr.dtype) if need[1] else None), (dv.to(v_lr.dtype) if need[2] else None),
                 None, None, None) + (None,) * ctx.nrest
+
+
+# ---- attention with a linear head folded in ------------------------------------------------------
+_HEAD_PATHS = ("auto", "fused", "composed")
+_BWD_DV = (32, 64, 96, 128, 192, 256)      # value widths the cell backward serves (naf_xna_bwd)
+
+
+def head_npad(n_out: int) -> int:
+    """Channels of a ``pv5`` row for ``n_out`` head outputs: rounded up to the 16 of an MFMA tile."""
+    return (int(n_out) + 15) // 16 * 16
+
+
+def project_head_values(weight: torch.Tensor, bias: Optional[torch.Tensor], features: torch.Tensor, heads: int, *,
+                        dtype: torch.dtype = torch.bfloat16):
+    """The low-res half of ``head(naf(features))`` for a linear head: ``PV_g = W[:, g*Dv:(g+1)*Dv] @ V_g`` per attention head ``g``.
+
+    weight [N, C] or [N, C, 1, 1], bias [N] or None, features [B, C, h, w] -> (pv5 [B, heads, h, w, Npad] ``dtype`` with Npad = N rounded
+    up to 16 and zero pad channels, bias as fp32 or None).  Pure torch, differentiable (this is where a trainable head's gradient enters
+    autograd), works on CPU tensors: an einsum on the low-res grid is host glue, not a hot path."""
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight[:, :, 0, 0]
+    if weight.dim() != 2:
+        raise ValueError(f"project_head_values: weight must be [N, C] or [N, C, 1, 1], got {tuple(weight.shape)}")
+    if features.dim() != 4:
+        raise ValueError(f"project_head_values: features must be [B, C, h, w], got {tuple(features.shape)}")
+    N, Cw = weight.shape
+    B, Cc, h, w = features.shape
+    if Cw != Cc:
+        raise ValueError(f"project_head_values: the head reads {Cw} channels, the features have {Cc}")
+    if heads <= 0 or Cc % heads:
+        raise ValueError(f"project_head_values: feature channels {Cc} not divisible by {heads} heads")
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise ValueError(f"project_head_values: bias must be [{N}], got {tuple(bias.shape)}")
+    Dv = Cc // heads
+    pv = torch.einsum("ngd,bgdhw->bghwn", weight.float().reshape(N, heads, Dv), features.float().reshape(B, heads, Dv, h, w))
+    pad = head_npad(N) - N
+    if pad:
+        pv = torch.nn.functional.pad(pv, (0, pad))
+    return pv.to(dtype), (None if bias is None else bias.float())
+
+
+def _fill_xna_head(q, k, pv, bias, out, n_out, ky, kx, path, scale, rope_tables=None) -> XnaHeadArgs:
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w = pv.shape[2:4]
+    a = XnaHeadArgs()
+    a.q, a.k_lr, a.pv_lr, a.out = q.data_ptr(), k.data_ptr(), pv.data_ptr(), out.data_ptr()
+    a.bias = bias.data_ptr() if bias is not None else None
+    if rope_tables is not None:
+        ty, tx = rope_tables
+        if ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
+                or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
+            raise ValueError("xna_head: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
+        a.rope_tab_y, a.rope_tab_x = ty.data_ptr(), tx.data_ptr()
+    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, int(n_out), ky, kx
+    a.out_dtype = _DT[out.dtype]
+    a.path = _lib.XNA_HEAD_FUSED if path == "fused" else _lib.XNA_HEAD_AUTO
+    a.scale = float(scale) if scale else 0.0
+    a.q_stride = _strides4(q, (0, 1, 2, 3))
+    a.k_stride = _strides4(k, (0, 1, 2, 3))
+    a.pv_stride = _strides4(pv, (0, 1, 2, 3))
+    a.o_stride = I64x3(*[int(out.stride(d)) for d in (0, 1, 2)])
+    return a
+
+
+def xna_head_select(q: torch.Tensor, lr_size, n_out: int, kernel_size, *, out_dtype: torch.dtype = torch.float32, rope_tables=None) -> str:
+    """Which route ``xna_head_forward(path="auto")`` takes for these shapes: "fused" (``naf_xna_head_select`` grants the head-summed kernel)
+    or "composed" (``xna_forward`` on the projected values, summed over the heads).  ``q``: the 5-D [B, heads, Ho, Wo, Dq] bf16 queries --
+    with ``rope_tables`` the un-rotated guidance.  A host-side query: nothing is launched or read.  Invalid arguments raise ValueError."""
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or out_dtype not in _DT or not 1 <= int(n_out) <= 256:
+        return "composed"
+    lib = _lib.load()
+    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    npad = head_npad(n_out)
+    a = XnaHeadArgs()
+    a.q = a.k_lr = a.pv_lr = a.out = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, int(n_out), ky, kx
+    a.out_dtype, a.path, a.scale = _DT[out_dtype], _lib.XNA_HEAD_AUTO, 0.0
+    a.q_stride = _strides4(q, (0, 1, 2, 3))
+    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
+    a.pv_stride = I64x4(heads * h * w * npad, h * w * npad, w * npad, npad)
+    a.o_stride = I64x3(Ho * Wo * int(n_out), Wo * int(n_out), int(n_out))
+    sel = lib.naf_xna_head_select(C.byref(a))
+    if sel == -1:
+        _lib.check(1, "naf_xna_head_select")
+    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
+
+
+def xna_head_forward(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, bias: Optional[torch.Tensor], kernel_size, *,
+                     n_out: int, out_dtype: torch.dtype = torch.float32, path: str = "auto", scale: Optional[float] = None,
+                     rope_tables=None) -> torch.Tensor:
+    """Cross-scale neighbourhood attention with a linear head folded in: ``bias + sum over heads of attention(q, k_lr, pv_lr)``.
+
+    q [B, heads, Ho, Wo, Dq] bf16, k_lr [B, heads, h, w, Dq] bf16, pv_lr [B, heads, h, w, Npad] bf16 from ``project_head_values``
+    (5-D strided views, last dim contiguous), bias fp32 [n_out] or None.  Returns the logits as a logical [B, n_out, Ho, Wo] view of a
+    dense channels-last [B, Ho, Wo, n_out] buffer of ``out_dtype`` (bfloat16 / float32).
+    ``path="auto"``: the head-summed kernel (``naf_xna_head_fwd``) where ``naf_xna_head_select`` grants it, else the composition that
+    serves every geometry ``xna_forward`` serves -- ``xna_forward`` on ``pv_lr`` with fp32 output, summed over the head axis, plus bias.
+    ``path="fused"`` insists on the kernel and raises where it does not serve the call; ``path="composed"`` insists on the composition.
+    ``rope_tables``: as in ``xna_forward`` (q is the un-rotated guidance)."""
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
+        _gpu(t, n)
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"xna_head_forward: {n} must be bfloat16, got {t.dtype}")
+        if t.dim() != 5 or t.stride(4) != 1:
+            raise ValueError(f"xna_head_forward: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    if path not in _HEAD_PATHS:
+        raise ValueError(f"xna_head_forward: path must be one of {_HEAD_PATHS}, got {path!r}")
+    if out_dtype not in _DT:
+        raise TypeError(f"xna_head_forward: out_dtype {out_dtype} not supported (bfloat16 / float32)")
+    lib = _lib.load()
+    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w, npad = pv_lr.shape[2:]
+    n_out = int(n_out)
+    if k_lr.shape != (B, heads, h, w, Dq) or pv_lr.shape[:2] != (B, heads):
+        raise ValueError(f"xna_head_forward: k_lr {tuple(k_lr.shape)} / pv_lr {tuple(pv_lr.shape)} do not match q {tuple(q.shape)}")
+    if n_out < 1 or npad != head_npad(n_out):
+        raise ValueError(f"xna_head_forward: pv_lr holds {npad} channels, n_out = {n_out} needs {head_npad(max(n_out, 1))}")
+    if bias is not None:
+        _gpu(bias, "bias")
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (n_out,) or not bias.is_contiguous():
+            raise ValueError(f"xna_head_forward: bias must be a contiguous float32 [{n_out}] tensor")
+    dev = q.device
+    if path != "composed" and (n_out <= 256 or path == "fused"):
+        out = torch.empty((B, Ho, Wo, n_out), dtype=out_dtype, device=dev)
+        a = _fill_xna_head(q, k_lr, pv_lr, bias, out, n_out, ky, kx, path, scale, rope_tables)
+        sel = lib.naf_xna_head_select(C.byref(a))
+        if sel == _lib.XNA_HEAD_FUSED:
+            with torch.cuda.device(dev), _Timed("xna_head"):
+                rc = lib.naf_xna_head_fwd(C.byref(a), _stream(q))
+            _lib.check(rc, "naf_xna_head_fwd")
+            return out.permute(0, 3, 1, 2)
+        if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
+            _lib.check(-sel, "naf_xna_head_select")
+        del out
+    with _Timed("xna_head_composed"):
+        o5 = xna_forward(q, k_lr, pv_lr, (ky, kx), out_dtype=torch.float32, path="auto", scale=scale, rope_tables=rope_tables)
+        o = o5.sum(dim=1)[..., :n_out]
+        if bias is not None:
+            o = o + bias
+        return o.to(out_dtype).contiguous().permute(0, 3, 1, 2)
+
+
+class XnaHeadFunction(torch.autograd.Function):
+    """Differentiable ``xna_head_forward`` with respect to the head: gradients reach ``pv_lr`` and ``bias`` only (the queries and keys come
+    from a frozen upsampler).  ``dPV_g[cell] = sum_px P_g[px, cell] * dOut[px]`` is the ``dv_lr`` of ``naf_xna_bwd`` with ONE ``dout`` shared
+    by all heads: the backward hands it over expanded along the head axis (stride 0) and discards dq / dk.  ``q`` holds materialised
+    (rotated) queries: the backward kernels have no rotate-on-load."""
+
+    @staticmethod
+    def forward(ctx, q, k_lr, pv_lr, bias, kernel_size, n_out, out_dtype, path="auto", scale=None):
+        ctx.save_for_backward(q, k_lr, pv_lr)
+        ctx.kernel_size, ctx.n_out, ctx.scale, ctx.has_bias = kernel_size, int(n_out), scale, bias is not None
+        return xna_head_forward(q, k_lr, pv_lr, bias, kernel_size, n_out=n_out, out_dtype=out_dtype, path=path, scale=scale)
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, k_lr, pv_lr = ctx.saved_tensors
+        need_pv, need_b = ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3]
+        N = ctx.n_out
+        dpv = dbias = None
+        if need_b:
+            dbias = dout.float().sum(dim=(0, 2, 3))
+        if need_pv:
+            B, heads, Ho, Wo, _ = q.shape
+            npad = pv_lr.shape[-1]
+            dvp = next((c for c in _BWD_DV if c >= npad), npad)     # a width the cell backward serves; the pad channels' gradient is zero
+            g = torch.zeros((B, Ho, Wo, dvp), dtype=torch.bfloat16, device=q.device)
+            g[..., :N] = dout.permute(0, 2, 3, 1)
+            pvp = torch.nn.functional.pad(pv_lr, (0, dvp - npad)) if dvp != npad else pv_lr
+            _, _, dv = xna_backward(q, k_lr, pvp, g.unsqueeze(1).expand(B, heads, Ho, Wo, dvp), ctx.kernel_size, scale=ctx.scale)
+            dpv = dv[..., :npad].to(pv_lr.dtype)
+        return None, None, dpv, dbias, None, None, None, None, None
 
 
 def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables, out_dtype=torch.bfloat16,
