@@ -61,7 +61,8 @@ extern "C" {
  * with a gradient of the scaled scores naf_xna_fwd returns in `logits` (naf_xna_bwd_scores_args), so that a loss on the scores trains q and k.
  * After 0.4.3, same version number (binary compatible: new entry points with a struct of their own, nothing else moves): naf_xna_head_select /
  * naf_xna_head_fwd / naf_xna_head_workspace_bytes -- the attention with a linear head folded in (naf_xna_head_args).  A host detects them by symbol
- * (dlsym), not by naf_version(). */
+ * (dlsym), not by naf_version().  Added the same way after them: naf_xna_head_ce_select / naf_xna_head_ce_fwd -- that attention with a
+ * cross-entropy / argmax epilogue (naf_xna_head_ce_args, which embeds naf_xna_head_args unchanged). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -497,6 +498,49 @@ int naf_xna_head_select(const naf_xna_head_args* a);
 /* Scratch bytes the call needs (0 today; kept so callers need not change later). */
 size_t naf_xna_head_workspace_bytes(const naf_xna_head_args* a);
 int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream);
+
+/* ---- ... with a classification objective in the epilogue (added after the head entries; detect by symbol) ------------
+ * What the reference does with the probe's logits (evaluation/eval_seg_probing.py:94-135 and its train / validate loops): a
+ * cross-entropy over the pixels whose target is not IGNORE = 255, or an argmax for accuracy / IoU.  The logits of a pixel are in the
+ * registers of four lanes when naf_xna_head_fwd's kernel is done, so this entry computes, per pixel and in fp32, over the N channels,
+ *     lse = max z + ln sum exp(z - max z),  label = argmax z,  loss = lse - z[t],  dlogits[n] = exp(z[n] - lse) - (n == t)
+ * and stores only what is asked for; the [B, Ho, Wo, N] logits need not exist.
+ *   head      naf_xna_head_args as for naf_xna_head_fwd, except that `out` may be NULL; when given it receives the logits, fp32
+ *             (out_dtype must be NAF_F32), bit for bit what naf_xna_head_fwd stores
+ *   target    device int64 [B, Ho, Wo], element strides t_stride {b, y, x}; NULL when only labels / logits are wanted.  A pixel is
+ *             IGNORED when target == ignore_index or target is outside [0, N)
+ *   loss      device float [B, Ho, Wo] (loss_stride), or NULL: lse - z[t], 0 for an ignored pixel.  Needs target.  The caller reduces
+ *             the map (sum, or sum / number of valid pixels): no atomics here, the result is deterministic
+ *   labels    device uint8 [B, Ho, Wo] (labels_stride), or NULL: the lowest index among equal maxima (torch.argmax's documented choice)
+ *   dlogits   device bf16 [B, Ho, Wo, dlogits_channels] (dlogits_stride {b, y, x}, channel axis contiguous), or NULL: softmax - onehot of a
+ *             valid pixel, zeros for an ignored one, rounded once to bf16 and NOT divided by the number of valid pixels (the caller scales
+ *             the low-res result of naf_xna_bwd, which is linear in it).  The kernel writes EVERY one of the dlogits_channels channels
+ *             (zeros from N up), so the buffer needs no clearing: it is the `dout` of naf_xna_bwd for all heads at once (head stride 0),
+ *             dlogits_channels being a value width that entry serves.  Needs target.
+ * naf_xna_head_ce_select answers as naf_xna_head_select does (NAF_XNA_HEAD_FUSED, -NAF_ERR_INVALID, -NAF_ERR_UNSUPPORTED, with
+ * naf_last_error) and additionally refuses: no output requested; loss / dlogits without target; dlogits_channels not a multiple of 8,
+ * smaller than N rounded up to 16, or above 256 (all -NAF_ERR_INVALID); a dlogits that is not 16-byte aligned or whose strides are not
+ * multiples of 8 elements (-NAF_ERR_UNSUPPORTED).  Served geometries: exactly naf_xna_head_fwd's.
+ * NOT what torch.nn.functional.cross_entropy does: (1) a target outside [0, N) that is not ignore_index is ignored (loss 0, zero
+ * gradient, not to be counted by the caller) where torch raises a device-side assert -- the target is only ever compared with channel
+ * indices, never used to form an address; (2) no reduction: the mean over zero valid pixels (torch: nan) is the caller's division;
+ * (3) no class weights, label smoothing or soft targets.  Caller-owned memory and stream; capturable; no workspace. */
+typedef struct naf_xna_head_ce_args {
+    naf_xna_head_args head; /* head.out may be NULL */
+    const int64_t* target;
+    float* loss;
+    uint8_t* labels;
+    void* dlogits;
+    int64_t ignore_index;
+    int32_t dlogits_channels;
+    int32_t reserved;
+    int64_t t_stride[3];
+    int64_t loss_stride[3];
+    int64_t labels_stride[3];
+    int64_t dlogits_stride[3];
+} naf_xna_head_ce_args;
+int naf_xna_head_ce_select(const naf_xna_head_ce_args* a);
+int naf_xna_head_ce_fwd(const naf_xna_head_ce_args* a, naf_stream_t stream);
 
 /* ---- cross-scale neighbourhood attention backward --------------------------------------------------
  * Replaces what autograd runs through legacy_attention (attentions.py:16-29: the backward of na2d_qk, the

@@ -58,6 +58,15 @@ class XnaHeadArgs(C.Structure):
     ]
 
 
+class XnaHeadCEArgs(C.Structure):
+    """naf_xna_head_ce_args (added after the head entries, detected by symbol): naf_xna_head_args plus the classification epilogue's maps."""
+    _fields_ = [
+        ("head", XnaHeadArgs), ("target", C.c_void_p), ("loss", C.c_void_p), ("labels", C.c_void_p), ("dlogits", C.c_void_p),
+        ("ignore_index", C.c_int64), ("dlogits_channels", C.c_int32), ("reserved", C.c_int32),
+        ("t_stride", I64x3), ("loss_stride", I64x3), ("labels_stride", I64x3), ("dlogits_stride", I64x3),
+    ]
+
+
 class StemConv0Args(C.Structure):
     _fields_ = [
         ("image", C.c_void_p), ("y", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("stats_out", C.c_void_p),
@@ -223,6 +232,8 @@ SIGNATURES = {
     "naf_xna_head_select": (C.c_int, [C.POINTER(XnaHeadArgs)]),
     "naf_xna_head_workspace_bytes": (C.c_size_t, [C.POINTER(XnaHeadArgs)]),
     "naf_xna_head_fwd": (C.c_int, [C.POINTER(XnaHeadArgs), C.c_void_p]),
+    "naf_xna_head_ce_select": (C.c_int, [C.POINTER(XnaHeadCEArgs)]),
+    "naf_xna_head_ce_fwd": (C.c_int, [C.POINTER(XnaHeadCEArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -352,9 +352,10 @@ int naf_xna_fwd(const naf_xna_args* a, naf_stream_t stream) {
 }
 
 // ---- attention with a linear head folded in (after 0.4.3) ----------------------------------------------------
-static int xna_head_validate(const naf_xna_head_args* a) {
+// need_out = false: the classification entry (naf_xna_head_ce_*), where `out` is optional
+static int xna_head_validate(const naf_xna_head_args* a, bool need_out = true) {
     NAF_REQUIRE(a != nullptr, "naf_xna_head_fwd: args is NULL");
-    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && a->out, "naf_xna_head_fwd: NULL tensor pointer");
+    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && (a->out || !need_out), "naf_xna_head_fwd: NULL tensor pointer");
     NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 && a->Dq > 0, "naf_xna_head_fwd: non-positive size");
     NAF_REQUIRE(a->N >= 1 && a->N <= 256, "naf_xna_head_fwd: N must be in 1 .. 256, got %d", a->N);
     NAF_REQUIRE(a->out_dtype == NAF_BF16 || a->out_dtype == NAF_F32, "naf_xna_head_fwd: out_dtype %d", a->out_dtype);
@@ -367,7 +368,7 @@ static int xna_head_validate(const naf_xna_head_args* a) {
     NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_head_fwd: rope_tab_y and rope_tab_x must be given together");
     NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "naf_xna_head_fwd: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)",
                 (long long)a->pv_stride[3], a->N);
-    NAF_REQUIRE(a->o_stride[2] >= a->N, "naf_xna_head_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
+    NAF_REQUIRE(a->out == nullptr || a->o_stride[2] >= a->N, "naf_xna_head_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
     return NAF_OK;
 }
 
@@ -389,6 +390,40 @@ int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream) {
     if (sel < 0) return -sel;
     const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
     return naf_launch_xna_head(a, scale, static_cast<hipStream_t>(stream));
+}
+
+// ---- ... and a classification objective folded into its epilogue (cross-entropy, argmax, softmax - onehot) ----
+static int xna_head_ce_validate(const naf_xna_head_ce_args* c) {
+    NAF_REQUIRE(c != nullptr, "naf_xna_head_ce: args is NULL");
+    const int rc = xna_head_validate(&c->head, false);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(c->head.out || c->loss || c->labels || c->dlogits, "naf_xna_head_ce: no output requested (out, loss, labels and dlogits are all NULL)");
+    NAF_REQUIRE(c->head.out == nullptr || c->head.out_dtype == NAF_F32, "naf_xna_head_ce: the optional logits are stored as NAF_F32 (out_dtype %d)", c->head.out_dtype);
+    NAF_REQUIRE(c->target != nullptr || (c->loss == nullptr && c->dlogits == nullptr), "naf_xna_head_ce: loss and dlogits need a target");
+    if (c->dlogits != nullptr) {
+        const int npad = (c->head.N + 15) & ~15;
+        NAF_REQUIRE(c->dlogits_channels % 8 == 0, "naf_xna_head_ce: dlogits_channels must be a multiple of 8, got %d", c->dlogits_channels);
+        NAF_REQUIRE(c->dlogits_channels >= npad, "naf_xna_head_ce: dlogits_channels %d smaller than N rounded up to 16 (%d)", c->dlogits_channels, npad);
+        NAF_REQUIRE(c->dlogits_channels <= 256, "naf_xna_head_ce: dlogits_channels %d above 256", c->dlogits_channels);
+        NAF_REQUIRE(c->dlogits_stride[2] >= c->dlogits_channels, "naf_xna_head_ce: dlogits x stride %lld smaller than dlogits_channels %d",
+                    (long long)c->dlogits_stride[2], c->dlogits_channels);
+    }
+    return NAF_OK;
+}
+
+int naf_xna_head_ce_select(const naf_xna_head_ce_args* a) {
+    int rc = xna_head_ce_validate(a);
+    if (rc != NAF_OK) return -rc;
+    rc = naf_xna_head_ce_eligible(a);
+    if (rc != NAF_OK) return -rc;
+    return NAF_XNA_HEAD_FUSED;
+}
+
+int naf_xna_head_ce_fwd(const naf_xna_head_ce_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_head_ce_select(a);
+    if (sel < 0) return -sel;
+    const float scale = a->head.scale > 0.f ? a->head.scale : 1.0f / sqrtf((float)a->head.Dq);
+    return naf_launch_xna_head_ce(a, scale, static_cast<hipStream_t>(stream));
 }
 
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {

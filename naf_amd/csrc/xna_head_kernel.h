@@ -24,6 +24,16 @@
 //     its pixels' 512-byte (heads x 64 x bf16) rows: whole rows in the end, from one CU.  Rotate-on-load as in the cell kernel: the tile's RoPE table rows are fetched once per round (they
 //     do not depend on the head) and applied with naf_rope_rotate, the same arithmetic and rounding as naf_rope_pool_fwd's.
 //   * the bias is added in the epilogue in fp32; a lane stores its 4 consecutive channels of its own pixel, channels >= N masked.
+//
+// Classification epilogue (template parameter CE, naf_xna_head_ce_fwd): the logits instantiations (CE = false) are the code they were.  With
+// CE a pixel's N logits z sit, in fp32, in the four lanes col + 16 * grp of its tile, so the softmax over the CLASSES is the reduction the
+// softmax over the key slots already uses (naf_rows_max / naf_rows_sum), channels >= N masked as key slots >= NSLOT are:
+//     m = max z, lse = m + ln(sum exp(z - m)), label = lowest n with z[n] = m, loss = lse - z[t], g[n] = exp(z[n] - lse) - (n == t)
+//   The target is one 8-byte load per lane of the pixel (the four lanes read the same word) and is ONLY COMPARED with channel indices,
+//   never used in an address: t == ignore_index or t outside [0, N) makes the pixel ignored (loss 0, g = 0).  Loss (fp32) and label (uint8)
+//   are stored by the pixel's grp = 0 lane; g is rounded once to bf16 and stored as 8-byte vectors by the lanes that own the channels,
+//   zeros for channels N .. gc-1 -- also past the NCT*16 accumulator channels (Npad = 160 -> gc = 192), so the host never clears the buffer.
+//   Every output is optional (NULL: a wave-uniform branch).  No atomics, no cross-workgroup reduction: the host sums the loss map.
 #pragma once
 #include "xna_mfma_kernel.h"
 
@@ -44,6 +54,21 @@ struct XnaHeadParams {
     int64_t os[3];                // {b, y, x}
 };
 
+// the classification epilogue's arguments (CE = true instantiations only; XnaHeadParams::out may be nullptr there).  The kernel reads
+// them from the kernel-argument segment in the epilogue, not before (see there): held across the head loop they are 34 more scalar
+// registers than there are, spilled into vector lanes.
+struct XnaHeadCEExtra {
+    const int64_t* target;   // [B, Ho, Wo] or nullptr
+    float* loss;             // per-pixel lse - z[t], or nullptr
+    uint8_t* labels;         // per-pixel argmax, or nullptr
+    bf16_t* dlogits;         // [B, Ho, Wo, gc] softmax - onehot, or nullptr
+    int64_t ignore_index;
+    int64_t ts[3], ls[3], bs[3], gs[3];   // {b, y, x} element strides of target / loss / labels / dlogits
+    int32_t gc;              // channels of a dlogits row the kernel writes (multiple of 8, >= npad)
+};
+// they are the kernel's SECOND argument: it follows XnaHeadParams in the kernel-argument segment at its natural alignment
+constexpr size_t XNA_HEAD_CE_ARG_OFFSET = (sizeof(XnaHeadParams) + alignof(XnaHeadCEExtra) - 1) / alignof(XnaHeadCEExtra) * alignof(XnaHeadCEExtra);
+
 constexpr int XNA_HEAD_NW = 8;   // waves per workgroup
 // channel tiles (16 channels each) a workgroup accumulates: the smallest of these that holds Npad
 constexpr int xna_head_nct(int npad) { return npad <= 32 ? 2 : npad <= 64 ? 4 : npad <= 160 ? 10 : 16; }
@@ -51,8 +76,11 @@ constexpr int xna_head_nct(int npad) { return npad <= 32 ? 2 : npad <= 64 ? 4 : 
 constexpr int xna_head_tpw(int ks, int nct) { return (nct >= 10 && ks >= 11) ? 1 : 2; }
 constexpr size_t xna_head_lds_for(int ks, int nct) { return (size_t)(ks * ks) * (72 + nct * 16 + 16) * 2; }
 
-template <int KS, int NCT, typename OutT>
-__global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHeadParams p) {
+// CE = false: the logits kernel, one argument, the code it was before the classification epilogue existed (a parameter of another type, even
+// one that is the same struct, moves its instruction schedule).  CE = true: Extra = XnaHeadCEExtra, read through the segment pointer.
+template <int KS, int NCT, typename OutT, bool CE = false, typename... Extra>
+__global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHeadParams p, const Extra... extra) {
+    static_assert(sizeof...(Extra) == (CE ? 1 : 0), "the classification epilogue takes XnaHeadCEExtra as its second argument");
     constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
     constexpr int TPW = xna_head_tpw(KS, NCT);
     using G = XnaGeom<KS, 1>;
@@ -253,17 +281,110 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
             }
         }
 
-        // ---- epilogue: + bias (fp32), store the N real channels of this lane's pixel ----
+        if constexpr (CE) {
+            // ---- classification epilogue (see the header comment): softmax over the classes, loss, label, softmax - onehot ----
+            constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+            // the epilogue's own arguments, fetched from the kernel-argument segment HERE: the empty asm makes the address opaque, so the
+            // scalar loads cannot be hoisted above the head loop and held in registers across it
+            const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ka));
+            // ... and the same for the lane's coordinates: what the epilogue derives from them (addresses, bias loads) is invariant in the
+            // head loop and would be hoisted above it, 21 vector registers held through the loop (143 instead of 120 at 7 x 7, N <= 32)
+            int ecol = col, egrp = grp;
+            asm volatile("" : "+v"(ecol), "+v"(egrp));
+            const XnaHeadCEExtra __attribute__((address_space(4)))* x = reinterpret_cast<const XnaHeadCEExtra __attribute__((address_space(4)))*>(ka + XNA_HEAD_CE_ARG_OFFSET);
 #pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            if (!livev[u] || tx0v[u] + col >= p.dx) continue;
-            OutT* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + col) * p.os[2];
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u]) continue;   // wave-uniform: the four-lane reductions below run on whole waves
+                const bool inpx = tx0v[u] + ecol < p.dx;
+                const int64_t gy = cy * p.dy + tyv[u];
+                const int64_t gx = cx * p.dx + min(tx0v[u] + ecol, p.dx - 1);   // lanes past a partial last tile repeat its last pixel, store nothing
+                // z = acc + bias: the expression of the logits epilogue, so a stored z is the logit naf_xna_head_fwd stores
+                float m = -INFINITY;
+                int am = 0;
 #pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
+                for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int ch = ct * 16 + grp * 4 + r;
-                    if (ch < p.N) op[ch] = (OutT)(acc[u][ct][r] + (p.bias != nullptr ? p.bias[ch] : 0.f));
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + egrp * 4 + r;
+                        if (ch < p.N) {
+                            const float z = acc[u][ct][r] + (p.bias != nullptr ? p.bias[ch] : 0.f);
+                            acc[u][ct][r] = z;
+                            if (z > m) {   // a lane's channels ascend with (ct, r): the first of equal maxima stays
+                                m = z;
+                                am = ch;
+                            }
+                        }
+                    }
+                const float mall = naf_rows_max(m);
+                // lowest index among the lanes that hold the maximum: indices <= 255 are exact in fp32
+                const int label = (int)(-naf_rows_max(m == mall ? -(float)am : -INFINITY));
+                int t = -1;   // the target as a channel index, -1 = ignored
+                if (x->target != nullptr) {
+                    const int64_t tv = x->target[b * x->ts[0] + gy * x->ts[1] + gx * x->ts[2]];
+                    t = (tv != x->ignore_index && tv >= 0 && tv < (int64_t)p.N) ? (int)tv : -1;
+                }
+                float sum = 0.f, zt = 0.f;
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + egrp * 4 + r;
+                        if (ch < p.N) {
+                            sum += __builtin_amdgcn_exp2f((acc[u][ct][r] - mall) * LOG2E);
+                            zt += ch == t ? acc[u][ct][r] : 0.f;   // one lane of the four holds z[t]
+                        }
+                    }
+                sum = naf_rows_sum(sum);   // >= 1: the maximum contributes exp2(0)
+                zt = naf_rows_sum(zt);
+                if (egrp == 0 && inpx) {
+                    if (x->loss != nullptr)
+                        x->loss[b * x->ls[0] + gy * x->ls[1] + gx * x->ls[2]] = t >= 0 ? (mall + __builtin_amdgcn_logf(sum) * LN2) - zt : 0.f;
+                    if (x->labels != nullptr) x->labels[b * x->bs[0] + gy * x->bs[1] + gx * x->bs[2]] = (uint8_t)label;
+                }
+                if (p.out != nullptr && inpx) {
+                    OutT* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ch = ct * 16 + egrp * 4 + r;
+                            if (ch < p.N) op[ch] = (OutT)acc[u][ct][r];
+                        }
+                }
+                if (x->dlogits != nullptr && inpx) {
+                    bf16_t* gp = x->dlogits + b * x->gs[0] + gy * x->gs[1] + gx * x->gs[2];
+                    const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) {
+                        const int c0 = ct * 16 + egrp * 4;
+                        if (c0 >= x->gc) continue;   // gc is a multiple of 8: a lane's four channels are all inside or all outside
+                        bf16x4_t gv;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ch = c0 + r;
+                            const float e = __builtin_amdgcn_exp2f((acc[u][ct][r] - mall) * LOG2E) * inv - (ch == t ? 1.f : 0.f);
+                            gv[r] = (bf16_t)((ch < p.N && t >= 0) ? e : 0.f);
+                        }
+                        *reinterpret_cast<bf16x4_t*>(gp + c0) = gv;
+                    }
+                    // channels past the accumulators (Npad = 160 -> gc = 192): plain zero stores
+                    for (int c0 = DVT + egrp * 4; c0 < x->gc; c0 += 16) *reinterpret_cast<bf16x4_t*>(gp + c0) = bf16x4_t{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+                }
+            }
+        } else {
+            // ---- epilogue: + bias (fp32), store the N real channels of this lane's pixel ----
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u] || tx0v[u] + col >= p.dx) continue;
+                OutT* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + col) * p.os[2];
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + grp * 4 + r;
+                        if (ch < p.N) op[ch] = (OutT)(acc[u][ct][r] + (p.bias != nullptr ? p.bias[ch] : 0.f));
+                    }
                 }
             }
         }
@@ -300,5 +421,32 @@ static int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t
     NAF_HEAD_CASE(16)
 #undef NAF_HEAD_CASE
     naf_set_error("xna_head: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
+    return NAF_ERR_UNSUPPORTED;
+}
+
+// ---- classification epilogue: one more instantiation per (window, channel-tile count); the optional outputs are run-time NULL checks ----
+template <int KS, int NCT>
+static int xna_head_ce_launch_one(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s) {
+    constexpr size_t lds = xna_head_lds_for(KS, NCT);
+    auto kern = xna_head_kernel<KS, NCT, float, true, XnaHeadCEExtra>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+            return NAF_ERR_LAUNCH;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, x);
+    return naf_check_launch("xna_head_kernel (classification epilogue)");
+}
+
+template <int KS>
+static int xna_head_ce_launch_ks(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s) {
+    const int nct = xna_head_nct(p.npad);
+    if (nct == 2) return xna_head_ce_launch_one<KS, 2>(p, x, s);
+    if (nct == 4) return xna_head_ce_launch_one<KS, 4>(p, x, s);
+    if (nct == 10) return xna_head_ce_launch_one<KS, 10>(p, x, s);
+    if (nct == 16) return xna_head_ce_launch_one<KS, 16>(p, x, s);
+    naf_set_error("xna_head_ce: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
     return NAF_ERR_UNSUPPORTED;
 }

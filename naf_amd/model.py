@@ -853,7 +853,8 @@ class NAF(nn.Module):
         out = out5.permute(0, 1, 4, 2, 3).reshape(B, C, ho, wo)
         return (out, logits) if return_weights else out
 
-    def forward(self, image, features, output_size, return_weights=False, *args, head=None, **kwargs):
+    def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
+                reduction="mean", predict=False, **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -876,7 +877,25 @@ class NAF(nn.Module):
         features runs the unfused composition ``head(self.forward_train(...))`` -- correct, not fused.  ``return_weights`` together with
         ``head`` is rejected (ValueError): the scores belong to the features' call.  Anything that is not one of the three forms raises
         TypeError; a 3x3 / strided / grouped / dilated convolution or a channel mismatch raises ValueError (no silent fallback).
-        ``head=None`` is the call above, untouched."""
+        ``head=None`` is the call above, untouched.
+
+        ``target``, ``ignore_index``, ``reduction``, ``predict`` (keyword only, with ``head``): the probe's objective instead of its logits --
+        what the reference's probing loop does with them (evaluation/eval_seg_probing.py:94-135).  ``target`` (integer class indices
+        [B, Ho, Wo] on the features' device; other integer dtypes are converted to int64, resizing a mismatching target stays the caller's
+        business) returns ``F.cross_entropy(head(naf(...)).float(), target, ignore_index=ignore_index, reduction=reduction)``: a 0-dim fp32
+        tensor, or [B, Ho, Wo] fp32 for ``reduction="none"``; ``predict=True`` returns ``head(naf(...)).argmax(1)`` as int64 [B, Ho, Wo];
+        both return ``(loss, labels)`` from one launch.  The logits tensor is not written: the head-summed kernel's epilogue
+        (``ops.xna_head_objective``) takes the softmax over the classes in registers.  ``ignore_index`` defaults to torch's -100 (the
+        reference passes 255).  One difference from torch: a target outside [0, N) that is not ``ignore_index`` is IGNORED (no loss, no
+        gradient, not counted) where ``F.cross_entropy`` raises a device-side assert.  ``reduction="mean"`` without a valid pixel is nan,
+        as in torch.  The gradient modes are those of the logits call: frozen upsampler and a probe that requires grad -- fused and
+        differentiable with respect to the probe (``ops.XnaHeadCEFunction``); no gradient wanted -- the kernel with rotate-on-load; a
+        gradient for the upsampler, the image or the features -- the unfused ``F.cross_entropy(head(self.forward_train(...)).float(), ...)``.
+        Not offered: class weights, label smoothing, soft targets, a confusion matrix, ``capture()`` of this call."""
+        if target is not None or predict:
+            if head is None:
+                raise ValueError("naf(..., target=... / predict=True) is the objective of a probe: pass head=probe as well")
+            return self._forward_head_objective(image, features, output_size, return_weights, head, target, ignore_index, reduction, bool(predict))
         if head is not None:
             return self._forward_head(image, features, output_size, return_weights, head)
         if torch.is_grad_enabled() and (image.requires_grad or features.requires_grad or
@@ -921,6 +940,55 @@ class NAF(nn.Module):
                 return ops.XnaHeadFunction.apply(q5, k5, pv5, b32, ksz, N, weight.dtype, "auto", self.upsampler.scale)
             with torch.no_grad():
                 return ops.xna_head_forward(q5, k5, pv5, b32, ksz, n_out=N, out_dtype=weight.dtype, scale=self.upsampler.scale, rope_tables=tabs)
+
+    def _forward_head_objective(self, image, features, output_size, return_weights, head, target, ignore_index, reduction, predict):
+        """``forward(..., head=head, target=... / predict=True)``: see ``forward``."""
+        if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
+        weight, bias = _linear_head(head, features.shape[1])      # host-side validation first: nothing has touched the device yet
+        if return_weights:
+            raise ValueError("naf(..., head=...) does not return attention scores: call naf(image, features, size, return_weights=True) for them")
+        if reduction not in ops._REDUCTIONS:
+            raise ValueError(f"reduction must be one of {ops._REDUCTIONS}, got {reduction!r}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, N = image.shape[0], weight.shape[0]
+        ignore_index = int(ignore_index)
+        if target is not None:
+            target = ops._check_target(target, (B, ho, wo), features.device, "naf(..., target=...)")
+        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
+            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
+                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
+        pack = lambda loss, labels: (loss, labels) if (target is not None and predict) else (loss if target is not None else labels)
+        grad = torch.is_grad_enabled()
+        if B == 0 or (grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters())))):
+            # an empty batch (what torch returns for empty inputs of these shapes), or a gradient for the upsampler or its inputs: the
+            # logits call (unfused there), then the objective as torch ops
+            logits = self._forward_head(image, features, output_size, False, head).float()
+            loss = None
+            if target is not None:      # torch's own cross-entropy, with this call's contract for targets outside the classes
+                loss = F.cross_entropy(logits, ops.head_sanitized_target(target, ignore_index, N), ignore_index=ignore_index, reduction=reduction)
+            return pack(loss, logits.detach().argmax(1) if predict else None)
+        heads = self.upsampler.num_heads
+        if features.shape[1] % heads:
+            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
+        head_grad = grad and target is not None and (weight.requires_grad or (bias is not None and bias.requires_grad))
+        ksz, lr = self.upsampler.kernel_size, features.shape[-2:]
+        with torch.no_grad():
+            # rotate-on-load only without a graph, as for the logits (the geometry decides, not the outputs asked for)
+            fusable = None if head_grad else (lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, rope_tables=tabs) == "fused")
+            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
+        pv5, b32 = ops.project_head_values(weight, bias, features, heads)
+        with ops._Timed("attention"):
+            if head_grad:
+                res = ops.XnaHeadCEFunction.apply(q5, k5, pv5, b32, target, ksz, N, ignore_index, reduction, predict, "auto", self.upsampler.scale)
+                loss, labels = res if predict else (res, None)
+            else:
+                with torch.no_grad():
+                    loss_map, labels, _, _ = ops.xna_head_objective(q5, k5, pv5, b32, ksz, n_out=N, target=target, ignore_index=ignore_index,
+                                                                    want_loss=target is not None, want_labels=predict,
+                                                                    scale=self.upsampler.scale, rope_tables=tabs)
+                    loss = None if target is None else ops.reduce_head_loss(loss_map, target, ignore_index, N, reduction)
+        return pack(loss, None if labels is None else labels.long())       # the kernel writes uint8; widened so that it drops into pred == target
 
     def _forward_inference(self, image, features, output_size, return_weights=False):
         if not (image.is_cuda and features.is_cuda):

@@ -976,6 +976,217 @@ class XnaHeadFunction(torch.autograd.Function):
         return None, None, dpv, dbias, None, None, None, None, None
 
 
+# ---- ... and a classification objective in its epilogue (cross-entropy / argmax of the probe's logits) -------------------
+_REDUCTIONS = ("mean", "sum", "none")
+
+
+def head_dlogits_channels(n_out: int) -> int:
+    """Channels of a ``dlogits`` row for ``n_out`` classes: the value width the cell backward serves that holds Npad (``_BWD_DV``)."""
+    npad = head_npad(n_out)
+    return next((c for c in _BWD_DV if c >= npad), npad)
+
+
+def head_valid_pixels(target: torch.Tensor, ignore_index: int, n_out: int) -> torch.Tensor:
+    """Bool map of the pixels the objective counts: ``target != ignore_index`` and ``0 <= target < n_out`` -- what the kernel does not
+    ignore.  (``torch.nn.functional.cross_entropy`` raises a device-side assert for a target outside the classes; here it is ignored.)"""
+    return (target != int(ignore_index)) & (target >= 0) & (target < int(n_out))
+
+
+def head_sanitized_target(target: torch.Tensor, ignore_index: int, n_out: int) -> torch.Tensor:
+    """``target`` with every ignored pixel (``head_valid_pixels``) set to ``ignore_index``: ``F.cross_entropy(logits, that, ignore_index=...)``
+    then has this library's contract for targets outside the classes and torch's arithmetic, without a device-side assert."""
+    return torch.where(head_valid_pixels(target, ignore_index, n_out), target, torch.full_like(target, int(ignore_index)))
+
+
+def head_objective_from_logits(logits: torch.Tensor, target: Optional[torch.Tensor] = None, ignore_index: int = -100, *,
+                               want_loss: bool = False, want_labels: bool = False, want_dlogits: bool = False,
+                               dlogits_channels: Optional[int] = None):
+    """The classification epilogue of ``naf_xna_head_ce_fwd`` as torch ops on materialised logits [B, N, Ho, Wo] (any device, CPU included):
+    what ``xna_head_objective`` composes where the kernel does not serve the geometry, with the same contract.  Returns
+    ``(loss_map, labels, dlogits)``, each None unless wanted: the per-pixel ``logsumexp(z) - z[t]`` (0 where the pixel is ignored; float64 for
+    float64 logits, else float32) [B, Ho, Wo]; ``argmax`` over the classes (uint8 up to 256 classes, else int64); ``softmax(z) - onehot(t)``,
+    zero rows for ignored pixels, bf16 channels-last [B, Ho, Wo, dlogits_channels] with zero pad channels.  Ignored: ``t == ignore_index`` or
+    ``t`` outside [0, N) (see ``head_valid_pixels``)."""
+    B, N, Ho, Wo = logits.shape
+    z = logits if logits.dtype == torch.float64 else logits.float()
+    if (want_loss or want_dlogits) and target is None:
+        raise ValueError("head objective: the loss and the gradient of the logits need a target")
+    loss = labels = g = None
+    if want_labels:
+        labels = z.argmax(dim=1)
+        if N <= 256:
+            labels = labels.to(torch.uint8)
+    if want_loss or want_dlogits:
+        valid = head_valid_pixels(target, ignore_index, N)
+        tc = torch.where(valid, target, torch.zeros_like(target)).unsqueeze(1)
+        lse = torch.logsumexp(z, dim=1)
+        if want_loss:
+            loss = torch.where(valid, lse - z.gather(1, tc)[:, 0], torch.zeros_like(lse))
+        if want_dlogits:
+            gc = int(dlogits_channels) if dlogits_channels is not None else head_dlogits_channels(N)
+            if gc < N:
+                raise ValueError(f"head objective: dlogits_channels {gc} smaller than the {N} classes")
+            sm = torch.exp(z - lse.unsqueeze(1)).permute(0, 2, 3, 1)
+            sm = sm - torch.nn.functional.one_hot(tc[:, 0], N).to(sm.dtype)
+            sm = sm * valid.unsqueeze(-1).to(sm.dtype)
+            g = torch.nn.functional.pad(sm, (0, gc - N)).to(torch.bfloat16)
+    return loss, labels, g
+
+
+def reduce_head_loss(loss_map: torch.Tensor, target: torch.Tensor, ignore_index: int, n_out: int, reduction: str) -> torch.Tensor:
+    """``reduction`` of the per-pixel loss map as ``F.cross_entropy`` defines it: "none" the map, "sum" its sum, "mean" the sum over the number
+    of valid pixels (``head_valid_pixels``, counted on the device without a host synchronisation; no valid pixel: nan, as torch)."""
+    if reduction == "none":
+        return loss_map
+    total = loss_map.sum()
+    if reduction == "sum":
+        return total
+    return total / head_valid_pixels(target, ignore_index, n_out).sum().to(total.dtype)
+
+
+def _check_target(target: torch.Tensor, shape, device, who: str) -> torch.Tensor:
+    if not isinstance(target, torch.Tensor) or target.dtype.is_floating_point or target.dtype.is_complex or target.dtype == torch.bool:
+        raise TypeError(f"{who}: target must be an integer tensor of class indices, got {getattr(target, 'dtype', type(target).__name__)}")
+    if tuple(target.shape) != tuple(shape):
+        raise ValueError(f"{who}: target must be [B, Ho, Wo] = {tuple(shape)}, got {tuple(target.shape)}")
+    if target.device != device:
+        raise ValueError(f"{who}: target is on {target.device}, the features on {device}")
+    return target if target.dtype == torch.int64 else target.long()
+
+
+def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, bias: Optional[torch.Tensor], kernel_size, *,
+                       n_out: int, target: Optional[torch.Tensor] = None, ignore_index: int = -100, want_loss: bool = False,
+                       want_labels: bool = False, want_dlogits: bool = False, return_logits: bool = False, path: str = "auto",
+                       scale: Optional[float] = None, rope_tables=None):
+    """``xna_head_forward`` with the classification objective in the kernel's epilogue (``naf_xna_head_ce_fwd``): one launch gives any of
+    the per-pixel cross-entropy, the argmax labels and ``softmax - onehot`` without the [B, N, Ho, Wo] logits ever being written.
+
+    Arguments as ``xna_head_forward``; ``target`` int64 [B, Ho, Wo] (any strides) is needed for the loss and the gradient.  Returns
+    ``(loss_map, labels, dlogits, logits)``, each None unless asked for: fp32 [B, Ho, Wo], 0 where the pixel is ignored; uint8 [B, Ho, Wo]
+    (int64 beyond 256 classes), the lowest index among equal maxima; bf16 [B, Ho, Wo, Gc] with ``Gc = head_dlogits_channels(n_out)``,
+    every channel written (zeros from ``n_out`` up) and NOT divided by the number of valid pixels -- the ``dout`` the attention backward takes
+    for all heads at once; fp32 logits as ``xna_head_forward(..., out_dtype=float32)`` returns them (``return_logits``).
+    A pixel is ignored when ``target == ignore_index`` OR ``target`` is outside [0, n_out): where ``F.cross_entropy`` raises a device-side
+    assert, the pixel contributes nothing.  ``path="auto"`` composes ``xna_head_forward(..., out_dtype=float32)`` with
+    ``head_objective_from_logits`` where the kernel does not serve the geometry (same contract); ``path="fused"`` insists and raises."""
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
+        _gpu(t, n)
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"xna_head_objective: {n} must be bfloat16, got {t.dtype}")
+        if t.dim() != 5 or t.stride(4) != 1:
+            raise ValueError(f"xna_head_objective: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    if path not in _HEAD_PATHS:
+        raise ValueError(f"xna_head_objective: path must be one of {_HEAD_PATHS}, got {path!r}")
+    if not (want_loss or want_labels or want_dlogits or return_logits):
+        raise ValueError("xna_head_objective: nothing asked for (want_loss / want_labels / want_dlogits / return_logits)")
+    lib = _lib.load()
+    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w, npad = pv_lr.shape[2:]
+    n_out = int(n_out)
+    if k_lr.shape != (B, heads, h, w, Dq) or pv_lr.shape[:2] != (B, heads):
+        raise ValueError(f"xna_head_objective: k_lr {tuple(k_lr.shape)} / pv_lr {tuple(pv_lr.shape)} do not match q {tuple(q.shape)}")
+    if n_out < 1 or npad != head_npad(n_out):
+        raise ValueError(f"xna_head_objective: pv_lr holds {npad} channels, n_out = {n_out} needs {head_npad(max(n_out, 1))}")
+    if bias is not None:
+        _gpu(bias, "bias")
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (n_out,) or not bias.is_contiguous():
+            raise ValueError(f"xna_head_objective: bias must be a contiguous float32 [{n_out}] tensor")
+    dev = q.device
+    if want_loss or want_dlogits:
+        if target is None:
+            raise ValueError("xna_head_objective: the loss and the gradient of the logits need a target")
+    if target is not None:
+        target = _check_target(target, (B, Ho, Wo), dev, "xna_head_objective")
+    gc = head_dlogits_channels(n_out)
+    if path != "composed" and (n_out <= 256 or path == "fused"):
+        out = torch.empty((B, Ho, Wo, n_out), dtype=torch.float32, device=dev) if return_logits else None
+        loss = torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev) if want_loss else None
+        labels = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=dev) if want_labels else None
+        g = torch.empty((B, Ho, Wo, gc), dtype=torch.bfloat16, device=dev) if want_dlogits else None     # the kernel writes every channel
+        a = _lib.XnaHeadCEArgs()
+        a.head = _fill_xna_head(q, k_lr, pv_lr, bias, out if out is not None else q, n_out, ky, kx, path, scale, rope_tables)
+        if out is None:
+            a.head.out, a.head.out_dtype = None, _lib.NAF_F32
+        a.ignore_index, a.dlogits_channels = int(ignore_index), gc
+        for t, ptr, st in ((target if (want_loss or want_dlogits) else None, "target", "t_stride"), (loss, "loss", "loss_stride"),
+                           (labels, "labels", "labels_stride"), (g, "dlogits", "dlogits_stride")):
+            if t is not None:
+                setattr(a, ptr, t.data_ptr())
+                setattr(a, st, I64x3(*[int(t.stride(d)) for d in (0, 1, 2)]))
+        sel = lib.naf_xna_head_ce_select(C.byref(a))
+        if sel == _lib.XNA_HEAD_FUSED:
+            with torch.cuda.device(dev), _Timed("xna_head_ce"):
+                rc = lib.naf_xna_head_ce_fwd(C.byref(a), _stream(q))
+            _lib.check(rc, "naf_xna_head_ce_fwd")
+            return loss, labels, g, (None if out is None else out.permute(0, 3, 1, 2))
+        if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
+            _lib.check(-sel, "naf_xna_head_ce_select")
+        del out, loss, labels, g
+    with _Timed("xna_head_ce_composed"):
+        logits = xna_head_forward(q, k_lr, pv_lr, bias, (ky, kx), n_out=n_out, out_dtype=torch.float32,
+                                  path="auto" if path == "auto" else "composed", scale=scale, rope_tables=rope_tables)
+        loss, labels, g = head_objective_from_logits(logits, target, ignore_index, want_loss=want_loss, want_labels=want_labels,
+                                                     want_dlogits=want_dlogits, dlogits_channels=gc)
+        return loss, labels, g, (logits if return_logits else None)
+
+
+class XnaHeadCEFunction(torch.autograd.Function):
+    """Differentiable cross-entropy of the head-summed attention's logits, with respect to the head (``pv_lr`` and ``bias`` only, as
+    ``XnaHeadFunction``): the forward is ONE launch (``xna_head_objective``) that leaves the loss map and ``g = softmax - onehot`` (bf16,
+    the attention backward's width, unnormalised); the backward hands ``g`` to ``xna_backward`` as the ``dout`` of every head (stride 0) and
+    scales the low-res result by the incoming gradient and, for "mean", by 1 / number of valid pixels -- the backward is linear in ``g``.
+    ``dbias = sum over pixels of g`` times the same.  reduction="none": the incoming gradient is a map, ``g`` is scaled per pixel first.
+    Returns the reduced loss, or ``(loss, labels)`` with ``want_labels``.  ``q`` holds materialised (rotated) queries.
+    Not here: a head-only backward kernel (dq / dk are computed and dropped), class weights, label smoothing, soft targets."""
+
+    @staticmethod
+    def forward(ctx, q, k_lr, pv_lr, bias, target, kernel_size, n_out, ignore_index=-100, reduction="mean", want_labels=False,
+                path="auto", scale=None):
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"reduction must be one of {_REDUCTIONS}, got {reduction!r}")
+        n_out = int(n_out)
+        loss_map, labels, g, _ = xna_head_objective(q, k_lr, pv_lr, bias, kernel_size, n_out=n_out, target=target, ignore_index=ignore_index,
+                                                    want_loss=True, want_labels=want_labels, want_dlogits=True, path=path, scale=scale)
+        tgt = target if target.dtype == torch.int64 else target.long()
+        inv_count = None
+        if reduction == "mean":
+            inv_count = head_valid_pixels(tgt, ignore_index, n_out).sum().float().reciprocal()
+        ctx.save_for_backward(q, k_lr, pv_lr, g, *(() if inv_count is None else (inv_count,)))
+        ctx.kernel_size, ctx.n_out, ctx.scale, ctx.has_bias, ctx.reduction = kernel_size, n_out, scale, bias is not None, reduction
+        loss = reduce_head_loss(loss_map, tgt, ignore_index, n_out, reduction)
+        if want_labels:
+            ctx.mark_non_differentiable(labels)
+            return loss, labels
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss, *rest):
+        q, k_lr, pv_lr, g = ctx.saved_tensors[:4]
+        need_pv, need_b = ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3]
+        N = ctx.n_out
+        dpv = dbias = None
+        if ctx.reduction == "none":
+            g = (g.float() * dloss.unsqueeze(-1)).to(torch.bfloat16)
+            factor = None
+        else:
+            factor = dloss.float() * ctx.saved_tensors[4] if ctx.reduction == "mean" else dloss.float()
+        if need_b:
+            dbias = g.float().sum(dim=(0, 1, 2))[:N]
+            if factor is not None:
+                dbias = dbias * factor
+        if need_pv:
+            B, heads, Ho, Wo, _ = q.shape
+            npad, gc = pv_lr.shape[-1], g.shape[-1]
+            pvp = torch.nn.functional.pad(pv_lr, (0, gc - npad)) if gc != npad else pv_lr
+            _, _, dv = xna_backward(q, k_lr, pvp, g.unsqueeze(1).expand(B, heads, Ho, Wo, gc), ctx.kernel_size, scale=ctx.scale)
+            dv = dv[..., :npad]
+            if factor is not None:
+                dv = dv * factor
+            dpv = dv.to(pv_lr.dtype)
+        return (None, None, dpv, dbias) + (None,) * 8
+
+
 def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables, out_dtype=torch.bfloat16,
                      path: str = "auto") -> bool:
     """True when ``xna_forward(q, ..., rope_tables=...)`` can rotate the queries on load for these shapes (MFMA path,
