@@ -62,7 +62,8 @@ extern "C" {
  * After 0.4.3, same version number (binary compatible: new entry points with a struct of their own, nothing else moves): naf_xna_head_select /
  * naf_xna_head_fwd / naf_xna_head_workspace_bytes -- the attention with a linear head folded in (naf_xna_head_args).  A host detects them by symbol
  * (dlsym), not by naf_version().  Added the same way after them: naf_xna_head_ce_select / naf_xna_head_ce_fwd -- that attention with a
- * cross-entropy / argmax epilogue (naf_xna_head_ce_args, which embeds naf_xna_head_args unchanged). */
+ * cross-entropy / argmax epilogue (naf_xna_head_ce_args, which embeds naf_xna_head_args unchanged); and after those naf_xna_head_cm_select /
+ * naf_xna_head_cm_fwd -- that epilogue counting into a confusion matrix (naf_xna_head_cm_args, which embeds naf_xna_head_ce_args unchanged). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -510,7 +511,8 @@ int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream);
  *   target    device int64 [B, Ho, Wo], element strides t_stride {b, y, x}; NULL when only labels / logits are wanted.  A pixel is
  *             IGNORED when target == ignore_index or target is outside [0, N)
  *   loss      device float [B, Ho, Wo] (loss_stride), or NULL: lse - z[t], 0 for an ignored pixel.  Needs target.  The caller reduces
- *             the map (sum, or sum / number of valid pixels): no atomics here, the result is deterministic
+ *             the map (sum, or sum / number of valid pixels): no floating-point atomics anywhere in this entry or the next, so every
+ *             output is deterministic, bit for bit
  *   labels    device uint8 [B, Ho, Wo] (labels_stride), or NULL: the lowest index among equal maxima (torch.argmax's documented choice)
  *   dlogits   device bf16 [B, Ho, Wo, dlogits_channels] (dlogits_stride {b, y, x}, channel axis contiguous), or NULL: softmax - onehot of a
  *             valid pixel, zeros for an ignored one, rounded once to bf16 and NOT divided by the number of valid pixels (the caller scales
@@ -541,6 +543,34 @@ typedef struct naf_xna_head_ce_args {
 } naf_xna_head_ce_args;
 int naf_xna_head_ce_select(const naf_xna_head_ce_args* a);
 int naf_xna_head_ce_fwd(const naf_xna_head_ce_args* a, naf_stream_t stream);
+
+/* ---- ... and a confusion matrix counted in that epilogue (added after the classification entries; detect by symbol) ------------
+ * What the reference's evaluate() reports (evaluation/eval_seg_probing.py:221-257: accuracy and Jaccard index of the masked predictions)
+ * is a function of one N x N confusion matrix summed over the validation set.  label and target of a pixel are in registers when the
+ * classification epilogue is done, so this entry adds, for every pixel that is not IGNORED (as defined for naf_xna_head_ce_args),
+ *     confusion[target * cm_stride + label] += 1                 (row = target, column = prediction)
+ *   ce         naf_xna_head_ce_args as for naf_xna_head_ce_fwd; every output of that entry stays available in the same launch, bit for bit
+ *              what naf_xna_head_ce_fwd stores for the same arguments, and all of them may be NULL here (the matrix is an output).
+ *              ce.target is required
+ *   confusion  device int64, N rows of cm_stride elements (cm_stride >= N), 8-byte aligned, caller-owned.  The call ACCUMULATES: the
+ *              library never clears it, so one matrix passed for every batch of a validation set ends up as the set's matrix without a
+ *              label map written or a host synchronisation; over several devices, each accumulates its own and the caller sums them
+ *              once.  Elements [row][N .. cm_stride) are not touched
+ * The counts are aggregated within a wave before they are added with integer atomics (vector memory, no return value).  Integer adds
+ * commute exactly, so the matrix -- like every other output -- is deterministic, bit for bit, whatever the order the workgroups run in.
+ * t * cm_stride + label is the one address this library ever forms from a target value, after t and label have been checked to lie in
+ * [0, N); a pixel whose logits are NaN (no maximum) is not counted.
+ * naf_xna_head_cm_select answers as naf_xna_head_ce_select does and additionally refuses (-NAF_ERR_INVALID): a NULL or not 8-byte
+ * aligned confusion, a NULL ce.target, cm_stride < N, non-zero reserved fields.  Served geometries: exactly naf_xna_head_ce_fwd's (at
+ * most 256 classes; beyond, the caller counts the labels of the composed path).  Caller-owned memory and stream; capturable; no workspace. */
+typedef struct naf_xna_head_cm_args {
+    naf_xna_head_ce_args ce; /* ce.target required; every output of ce may be NULL */
+    int64_t* confusion;
+    int64_t cm_stride;
+    int64_t reserved[2]; /* must be 0 */
+} naf_xna_head_cm_args;
+int naf_xna_head_cm_select(const naf_xna_head_cm_args* a);
+int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream);
 
 /* ---- cross-scale neighbourhood attention backward --------------------------------------------------
  * Replaces what autograd runs through legacy_attention (attentions.py:16-29: the backward of na2d_qk, the

@@ -67,6 +67,11 @@ class XnaHeadCEArgs(C.Structure):
     ]
 
 
+class XnaHeadCMArgs(C.Structure):
+    """naf_xna_head_cm_args (added after the classification entries, detected by symbol): naf_xna_head_ce_args plus the confusion matrix."""
+    _fields_ = [("ce", XnaHeadCEArgs), ("confusion", C.c_void_p), ("cm_stride", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
 class StemConv0Args(C.Structure):
     _fields_ = [
         ("image", C.c_void_p), ("y", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("stats_out", C.c_void_p),
@@ -234,6 +239,8 @@ SIGNATURES = {
     "naf_xna_head_fwd": (C.c_int, [C.POINTER(XnaHeadArgs), C.c_void_p]),
     "naf_xna_head_ce_select": (C.c_int, [C.POINTER(XnaHeadCEArgs)]),
     "naf_xna_head_ce_fwd": (C.c_int, [C.POINTER(XnaHeadCEArgs), C.c_void_p]),
+    "naf_xna_head_cm_select": (C.c_int, [C.POINTER(XnaHeadCMArgs)]),
+    "naf_xna_head_cm_fwd": (C.c_int, [C.POINTER(XnaHeadCMArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -393,11 +393,12 @@ int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream) {
 }
 
 // ---- ... and a classification objective folded into its epilogue (cross-entropy, argmax, softmax - onehot) ----
-static int xna_head_ce_validate(const naf_xna_head_ce_args* c) {
+// counts = true: the confusion-matrix entry (naf_xna_head_cm_*), whose matrix is an output of its own
+static int xna_head_ce_validate(const naf_xna_head_ce_args* c, bool counts = false) {
     NAF_REQUIRE(c != nullptr, "naf_xna_head_ce: args is NULL");
     const int rc = xna_head_validate(&c->head, false);
     if (rc != NAF_OK) return rc;
-    NAF_REQUIRE(c->head.out || c->loss || c->labels || c->dlogits, "naf_xna_head_ce: no output requested (out, loss, labels and dlogits are all NULL)");
+    NAF_REQUIRE(counts || c->head.out || c->loss || c->labels || c->dlogits, "naf_xna_head_ce: no output requested (out, loss, labels and dlogits are all NULL)");
     NAF_REQUIRE(c->head.out == nullptr || c->head.out_dtype == NAF_F32, "naf_xna_head_ce: the optional logits are stored as NAF_F32 (out_dtype %d)", c->head.out_dtype);
     NAF_REQUIRE(c->target != nullptr || (c->loss == nullptr && c->dlogits == nullptr), "naf_xna_head_ce: loss and dlogits need a target");
     if (c->dlogits != nullptr) {
@@ -424,6 +425,34 @@ int naf_xna_head_ce_fwd(const naf_xna_head_ce_args* a, naf_stream_t stream) {
     if (sel < 0) return -sel;
     const float scale = a->head.scale > 0.f ? a->head.scale : 1.0f / sqrtf((float)a->head.Dq);
     return naf_launch_xna_head_ce(a, scale, static_cast<hipStream_t>(stream));
+}
+
+// ---- ... and a confusion matrix counted in that epilogue ----
+static int xna_head_cm_validate(const naf_xna_head_cm_args* a) {
+    NAF_REQUIRE(a != nullptr, "naf_xna_head_cm: args is NULL");
+    const int rc = xna_head_ce_validate(&a->ce, true);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(a->confusion != nullptr, "naf_xna_head_cm: confusion is NULL (naf_xna_head_ce_fwd is the call without a matrix)");
+    NAF_REQUIRE(reinterpret_cast<uintptr_t>(a->confusion) % 8 == 0, "naf_xna_head_cm: confusion is not 8-byte aligned");
+    NAF_REQUIRE(a->ce.target != nullptr, "naf_xna_head_cm: a confusion matrix needs a target");
+    NAF_REQUIRE(a->cm_stride >= a->ce.head.N, "naf_xna_head_cm: cm_stride %lld smaller than N %d", (long long)a->cm_stride, a->ce.head.N);
+    NAF_REQUIRE(a->reserved[0] == 0 && a->reserved[1] == 0, "naf_xna_head_cm: reserved fields must be 0");
+    return NAF_OK;
+}
+
+int naf_xna_head_cm_select(const naf_xna_head_cm_args* a) {
+    int rc = xna_head_cm_validate(a);
+    if (rc != NAF_OK) return -rc;
+    rc = naf_xna_head_ce_eligible(&a->ce);
+    if (rc != NAF_OK) return -rc;
+    return NAF_XNA_HEAD_FUSED;
+}
+
+int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_head_cm_select(a);
+    if (sel < 0) return -sel;
+    const float scale = a->ce.head.scale > 0.f ? a->ce.head.scale : 1.0f / sqrtf((float)a->ce.head.Dq);
+    return naf_launch_xna_head_cm(a, scale, static_cast<hipStream_t>(stream));
 }
 
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {

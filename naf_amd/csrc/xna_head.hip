@@ -7,6 +7,9 @@ NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DE
 #define NAF_DECL(K) int naf_xna_head_ce_launch_k##K(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s);
 NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
 #undef NAF_DECL
+#define NAF_DECL(K) int naf_xna_head_cm_launch_k##K(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s);
+NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
+#undef NAF_DECL
 
 static bool head_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
 
@@ -109,11 +112,7 @@ int naf_launch_xna_head(const naf_xna_head_args* a, float scale, hipStream_t s) 
     return NAF_ERR_UNSUPPORTED;
 }
 
-int naf_launch_xna_head_ce(const naf_xna_head_ce_args* c, float scale, hipStream_t s) {
-    XnaHeadParams p;
-    const int rc = head_fill_params(&c->head, scale, "naf_xna_head_ce_fwd", p);
-    if (rc != NAF_OK) return rc;
-    XnaHeadCEExtra x;
+static void head_fill_ce(const naf_xna_head_ce_args* c, XnaHeadCEExtra& x) {
     x.target = c->target;
     x.loss = c->loss;
     x.labels = c->labels;
@@ -123,6 +122,14 @@ int naf_launch_xna_head_ce(const naf_xna_head_ce_args* c, float scale, hipStream
     for (int i = 0; i < 3; ++i) {
         x.ts[i] = c->t_stride[i]; x.ls[i] = c->loss_stride[i]; x.bs[i] = c->labels_stride[i]; x.gs[i] = c->dlogits_stride[i];
     }
+}
+
+int naf_launch_xna_head_ce(const naf_xna_head_ce_args* c, float scale, hipStream_t s) {
+    XnaHeadParams p;
+    const int rc = head_fill_params(&c->head, scale, "naf_xna_head_ce_fwd", p);
+    if (rc != NAF_OK) return rc;
+    XnaHeadCEExtra x;
+    head_fill_ce(c, x);
     switch (c->head.ky) {
         case 3: return naf_xna_head_ce_launch_k3(p, x, s);
         case 5: return naf_xna_head_ce_launch_k5(p, x, s);
@@ -133,5 +140,27 @@ int naf_launch_xna_head_ce(const naf_xna_head_ce_args* c, float scale, hipStream
         case 15: return naf_xna_head_ce_launch_k15(p, x, s);
     }
     naf_set_error("naf_xna_head_ce_fwd: kernel size %d has no instantiation", c->head.ky);
+    return NAF_ERR_UNSUPPORTED;
+}
+
+int naf_launch_xna_head_cm(const naf_xna_head_cm_args* m, float scale, hipStream_t s) {
+    const naf_xna_head_ce_args* c = &m->ce;
+    XnaHeadParams p;
+    const int rc = head_fill_params(&c->head, scale, "naf_xna_head_cm_fwd", p);
+    if (rc != NAF_OK) return rc;
+    XnaHeadCMExtra x;
+    head_fill_ce(c, x.ce);
+    x.confusion = reinterpret_cast<unsigned long long*>(m->confusion);   // counts are non-negative: the 64-bit add is the same for both
+    x.cm_stride = m->cm_stride;
+    switch (c->head.ky) {
+        case 3: return naf_xna_head_cm_launch_k3(p, x, s);
+        case 5: return naf_xna_head_cm_launch_k5(p, x, s);
+        case 7: return naf_xna_head_cm_launch_k7(p, x, s);
+        case 9: return naf_xna_head_cm_launch_k9(p, x, s);
+        case 11: return naf_xna_head_cm_launch_k11(p, x, s);
+        case 13: return naf_xna_head_cm_launch_k13(p, x, s);
+        case 15: return naf_xna_head_cm_launch_k15(p, x, s);
+    }
+    naf_set_error("naf_xna_head_cm_fwd: kernel size %d has no instantiation", c->head.ky);
     return NAF_ERR_UNSUPPORTED;
 }

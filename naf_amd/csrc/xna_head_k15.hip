@@ -8,3 +8,7 @@ int naf_xna_head_launch_k15(const XnaHeadParams& p, int out_dtype, hipStream_t s
 int naf_xna_head_ce_launch_k15(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s) {
     return xna_head_ce_launch_ks<15>(p, x, s);
 }
+
+int naf_xna_head_cm_launch_k15(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s) {
+    return xna_head_cm_launch_ks<15>(p, x, s);
+}

@@ -34,6 +34,19 @@
 //   are stored by the pixel's grp = 0 lane; g is rounded once to bf16 and stored as 8-byte vectors by the lanes that own the channels,
 //   zeros for channels N .. gc-1 -- also past the NCT*16 accumulator channels (Npad = 160 -> gc = 192), so the host never clears the buffer.
 //   Every output is optional (NULL: a wave-uniform branch).  No atomics, no cross-workgroup reduction: the host sums the loss map.
+//
+// Confusion matrix (Extra = XnaHeadCMExtra, naf_xna_head_cm_fwd): further instantiations of the classification epilogue; the CE = false and
+// the XnaHeadCEExtra ones keep their code (`if constexpr`).  A pixel that is inside the image, of a live tile and not ignored adds one to
+// confusion[t][label] (int64, caller-owned, accumulated).  Never one atomic per pixel: label and t are known to all four lanes of a pixel,
+// so tile u of the wave puts its key t * 256 + label into the lanes grp == u (-1 = counts nothing: repeated last pixel of a partial tile,
+// dead tile, ignored pixel), and after the tiles ONE ballot loop runs over the wave: take the key of the first lane left, ballot the
+// lanes that hold it, that lane owns the population count, clear them, repeat.  A tile lies inside one low-res cell, so on a real
+// segmentation this is one or two rounds.  The FIRST pair of every wave goes to LDS (64 bytes of static LDS, these instantiations only)
+// and, after a barrier, eight lanes of wave 0 merge the eight pairs: a cell inside one segment costs ONE atomic per round instead
+// of eight on the same address -- with every pixel of G1 / N = 21 on one counter 0.463 -> 0.206 ms (profiles/head_confusion.txt).  Later pairs
+// of a wave are added directly.  The adds are no-return 64-bit vector atomics; integer adds commute exactly, so the matrix does not
+// depend on the order.  t * cm_stride + label is the ONE address formed from the target, after t AND label have been checked to lie
+// in [0, N) (a pixel whose logits are NaN has no maximum and counts nothing).
 #pragma once
 #include "xna_mfma_kernel.h"
 
@@ -66,6 +79,14 @@ struct XnaHeadCEExtra {
     int64_t ts[3], ls[3], bs[3], gs[3];   // {b, y, x} element strides of target / loss / labels / dlogits
     int32_t gc;              // channels of a dlogits row the kernel writes (multiple of 8, >= npad)
 };
+// ... and with a confusion matrix: XnaHeadCEExtra first, so the epilogue reads both through the same pointer
+struct XnaHeadCMExtra {
+    XnaHeadCEExtra ce;
+    unsigned long long* confusion;   // [N][cm_stride] counts, row = target, column = label; never nullptr (host)
+    int64_t cm_stride;               // >= N (host)
+};
+template <typename... T> struct XnaHeadIsCM { static constexpr bool value = false; };
+template <> struct XnaHeadIsCM<XnaHeadCMExtra> { static constexpr bool value = true; };
 // they are the kernel's SECOND argument: it follows XnaHeadParams in the kernel-argument segment at its natural alignment
 constexpr size_t XNA_HEAD_CE_ARG_OFFSET = (sizeof(XnaHeadParams) + alignof(XnaHeadCEExtra) - 1) / alignof(XnaHeadCEExtra) * alignof(XnaHeadCEExtra);
 
@@ -81,6 +102,7 @@ constexpr size_t xna_head_lds_for(int ks, int nct) { return (size_t)(ks * ks) * 
 template <int KS, int NCT, typename OutT, bool CE = false, typename... Extra>
 __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHeadParams p, const Extra... extra) {
     static_assert(sizeof...(Extra) == (CE ? 1 : 0), "the classification epilogue takes XnaHeadCEExtra as its second argument");
+    constexpr bool CM = XnaHeadIsCM<Extra...>::value;   // ... or XnaHeadCMExtra: it counts into a confusion matrix as well
     constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
     constexpr int TPW = xna_head_tpw(KS, NCT);
     using G = XnaGeom<KS, 1>;
@@ -293,6 +315,8 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
             int ecol = col, egrp = grp;
             asm volatile("" : "+v"(ecol), "+v"(egrp));
             const XnaHeadCEExtra __attribute__((address_space(4)))* x = reinterpret_cast<const XnaHeadCEExtra __attribute__((address_space(4)))*>(ka + XNA_HEAD_CE_ARG_OFFSET);
+            [[maybe_unused]] int cmkey = -1;   // CM: t * 256 + label of tile u's pixel in the lanes grp == u, -1 = counts nothing
+            static_assert(!CM || TPW <= 4, "one lane group per tile of the wave");
 #pragma unroll
             for (int u = 0; u < TPW; ++u) {
                 if (!livev[u]) continue;   // wave-uniform: the four-lane reductions below run on whole waves
@@ -342,6 +366,10 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
                         x->loss[b * x->ls[0] + gy * x->ls[1] + gx * x->ls[2]] = t >= 0 ? (mall + __builtin_amdgcn_logf(sum) * LN2) - zt : 0.f;
                     if (x->labels != nullptr) x->labels[b * x->bs[0] + gy * x->bs[1] + gx * x->bs[2]] = (uint8_t)label;
                 }
+                if constexpr (CM) {
+                    // 0 <= t < N <= 256 (checked above); label < N unless the logits are NaN (no lane holds the maximum): such a pixel counts nothing
+                    if (egrp == u && inpx && t >= 0 && (unsigned)label < (unsigned)p.N) cmkey = t * 256 + label;
+                }
                 if (p.out != nullptr && inpx) {
                     OutT* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
 #pragma unroll
@@ -370,6 +398,50 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
                     }
                     // channels past the accumulators (Npad = 160 -> gc = 192): plain zero stores
                     for (int c0 = DVT + egrp * 4; c0 < x->gc; c0 += 16) *reinterpret_cast<bf16x4_t*>(gp + c0) = bf16x4_t{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+                }
+            }
+            if constexpr (CM) {
+                // ---- confusion[t][label] += 1 per counted pixel, aggregated over the wave and then over the workgroup (see the header comment) ----
+                const XnaHeadCMExtra __attribute__((address_space(4)))* xc = reinterpret_cast<const XnaHeadCMExtra __attribute__((address_space(4)))*>(ka + XNA_HEAD_CE_ARG_OFFSET);
+                int elane = lane;   // opaque like ecol / egrp: nothing of this block is computed above the head loop and held through it
+                asm volatile("" : "+v"(elane));
+                __shared__ int cm_key[NW], cm_cnt[NW];   // each wave's first (key, count) pair of the round; -1 = none
+                auto count = [&](int key, int n) __attribute__((always_inline)) {
+                    __hip_atomic_fetch_add(xc->confusion + (int64_t)(key >> 8) * xc->cm_stride + (key & 255), (unsigned long long)n, __ATOMIC_RELAXED,
+                                           __HIP_MEMORY_SCOPE_AGENT);
+                };
+                unsigned long long todo = __ballot(cmkey >= 0);
+                bool first = true;
+                if (todo == 0ull && elane == 0) cm_key[wave] = -1;
+                while (todo != 0ull) {   // wave-uniform
+                    const int lead = __builtin_ctzll(todo);
+                    const int key = __builtin_amdgcn_readlane(cmkey, lead);
+                    const unsigned long long same = __ballot(cmkey == key);
+                    const int n = __builtin_popcountll(same);
+                    if (elane == lead) {
+                        if (first) {   // wave-uniform: to the workgroup's merge
+                            cm_key[wave] = key;
+                            cm_cnt[wave] = n;
+                        } else {
+                            count(key, n);
+                        }
+                    }
+                    first = false;
+                    todo &= ~same;
+                }
+                __syncthreads();   // the next round writes these slots only after two more barriers (head loop): wave 0 has read them by then
+                if (wave == 0) {
+                    // lane i < NW takes wave i's pair; the lowest lane of every distinct key adds the sum of that key's counts
+                    const int kk = elane < NW ? cm_key[elane & (NW - 1)] : -1, cc = cm_cnt[elane & (NW - 1)];
+                    int n = 0;
+                    bool lowest = kk >= 0;
+#pragma unroll
+                    for (int j = 0; j < NW; ++j) {
+                        const int kj = __builtin_amdgcn_readlane(kk, j), cj = __builtin_amdgcn_readlane(cc, j);
+                        n += kj == kk ? cj : 0;
+                        lowest = lowest && !(kj == kk && j < elane);
+                    }
+                    if (lowest) count(kk, n);
                 }
             }
         } else {
@@ -448,5 +520,32 @@ static int xna_head_ce_launch_ks(const XnaHeadParams& p, const XnaHeadCEExtra& x
     if (nct == 10) return xna_head_ce_launch_one<KS, 10>(p, x, s);
     if (nct == 16) return xna_head_ce_launch_one<KS, 16>(p, x, s);
     naf_set_error("xna_head_ce: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
+    return NAF_ERR_UNSUPPORTED;
+}
+
+// ---- ... with a confusion matrix: one more instantiation per (window, channel-tile count), selected only by naf_xna_head_cm_fwd ----
+template <int KS, int NCT>
+static int xna_head_cm_launch_one(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s) {
+    constexpr size_t lds = xna_head_lds_for(KS, NCT);
+    auto kern = xna_head_kernel<KS, NCT, float, true, XnaHeadCMExtra>;
+    if (lds > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) {
+            naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+            return NAF_ERR_LAUNCH;
+        }
+    }
+    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, x);
+    return naf_check_launch("xna_head_kernel (confusion matrix)");
+}
+
+template <int KS>
+static int xna_head_cm_launch_ks(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s) {
+    const int nct = xna_head_nct(p.npad);
+    if (nct == 2) return xna_head_cm_launch_one<KS, 2>(p, x, s);
+    if (nct == 4) return xna_head_cm_launch_one<KS, 4>(p, x, s);
+    if (nct == 10) return xna_head_cm_launch_one<KS, 10>(p, x, s);
+    if (nct == 16) return xna_head_cm_launch_one<KS, 16>(p, x, s);
+    naf_set_error("xna_head_cm: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
     return NAF_ERR_UNSUPPORTED;
 }

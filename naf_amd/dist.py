@@ -125,6 +125,21 @@ def gather_outputs(local: torch.Tensor, n_total: int) -> torch.Tensor:
     return torch.cat([o[: b - a] for o, (a, b) in zip(outs, sizes)], dim=0)
 
 
+def reduce_confusion(cm: torch.Tensor) -> torch.Tensor:
+    """Sum a confusion matrix (``naf(..., head=probe, target=t, confusion=cm)``, int64 [N, N]) over the ranks: ONE ``all_reduce(SUM)`` of
+    N x N integers, in place, returning ``cm``.  Each rank accumulates over its own shard of the validation set and calls this once at
+    the end -- the data path stays free of collectives.  Without an initialised process group it returns its argument untouched."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return cm
+    if cm.is_contiguous():
+        dist.all_reduce(cm, op=dist.ReduceOp.SUM)
+        return cm
+    buf = cm.contiguous()         # a matrix with a row stride: reduce a dense copy, write it back
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    cm.copy_(buf)
+    return cm
+
+
 class ShardedNAF:
     """Runs ``model`` on this rank's slice of a batch, in micro-batches to bound the encoder's activations (bf16 guidance
     at full resolution: 1 GB per image in flight).  ``concat=False`` returns the list of micro-batch outputs instead of

@@ -854,7 +854,7 @@ class NAF(nn.Module):
         return (out, logits) if return_weights else out
 
     def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
-                reduction="mean", predict=False, **kwargs):
+                reduction="mean", predict=False, confusion=None, **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -891,7 +891,25 @@ class NAF(nn.Module):
         as in torch.  The gradient modes are those of the logits call: frozen upsampler and a probe that requires grad -- fused and
         differentiable with respect to the probe (``ops.XnaHeadCEFunction``); no gradient wanted -- the kernel with rotate-on-load; a
         gradient for the upsampler, the image or the features -- the unfused ``F.cross_entropy(head(self.forward_train(...)).float(), ...)``.
-        Not offered: class weights, label smoothing, soft targets, a confusion matrix, ``capture()`` of this call."""
+
+        ``confusion`` (keyword only, with ``head`` and ``target``): the probe's EVALUATION -- what the reference's ``evaluate()``
+        (evaluation/eval_seg_probing.py:221-257) accumulates for its accuracy and Jaccard index.  ``confusion=True`` returns a fresh int64
+        [N, N] matrix of this call, ``cm[t, p]`` = number of pixels with target ``t`` and predicted label ``p`` (row = target, column =
+        prediction) over the pixels that are not ignored (``target != ignore_index`` and ``0 <= target < N``); an int64 [N, N] tensor on
+        the features' device (columns contiguous) is ACCUMULATED into in place and returned, so an evaluation loop passes the same
+        tensor for every batch and never synchronises with the host; ``naf_amd.confusion_metrics(cm)`` turns it into accuracy and IoU,
+        ``naf_amd.dist.reduce_confusion(cm)`` sums it over ranks.  The call returns the matrix IN PLACE OF the loss -- no cross-entropy is
+        computed (``reduction`` is not used) -- or ``(matrix, labels)`` with ``predict=True``.  The head-summed kernel's epilogue counts
+        (``naf_xna_head_cm_fwd``: aggregated per wave, integer atomics, bit-reproducible); no label map is written unless asked for.  It
+        is never differentiable and runs the inference kernels (rotate-on-load where the geometry allows) whatever the gradient mode.
+        Geometries or class counts the kernel does not serve count the labels of the composed path, same contract.  An empty batch leaves
+        the matrix as it was.  Loss and matrix from ONE launch stay available one level down: ``ops.xna_head_objective(..., want_loss=True,
+        confusion=cm)``.
+        Not offered: class weights, label smoothing, soft targets, ``capture()`` of this call."""
+        if confusion is not None and confusion is not False:
+            if head is None or target is None:
+                raise ValueError("naf(..., confusion=...) is the evaluation of a probe against a target: pass head=probe and target=... as well")
+            return self._forward_head_confusion(image, features, output_size, return_weights, head, target, ignore_index, reduction, bool(predict), confusion)
         if target is not None or predict:
             if head is None:
                 raise ValueError("naf(..., target=... / predict=True) is the objective of a probe: pass head=probe as well")
@@ -989,6 +1007,42 @@ class NAF(nn.Module):
                                                                     scale=self.upsampler.scale, rope_tables=tabs)
                     loss = None if target is None else ops.reduce_head_loss(loss_map, target, ignore_index, N, reduction)
         return pack(loss, None if labels is None else labels.long())       # the kernel writes uint8; widened so that it drops into pred == target
+
+    def _forward_head_confusion(self, image, features, output_size, return_weights, head, target, ignore_index, reduction, predict, confusion):
+        """``forward(..., head=head, target=..., confusion=True / matrix)``: see ``forward``."""
+        if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
+        weight, bias = _linear_head(head, features.shape[1])      # host-side validation first: nothing has touched the device yet
+        if return_weights:
+            raise ValueError("naf(..., head=...) does not return attention scores: call naf(image, features, size, return_weights=True) for them")
+        if reduction not in ops._REDUCTIONS:
+            raise ValueError(f"reduction must be one of {ops._REDUCTIONS}, got {reduction!r}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, N = image.shape[0], weight.shape[0]
+        ignore_index = int(ignore_index)
+        target = ops._check_target(target, (B, ho, wo), features.device, "naf(..., target=...)")
+        if confusion is not True:
+            if not isinstance(confusion, torch.Tensor):
+                raise TypeError(f"confusion must be True or an int64 [N, N] tensor, got {type(confusion).__name__}")
+            ops._check_confusion(confusion, N, features.device, "naf(..., confusion=...)")
+        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
+            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
+                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
+        heads = self.upsampler.num_heads
+        if features.shape[1] % heads:
+            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
+        with torch.no_grad():
+            cm = torch.zeros((N, N), dtype=torch.int64, device=features.device) if confusion is True else confusion
+            if B == 0:
+                return (cm, torch.empty((0, ho, wo), dtype=torch.int64, device=features.device)) if predict else cm
+            ksz, lr = self.upsampler.kernel_size, features.shape[-2:]
+            fusable = lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, rope_tables=tabs) == "fused"
+            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
+            pv5, b32 = ops.project_head_values(weight, bias, features, heads)
+            with ops._Timed("attention"):
+                _, labels, _, _ = ops.xna_head_objective(q5, k5, pv5, b32, ksz, n_out=N, target=target, ignore_index=ignore_index,
+                                                         want_labels=predict, scale=self.upsampler.scale, rope_tables=tabs, confusion=cm)
+            return (cm, labels.long()) if predict else cm
 
     def _forward_inference(self, image, features, output_size, return_weights=False):
         if not (image.is_cuda and features.is_cuda):

@@ -13,6 +13,7 @@ Reference counterparts (paths relative to the reference repo):
 """
 from __future__ import annotations
 
+import collections
 import contextlib
 import ctypes as C
 import threading
@@ -1054,10 +1055,73 @@ def _check_target(target: torch.Tensor, shape, device, who: str) -> torch.Tensor
     return target if target.dtype == torch.int64 else target.long()
 
 
+def _check_confusion(confusion, n_out: int, device, who: str) -> None:
+    if not isinstance(confusion, torch.Tensor) or confusion.dtype != torch.int64:
+        raise TypeError(f"{who}: confusion must be an int64 tensor, got {getattr(confusion, 'dtype', type(confusion).__name__)}")
+    if tuple(confusion.shape) != (int(n_out), int(n_out)) or confusion.stride(1) != 1 or confusion.stride(0) < int(n_out):
+        raise ValueError(f"{who}: confusion must be [N, N] = [{int(n_out)}, {int(n_out)}] with contiguous columns, "
+                         f"got {tuple(confusion.shape)} with strides {tuple(confusion.stride())}")
+    if confusion.device != device:
+        raise ValueError(f"{who}: confusion is on {confusion.device}, the features on {device}")
+
+
+def head_confusion_from_labels(labels: torch.Tensor, target: torch.Tensor, ignore_index: int, n_out: int,
+                               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The confusion matrix of ``naf_xna_head_cm_fwd`` as torch ops (any device, CPU included): int64 [N, N], ``cm[t, p]`` = number of
+    pixels with target ``t`` and predicted label ``p`` (row = target, column = prediction) over the pixels ``head_valid_pixels`` counts --
+    ``target != ignore_index`` and ``0 <= target < n_out``; everything else adds nothing.  ``out`` (int64 [N, N], columns contiguous, any row
+    stride): the counts are ADDED to it and it is returned; None: a fresh matrix.  What ``xna_head_objective`` composes where the kernel
+    does not serve the geometry, and the definition the tests hold the kernel to.  No host synchronisation: the counts are an
+    ``index_add_`` of ones (integer adds, exact in any order) -- ``bincount(t * N + p, minlength=N * N)`` without its size query.  A label
+    outside [0, N) (none comes out of an argmax over N classes) is not counted either."""
+    N = int(n_out)
+    if labels.shape != target.shape:
+        raise ValueError(f"head_confusion_from_labels: labels {tuple(labels.shape)} and target {tuple(target.shape)} differ in shape")
+    target = target if target.dtype == torch.int64 else target.long()
+    pred = labels.long()
+    valid = head_valid_pixels(target, ignore_index, N) & (pred >= 0) & (pred < N)
+    key = torch.where(valid, target * N + pred, torch.full_like(target, N * N))      # the extra slot takes what is not counted
+    counts = torch.zeros(N * N + 1, dtype=torch.int64, device=target.device)
+    counts.index_add_(0, key.reshape(-1), torch.ones((), dtype=torch.int64, device=target.device).expand(key.numel()))
+    cm = counts[:N * N].view(N, N)
+    if out is None:
+        return cm
+    _check_confusion(out, N, target.device, "head_confusion_from_labels")
+    return out.add_(cm)
+
+
+ConfusionMetrics = collections.namedtuple("ConfusionMetrics", ("accuracy", "iou", "miou", "present"))
+
+
+def confusion_metrics(cm: torch.Tensor) -> "ConfusionMetrics":
+    """Accuracy and intersection-over-union from a confusion matrix [N, N] (row = target, column = prediction), in float64 on the matrix's
+    device, without a host synchronisation.  Returns ``ConfusionMetrics(accuracy, iou, miou, present)``:
+
+        accuracy = trace(cm) / sum(cm)                                   (micro: every counted pixel weighs the same)
+        iou[c]   = cm[c, c] / (row_c + col_c - cm[c, c]),  0 where that union is 0
+        present  = union != 0                                            (bool [N]: the class occurs in the targets or the predictions)
+        miou     = mean of iou over the present classes
+
+    A class absent from both targets and predictions is left out of ``miou``; one that is predicted but never a target counts with IoU 0.
+    A matrix without counts (every pixel ignored) gives nan for ``accuracy`` and ``miou``, as a 0 / 0 mean is in torch.  These are the
+    definitions the reference's ``evaluate()`` gets from ``torchmetrics`` ``Accuracy(task="multiclass")`` (its default, micro) and
+    ``JaccardIndex(task="multiclass")`` as far as their documentation goes; ``torchmetrics`` is not a dependency of this project and the
+    equivalence has NOT been verified against it."""
+    if not isinstance(cm, torch.Tensor) or cm.dim() != 2 or cm.shape[0] != cm.shape[1] or cm.dtype.is_floating_point or cm.dtype == torch.bool:
+        raise ValueError(f"confusion_metrics: an integer [N, N] matrix is expected, got {getattr(cm, 'dtype', type(cm).__name__)} "
+                         f"{tuple(getattr(cm, 'shape', ()))}")
+    c = cm.to(torch.float64)
+    diag, total = c.diagonal(), c.sum()
+    union = c.sum(dim=1) + c.sum(dim=0) - diag
+    present = union != 0
+    iou = torch.where(present, diag / torch.where(present, union, torch.ones_like(union)), torch.zeros_like(union))
+    return ConfusionMetrics(diag.sum() / total, iou, iou.sum() / present.sum().to(torch.float64), present)
+
+
 def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, bias: Optional[torch.Tensor], kernel_size, *,
                        n_out: int, target: Optional[torch.Tensor] = None, ignore_index: int = -100, want_loss: bool = False,
                        want_labels: bool = False, want_dlogits: bool = False, return_logits: bool = False, path: str = "auto",
-                       scale: Optional[float] = None, rope_tables=None):
+                       scale: Optional[float] = None, rope_tables=None, confusion: Optional[torch.Tensor] = None):
     """``xna_head_forward`` with the classification objective in the kernel's epilogue (``naf_xna_head_ce_fwd``): one launch gives any of
     the per-pixel cross-entropy, the argmax labels and ``softmax - onehot`` without the [B, N, Ho, Wo] logits ever being written.
 
@@ -1068,7 +1132,11 @@ def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor,
     for all heads at once; fp32 logits as ``xna_head_forward(..., out_dtype=float32)`` returns them (``return_logits``).
     A pixel is ignored when ``target == ignore_index`` OR ``target`` is outside [0, n_out): where ``F.cross_entropy`` raises a device-side
     assert, the pixel contributes nothing.  ``path="auto"`` composes ``xna_head_forward(..., out_dtype=float32)`` with
-    ``head_objective_from_logits`` where the kernel does not serve the geometry (same contract); ``path="fused"`` insists and raises."""
+    ``head_objective_from_logits`` where the kernel does not serve the geometry (same contract); ``path="fused"`` insists and raises.
+    ``confusion``: an int64 [n_out, n_out] device tensor (any row stride, columns contiguous) that the call ACCUMULATES into in the same
+    launch (``naf_xna_head_cm_fwd``): ``confusion[t, label] += 1`` for every pixel that is not ignored; needs ``target``; the returned
+    4-tuple is unchanged and may be all None.  Loss, labels and matrix of one launch are available here together.  The composed route
+    counts its labels with ``head_confusion_from_labels``."""
     for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
         _gpu(t, n)
         if t.dtype != torch.bfloat16:
@@ -1077,8 +1145,8 @@ def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor,
             raise ValueError(f"xna_head_objective: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
     if path not in _HEAD_PATHS:
         raise ValueError(f"xna_head_objective: path must be one of {_HEAD_PATHS}, got {path!r}")
-    if not (want_loss or want_labels or want_dlogits or return_logits):
-        raise ValueError("xna_head_objective: nothing asked for (want_loss / want_labels / want_dlogits / return_logits)")
+    if not (want_loss or want_labels or want_dlogits or return_logits or confusion is not None):
+        raise ValueError("xna_head_objective: nothing asked for (want_loss / want_labels / want_dlogits / return_logits / confusion)")
     lib = _lib.load()
     ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
     B, heads, Ho, Wo, Dq = q.shape
@@ -1096,6 +1164,10 @@ def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor,
     if want_loss or want_dlogits:
         if target is None:
             raise ValueError("xna_head_objective: the loss and the gradient of the logits need a target")
+    if confusion is not None:
+        if target is None:
+            raise ValueError("xna_head_objective: a confusion matrix needs a target")
+        _check_confusion(confusion, n_out, dev, "xna_head_objective")
     if target is not None:
         target = _check_target(target, (B, Ho, Wo), dev, "xna_head_objective")
     gc = head_dlogits_channels(n_out)
@@ -1109,26 +1181,35 @@ def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor,
         if out is None:
             a.head.out, a.head.out_dtype = None, _lib.NAF_F32
         a.ignore_index, a.dlogits_channels = int(ignore_index), gc
-        for t, ptr, st in ((target if (want_loss or want_dlogits) else None, "target", "t_stride"), (loss, "loss", "loss_stride"),
+        for t, ptr, st in ((target if (want_loss or want_dlogits or confusion is not None) else None, "target", "t_stride"), (loss, "loss", "loss_stride"),
                            (labels, "labels", "labels_stride"), (g, "dlogits", "dlogits_stride")):
             if t is not None:
                 setattr(a, ptr, t.data_ptr())
                 setattr(a, st, I64x3(*[int(t.stride(d)) for d in (0, 1, 2)]))
-        sel = lib.naf_xna_head_ce_select(C.byref(a))
+        if confusion is not None:              # the same epilogue counting into the caller's matrix: an entry point of its own
+            m = _lib.XnaHeadCMArgs()
+            m.ce, m.confusion, m.cm_stride = a, confusion.data_ptr(), int(confusion.stride(0))
+            a, entry, select, fwd = m, "naf_xna_head_cm", lib.naf_xna_head_cm_select, lib.naf_xna_head_cm_fwd
+        else:
+            entry, select, fwd = "naf_xna_head_ce", lib.naf_xna_head_ce_select, lib.naf_xna_head_ce_fwd
+        sel = select(C.byref(a))
         if sel == _lib.XNA_HEAD_FUSED:
             with torch.cuda.device(dev), _Timed("xna_head_ce"):
-                rc = lib.naf_xna_head_ce_fwd(C.byref(a), _stream(q))
-            _lib.check(rc, "naf_xna_head_ce_fwd")
+                rc = fwd(C.byref(a), _stream(q))
+            _lib.check(rc, entry + "_fwd")
             return loss, labels, g, (None if out is None else out.permute(0, 3, 1, 2))
         if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
-            _lib.check(-sel, "naf_xna_head_ce_select")
+            _lib.check(-sel, entry + "_select")
         del out, loss, labels, g
     with _Timed("xna_head_ce_composed"):
         logits = xna_head_forward(q, k_lr, pv_lr, bias, (ky, kx), n_out=n_out, out_dtype=torch.float32,
                                   path="auto" if path == "auto" else "composed", scale=scale, rope_tables=rope_tables)
-        loss, labels, g = head_objective_from_logits(logits, target, ignore_index, want_loss=want_loss, want_labels=want_labels,
+        loss, labels, g = head_objective_from_logits(logits, target, ignore_index, want_loss=want_loss,
+                                                     want_labels=want_labels or confusion is not None,
                                                      want_dlogits=want_dlogits, dlogits_channels=gc)
-        return loss, labels, g, (logits if return_logits else None)
+        if confusion is not None:
+            head_confusion_from_labels(labels, target, ignore_index, n_out, out=confusion)
+        return loss, (labels if want_labels else None), g, (logits if return_logits else None)
 
 
 class XnaHeadCEFunction(torch.autograd.Function):
