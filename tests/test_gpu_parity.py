@@ -12,6 +12,8 @@ Tolerances (fp, stated here as the prompt asks):
       with its measured budget (profiles/r04_tolerance_budget.txt, tools/tolerance_probe.py: measured maximum x 1.5 and a bound
       on the fraction of elements outside 8c): cells of 2 pixels 3.6e-2, of 1 pixel 6e-2 (+ 1e-2*|ref|), the one-head k=5
       denoising golden F6 4.5e-2 (profiles/r03_f6_error.txt).  Everything else, bf16 I/O and 14-pixel cells included, holds 8c.
+  * these constants are sized for unit-variance inputs; the scale-aware per-element bounds (n bf16 roundings * 2^-8 * abs-sum) on channel
+      offsets, outlier tokens, 2^+-10 magnitudes, peaked / offset scores and image-like images are in tests/test_gpu_input_statistics.py.
 """
 import os
 
