@@ -37,6 +37,23 @@ int naf_cu_count() {
     return cached[dev];
 }
 
+// The softmax scale of a call: the caller's, or 1 / sqrt(Dq) when it leaves the field at 0.
+static float xna_scale(float scale, int Dq) { return scale > 0.f ? scale : 1.0f / sqrtf((float)Dq); }
+
+// The geometry every attention entry asks for (A: naf_xna_args, naf_xna_head_args or naf_xna_bwd_args; `who` is the entry's name in the
+// messages; Dv is a parameter because the head's arguments have none).
+template <typename A>
+static int xna_geometry_validate(const char* who, const A* a, int Dv) {
+    NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 && a->Dq > 0 && Dv > 0, "%s: non-positive size", who);
+    NAF_REQUIRE(a->ky > 0 && a->kx > 0 && (a->ky & 1) && (a->kx & 1), "%s: kernel size must be odd, got %dx%d", who, a->ky, a->kx);
+    // attentions.py:54-57 dilation = Ho // h ; NATTEN: kernel_size * dilation <= extent
+    NAF_REQUIRE(a->Ho >= a->h && a->Wo >= a->w, "%s: output %dx%d smaller than feature grid %dx%d (dilation 0)", who, a->Ho, a->Wo, a->h, a->w);
+    NAF_REQUIRE((int64_t)a->ky * (a->Ho / a->h) <= a->Ho && (int64_t)a->kx * (a->Wo / a->w) <= a->Wo,
+                "%s: kernel_size * dilation exceeds the output extent (k=%dx%d, dilation=%dx%d, out=%dx%d)",
+                who, a->ky, a->kx, a->Ho / a->h, a->Wo / a->w, a->Ho, a->Wo);
+    return NAF_OK;
+}
+
 extern "C" {
 
 int naf_version(void) { return NAF_HIP_VERSION; }
@@ -275,15 +292,9 @@ int naf_stem_act_bwd(const naf_stem_act_bwd_args* a, naf_stream_t stream) {
 static int xna_validate(const naf_xna_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_fwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->out, "naf_xna_fwd: NULL tensor pointer");
-    NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 && a->Dq > 0 && a->Dv > 0,
-                "naf_xna_fwd: non-positive size");
+    const int rc = xna_geometry_validate("naf_xna_fwd", a, a->Dv);
+    if (rc != NAF_OK) return rc;
     NAF_REQUIRE(a->out_dtype == NAF_BF16 || a->out_dtype == NAF_F32, "naf_xna_fwd: out_dtype %d", a->out_dtype);
-    NAF_REQUIRE(a->ky > 0 && a->kx > 0 && (a->ky & 1) && (a->kx & 1), "naf_xna_fwd: kernel size must be odd, got %dx%d", a->ky, a->kx);
-    // attentions.py:54-57 dilation = Ho // h ; NATTEN: kernel_size * dilation <= extent
-    NAF_REQUIRE(a->Ho >= a->h && a->Wo >= a->w, "naf_xna_fwd: output %dx%d smaller than feature grid %dx%d (dilation 0)", a->Ho, a->Wo, a->h, a->w);
-    NAF_REQUIRE((int64_t)a->ky * (a->Ho / a->h) <= a->Ho && (int64_t)a->kx * (a->Wo / a->w) <= a->Wo,
-                "naf_xna_fwd: kernel_size * dilation exceeds the output extent (k=%dx%d, dilation=%dx%d, out=%dx%d)",
-                a->ky, a->kx, a->Ho / a->h, a->Wo / a->w, a->Ho, a->Wo);
     NAF_REQUIRE(a->path == NAF_XNA_AUTO || a->path == NAF_XNA_MFMA || a->path == NAF_XNA_GENERIC || a->path == NAF_XNA_UNION || a->path == NAF_XNA_ROWS, "naf_xna_fwd: path %d", a->path);
     NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_fwd: rope_tab_y and rope_tab_x must be given together");
     return NAF_OK;
@@ -344,7 +355,7 @@ size_t naf_workspace_bytes(const naf_xna_args* a) {
 int naf_xna_fwd(const naf_xna_args* a, naf_stream_t stream) {
     const int sel = naf_xna_select(a);
     if (sel < 0) return -sel;
-    const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
+    const float scale = xna_scale(a->scale, a->Dq);
     if (sel == NAF_XNA_MFMA) return naf_launch_xna_mfma(a, scale, static_cast<hipStream_t>(stream));
     if (sel == NAF_XNA_UNION) return naf_launch_xna_union(a, scale, static_cast<hipStream_t>(stream));
     if (sel == NAF_XNA_ROWS) return naf_launch_xna_rows(a, scale, static_cast<hipStream_t>(stream));
@@ -356,14 +367,10 @@ int naf_xna_fwd(const naf_xna_args* a, naf_stream_t stream) {
 static int xna_head_validate(const naf_xna_head_args* a, bool need_out = true) {
     NAF_REQUIRE(a != nullptr, "naf_xna_head_fwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && (a->out || !need_out), "naf_xna_head_fwd: NULL tensor pointer");
-    NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 && a->Dq > 0, "naf_xna_head_fwd: non-positive size");
+    const int rc = xna_geometry_validate("naf_xna_head_fwd", a, 1);   // the value channels are N, with a range of their own
+    if (rc != NAF_OK) return rc;
     NAF_REQUIRE(a->N >= 1 && a->N <= 256, "naf_xna_head_fwd: N must be in 1 .. 256, got %d", a->N);
     NAF_REQUIRE(a->out_dtype == NAF_BF16 || a->out_dtype == NAF_F32, "naf_xna_head_fwd: out_dtype %d", a->out_dtype);
-    NAF_REQUIRE(a->ky > 0 && a->kx > 0 && (a->ky & 1) && (a->kx & 1), "naf_xna_head_fwd: kernel size must be odd, got %dx%d", a->ky, a->kx);
-    NAF_REQUIRE(a->Ho >= a->h && a->Wo >= a->w, "naf_xna_head_fwd: output %dx%d smaller than feature grid %dx%d (dilation 0)", a->Ho, a->Wo, a->h, a->w);
-    NAF_REQUIRE((int64_t)a->ky * (a->Ho / a->h) <= a->Ho && (int64_t)a->kx * (a->Wo / a->w) <= a->Wo,
-                "naf_xna_head_fwd: kernel_size * dilation exceeds the output extent (k=%dx%d, dilation=%dx%d, out=%dx%d)",
-                a->ky, a->kx, a->Ho / a->h, a->Wo / a->w, a->Ho, a->Wo);
     NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "naf_xna_head_fwd: path %d", a->path);
     NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_head_fwd: rope_tab_y and rope_tab_x must be given together");
     NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "naf_xna_head_fwd: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)",
@@ -374,10 +381,8 @@ static int xna_head_validate(const naf_xna_head_args* a, bool need_out = true) {
 
 int naf_xna_head_select(const naf_xna_head_args* a) {
     int rc = xna_head_validate(a);
-    if (rc != NAF_OK) return -rc;
-    rc = naf_xna_head_eligible(a);
-    if (rc != NAF_OK) return -rc;
-    return NAF_XNA_HEAD_FUSED;
+    if (rc == NAF_OK) rc = naf_xna_head_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
 }
 
 size_t naf_xna_head_workspace_bytes(const naf_xna_head_args* a) {
@@ -388,8 +393,7 @@ size_t naf_xna_head_workspace_bytes(const naf_xna_head_args* a) {
 int naf_xna_head_fwd(const naf_xna_head_args* a, naf_stream_t stream) {
     const int sel = naf_xna_head_select(a);
     if (sel < 0) return -sel;
-    const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
-    return naf_launch_xna_head(a, scale, static_cast<hipStream_t>(stream));
+    return naf_launch_xna_head(a, xna_scale(a->scale, a->Dq), static_cast<hipStream_t>(stream));
 }
 
 // ---- ... and a classification objective folded into its epilogue (cross-entropy, argmax, softmax - onehot) ----
@@ -414,17 +418,14 @@ static int xna_head_ce_validate(const naf_xna_head_ce_args* c, bool counts = fal
 
 int naf_xna_head_ce_select(const naf_xna_head_ce_args* a) {
     int rc = xna_head_ce_validate(a);
-    if (rc != NAF_OK) return -rc;
-    rc = naf_xna_head_ce_eligible(a);
-    if (rc != NAF_OK) return -rc;
-    return NAF_XNA_HEAD_FUSED;
+    if (rc == NAF_OK) rc = naf_xna_head_ce_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
 }
 
 int naf_xna_head_ce_fwd(const naf_xna_head_ce_args* a, naf_stream_t stream) {
     const int sel = naf_xna_head_ce_select(a);
     if (sel < 0) return -sel;
-    const float scale = a->head.scale > 0.f ? a->head.scale : 1.0f / sqrtf((float)a->head.Dq);
-    return naf_launch_xna_head_ce(a, scale, static_cast<hipStream_t>(stream));
+    return naf_launch_xna_head_ce(a, xna_scale(a->head.scale, a->head.Dq), static_cast<hipStream_t>(stream));
 }
 
 // ---- ... and a confusion matrix counted in that epilogue ----
@@ -442,30 +443,20 @@ static int xna_head_cm_validate(const naf_xna_head_cm_args* a) {
 
 int naf_xna_head_cm_select(const naf_xna_head_cm_args* a) {
     int rc = xna_head_cm_validate(a);
-    if (rc != NAF_OK) return -rc;
-    rc = naf_xna_head_ce_eligible(&a->ce);
-    if (rc != NAF_OK) return -rc;
-    return NAF_XNA_HEAD_FUSED;
+    if (rc == NAF_OK) rc = naf_xna_head_ce_eligible(&a->ce);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
 }
 
 int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream) {
     const int sel = naf_xna_head_cm_select(a);
     if (sel < 0) return -sel;
-    const float scale = a->ce.head.scale > 0.f ? a->ce.head.scale : 1.0f / sqrtf((float)a->ce.head.Dq);
-    return naf_launch_xna_head_cm(a, scale, static_cast<hipStream_t>(stream));
+    return naf_launch_xna_head_cm(a, xna_scale(a->ce.head.scale, a->ce.head.Dq), static_cast<hipStream_t>(stream));
 }
 
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_bwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->dout && a->dq && a->dk_lr && a->dv_lr, "naf_xna_bwd: NULL tensor pointer");
-    NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 && a->Dq > 0 && a->Dv > 0,
-                "naf_xna_bwd: non-positive size");
-    NAF_REQUIRE(a->ky > 0 && a->kx > 0 && (a->ky & 1) && (a->kx & 1), "naf_xna_bwd: kernel size must be odd, got %dx%d", a->ky, a->kx);
-    NAF_REQUIRE(a->Ho >= a->h && a->Wo >= a->w, "naf_xna_bwd: output %dx%d smaller than feature grid %dx%d (dilation 0)", a->Ho, a->Wo, a->h, a->w);
-    NAF_REQUIRE((int64_t)a->ky * (a->Ho / a->h) <= a->Ho && (int64_t)a->kx * (a->Wo / a->w) <= a->Wo,
-                "naf_xna_bwd: kernel_size * dilation exceeds the output extent (k=%dx%d, dilation=%dx%d, out=%dx%d)",
-                a->ky, a->kx, a->Ho / a->h, a->Wo / a->w, a->Ho, a->Wo);
-    return NAF_OK;
+    return xna_geometry_validate("naf_xna_bwd", a, a->Dv);
 }
 
 // Which kernel serves the request under a->path (0.4.1: the field that was `reserved`; 0 = NAF_XNA_AUTO as before): AUTO takes the cell
@@ -516,23 +507,29 @@ size_t naf_xna_bwd_workspace_bytes(const naf_xna_bwd_args* a) {
     return naf_xna_rows_bwd_workspace(a);
 }
 
-int naf_xna_bwd(const naf_xna_bwd_args* a, naf_stream_t stream) {
-    const int rc = xna_bwd_validate(a);
-    if (rc != NAF_OK) return rc;
-    const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
-    const int sel = xna_bwd_pick(a);
+// What naf_xna_bwd and naf_xna_bwd_scores do behind their validation: `who` is the entry's name in the messages, `sel` its pick, `sg` the
+// score gradient (NULL: none).
+static int xna_bwd_dispatch(const char* who, const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args* sg, int sel, naf_stream_t stream) {
     if (sel < 0) return -sel;
-    if (sel == NAF_XNA_MFMA) return naf_launch_xna_bwd(a, scale, static_cast<hipStream_t>(stream));
+    const float scale = xna_scale(a->scale, a->Dq);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    if (sel == NAF_XNA_MFMA) return naf_launch_xna_bwd(a, scale, s, sg);
     // the denoising call's shapes: matrix cores when the caller brought the tables and the statistics workspace
     // a workspace pointer that is not 16-byte aligned cannot be one this library asked for (a host built against a 0.1.0 header
     // leaves stack garbage in the field): refuse it instead of writing the per-query statistics through it
-    NAF_REQUIRE(a->workspace == nullptr || al16(a->workspace), "naf_xna_bwd: workspace must be 16-byte aligned");
+    NAF_REQUIRE(a->workspace == nullptr || al16(a->workspace), "%s: workspace must be 16-byte aligned", who);
     if (sel == NAF_XNA_ROWS) {
         if (a->idx_y && a->idx_x && a->workspace && (size_t)a->workspace_bytes >= naf_xna_rows_bwd_workspace(a))
-            return naf_launch_xna_rows_bwd(a, scale, static_cast<hipStream_t>(stream));
-        NAF_REQUIRE(a->path == NAF_XNA_AUTO, "naf_xna_bwd: path NAF_XNA_ROWS needs idx_y / idx_x and a workspace of naf_xna_bwd_workspace_bytes()");
+            return naf_launch_xna_rows_bwd(a, scale, s, sg);
+        NAF_REQUIRE(a->path == NAF_XNA_AUTO, "%s: path NAF_XNA_ROWS needs idx_y / idx_x and a workspace of naf_xna_bwd_workspace_bytes()", who);
     }
-    return naf_launch_xna_generic_bwd(a, scale, static_cast<hipStream_t>(stream));
+    return naf_launch_xna_generic_bwd(a, scale, s, sg);
+}
+
+int naf_xna_bwd(const naf_xna_bwd_args* a, naf_stream_t stream) {
+    const int rc = xna_bwd_validate(a);
+    if (rc != NAF_OK) return rc;
+    return xna_bwd_dispatch("naf_xna_bwd", a, nullptr, xna_bwd_pick(a), stream);
 }
 
 // ---- 0.4.3: the backward with a gradient of the scores ------------------------------------------------------
@@ -585,18 +582,7 @@ int naf_xna_bwd_scores(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args*
     if (!scores_given(s)) return naf_xna_bwd(a, stream);
     const int rc = xna_bwd_scores_validate(a, s);
     if (rc != NAF_OK) return rc;
-    const float scale = a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq);
-    const int sel = xna_bwd_scores_pick(a, s);
-    if (sel < 0) return -sel;
-    const hipStream_t st = static_cast<hipStream_t>(stream);
-    if (sel == NAF_XNA_MFMA) return naf_launch_xna_bwd(a, scale, st, s);
-    NAF_REQUIRE(a->workspace == nullptr || al16(a->workspace), "naf_xna_bwd_scores: workspace must be 16-byte aligned");
-    if (sel == NAF_XNA_ROWS) {
-        if (a->idx_y && a->idx_x && a->workspace && (size_t)a->workspace_bytes >= naf_xna_rows_bwd_workspace(a))
-            return naf_launch_xna_rows_bwd(a, scale, st, s);
-        NAF_REQUIRE(a->path == NAF_XNA_AUTO, "naf_xna_bwd_scores: path NAF_XNA_ROWS needs idx_y / idx_x and a workspace of naf_xna_bwd_workspace_bytes()");
-    }
-    return naf_launch_xna_generic_bwd(a, scale, st, s);
+    return xna_bwd_dispatch("naf_xna_bwd_scores", a, s, xna_bwd_scores_pick(a, s), stream);
 }
 
 // ---- whole forward in one call ---------------------------------------------------------------------------
@@ -1118,8 +1104,7 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
         const int sel = naf_xna_select(&x);
         if (sel < 0) return -sel;
         if (sel == NAF_XNA_MFMA) {
-            const float scale = x.scale > 0.f ? x.scale : 1.0f / sqrtf((float)x.Dq);
-            rc = naf_launch_xna_mfma(&x, scale, s, reinterpret_cast<uint32_t*>(ws + L.steal));
+            rc = naf_launch_xna_mfma(&x, xna_scale(x.scale, x.Dq), s, reinterpret_cast<uint32_t*>(ws + L.steal));
         } else {
             rc = naf_xna_fwd(&x, stream);
         }

@@ -1,15 +1,8 @@
 // Eligibility test + dispatcher for the head-summed MFMA cell kernel (see xna_head_kernel.h).
 #include "xna_head_kernel.h"
 
-#define NAF_DECL(K) int naf_xna_head_launch_k##K(const XnaHeadParams& p, int out_dtype, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-#define NAF_DECL(K) int naf_xna_head_ce_launch_k##K(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-#define NAF_DECL(K) int naf_xna_head_cm_launch_k##K(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
+NAF_XNA_HEAD_WINDOW(extern, 3) NAF_XNA_HEAD_WINDOW(extern, 5) NAF_XNA_HEAD_WINDOW(extern, 7) NAF_XNA_HEAD_WINDOW(extern, 9)
+NAF_XNA_HEAD_WINDOW(extern, 11) NAF_XNA_HEAD_WINDOW(extern, 13) NAF_XNA_HEAD_WINDOW(extern, 15)
 
 static bool head_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
 
@@ -70,7 +63,8 @@ int naf_xna_head_ce_eligible(const naf_xna_head_ce_args* c) {
     return NAF_OK;
 }
 
-static int head_fill_params(const naf_xna_head_args* a, float scale, const char* who, XnaHeadParams& p) {
+// `tag` names the variant in the messages: the C entry point is naf_<tag>_fwd.
+static int head_fill_params(const naf_xna_head_args* a, float scale, const char* tag, XnaHeadParams& p) {
     p.q = static_cast<const bf16_t*>(a->q);
     p.k = static_cast<const bf16_t*>(a->k_lr);
     p.pv = static_cast<const bf16_t*>(a->pv_lr);
@@ -83,7 +77,7 @@ static int head_fill_params(const naf_xna_head_args* a, float scale, const char*
     p.npad = (a->N + 15) & ~15;
     const int64_t nb = (int64_t)a->B * a->h * a->w;
     if (nb <= 0 || nb > 0x7fffffffLL) {
-        naf_set_error("%s: grid of %lld workgroups out of range", who, (long long)nb);
+        naf_set_error("naf_%s_fwd: grid of %lld workgroups out of range", tag, (long long)nb);
         return NAF_ERR_INVALID;
     }
     p.nblocks = (uint32_t)nb;
@@ -95,20 +89,18 @@ static int head_fill_params(const naf_xna_head_args* a, float scale, const char*
     return NAF_OK;
 }
 
-int naf_launch_xna_head(const naf_xna_head_args* a, float scale, hipStream_t s) {
+// Fills the parameters and dispatches on the window; `what` names the launch in a launch error, `x` is the variant's extra kernel argument.
+template <typename... Extra>
+static int head_launch(const naf_xna_head_args* a, float scale, hipStream_t s, const char* tag, const char* what, const Extra&... x) {
     XnaHeadParams p;
-    const int rc = head_fill_params(a, scale, "naf_xna_head_fwd", p);
+    const int rc = head_fill_params(a, scale, tag, p);
     if (rc != NAF_OK) return rc;
     switch (a->ky) {
-        case 3: return naf_xna_head_launch_k3(p, a->out_dtype, s);
-        case 5: return naf_xna_head_launch_k5(p, a->out_dtype, s);
-        case 7: return naf_xna_head_launch_k7(p, a->out_dtype, s);
-        case 9: return naf_xna_head_launch_k9(p, a->out_dtype, s);
-        case 11: return naf_xna_head_launch_k11(p, a->out_dtype, s);
-        case 13: return naf_xna_head_launch_k13(p, a->out_dtype, s);
-        case 15: return naf_xna_head_launch_k15(p, a->out_dtype, s);
+#define NAF_CASE(K) case K: return xna_head_launch_ks<K>(p, a->out_dtype, s, tag, what, x...);
+        NAF_CASE(3) NAF_CASE(5) NAF_CASE(7) NAF_CASE(9) NAF_CASE(11) NAF_CASE(13) NAF_CASE(15)
+#undef NAF_CASE
     }
-    naf_set_error("naf_xna_head_fwd: kernel size %d has no instantiation", a->ky);
+    naf_set_error("naf_%s_fwd: kernel size %d has no instantiation", tag, a->ky);
     return NAF_ERR_UNSUPPORTED;
 }
 
@@ -124,43 +116,18 @@ static void head_fill_ce(const naf_xna_head_ce_args* c, XnaHeadCEExtra& x) {
     }
 }
 
+int naf_launch_xna_head(const naf_xna_head_args* a, float scale, hipStream_t s) { return head_launch(a, scale, s, "xna_head", "xna_head_kernel"); }
+
 int naf_launch_xna_head_ce(const naf_xna_head_ce_args* c, float scale, hipStream_t s) {
-    XnaHeadParams p;
-    const int rc = head_fill_params(&c->head, scale, "naf_xna_head_ce_fwd", p);
-    if (rc != NAF_OK) return rc;
     XnaHeadCEExtra x;
     head_fill_ce(c, x);
-    switch (c->head.ky) {
-        case 3: return naf_xna_head_ce_launch_k3(p, x, s);
-        case 5: return naf_xna_head_ce_launch_k5(p, x, s);
-        case 7: return naf_xna_head_ce_launch_k7(p, x, s);
-        case 9: return naf_xna_head_ce_launch_k9(p, x, s);
-        case 11: return naf_xna_head_ce_launch_k11(p, x, s);
-        case 13: return naf_xna_head_ce_launch_k13(p, x, s);
-        case 15: return naf_xna_head_ce_launch_k15(p, x, s);
-    }
-    naf_set_error("naf_xna_head_ce_fwd: kernel size %d has no instantiation", c->head.ky);
-    return NAF_ERR_UNSUPPORTED;
+    return head_launch(&c->head, scale, s, "xna_head_ce", "xna_head_kernel (classification epilogue)", x);
 }
 
 int naf_launch_xna_head_cm(const naf_xna_head_cm_args* m, float scale, hipStream_t s) {
-    const naf_xna_head_ce_args* c = &m->ce;
-    XnaHeadParams p;
-    const int rc = head_fill_params(&c->head, scale, "naf_xna_head_cm_fwd", p);
-    if (rc != NAF_OK) return rc;
     XnaHeadCMExtra x;
-    head_fill_ce(c, x.ce);
+    head_fill_ce(&m->ce, x.ce);
     x.confusion = reinterpret_cast<unsigned long long*>(m->confusion);   // counts are non-negative: the 64-bit add is the same for both
     x.cm_stride = m->cm_stride;
-    switch (c->head.ky) {
-        case 3: return naf_xna_head_cm_launch_k3(p, x, s);
-        case 5: return naf_xna_head_cm_launch_k5(p, x, s);
-        case 7: return naf_xna_head_cm_launch_k7(p, x, s);
-        case 9: return naf_xna_head_cm_launch_k9(p, x, s);
-        case 11: return naf_xna_head_cm_launch_k11(p, x, s);
-        case 13: return naf_xna_head_cm_launch_k13(p, x, s);
-        case 15: return naf_xna_head_cm_launch_k15(p, x, s);
-    }
-    naf_set_error("naf_xna_head_cm_fwd: kernel size %d has no instantiation", c->head.ky);
-    return NAF_ERR_UNSUPPORTED;
+    return head_launch(&m->ce.head, scale, s, "xna_head_cm", "xna_head_kernel (confusion matrix)", x);
 }

@@ -1,14 +1,4 @@
 // Head-summed MFMA cell kernel, 3x3 window (one translation unit per window: parallel compilation).
 #include "xna_head_kernel.h"
 
-int naf_xna_head_launch_k3(const XnaHeadParams& p, int out_dtype, hipStream_t s) {
-    return xna_head_launch_ks<3>(p, out_dtype, s);
-}
-
-int naf_xna_head_ce_launch_k3(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s) {
-    return xna_head_ce_launch_ks<3>(p, x, s);
-}
-
-int naf_xna_head_cm_launch_k3(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s) {
-    return xna_head_cm_launch_ks<3>(p, x, s);
-}
+NAF_XNA_HEAD_WINDOW(, 3)

@@ -463,11 +463,13 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
     }
 }
 
-template <int KS, int NCT, typename OutT>
-static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s) {
+// One launcher for the three variants: no Extra = logits, XnaHeadCEExtra = classification epilogue, XnaHeadCMExtra = ... with a
+// confusion matrix.  The optional outputs of an epilogue are run-time NULL checks inside the kernel.
+template <int KS, int NCT, typename OutT, typename... Extra>
+static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s, const char* what, const Extra&... extra) {
     constexpr size_t lds = xna_head_lds_for(KS, NCT);
     static_assert(lds <= 160 * 1024, "LDS budget");
-    auto kern = xna_head_kernel<KS, NCT, OutT>;
+    auto kern = xna_head_kernel<KS, NCT, OutT, sizeof...(Extra) != 0, Extra...>;
     if (lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
@@ -475,77 +477,32 @@ static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s) {
             return NAF_ERR_LAUNCH;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p);
-    return naf_check_launch("xna_head_kernel");
+    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, extra...);
+    return naf_check_launch(what);
 }
 
-template <int KS>
-static int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s) {
+// The window's entry point, one explicit instantiation per variant in xna_head_k<KS>.hip.  `who` names the variant in the messages
+// ("xna_head", "xna_head_ce", "xna_head_cm"); the logits variant stores bf16 or float, the epilogues float only.
+template <int KS, typename... Extra>
+int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s, const char* who, const char* what, const Extra&... extra) {
     const int nct = xna_head_nct(p.npad);
-#define NAF_HEAD_CASE(C)                                                            \
-    if (nct == C) {                                                                 \
-        if (out_dtype == NAF_BF16) return xna_head_launch_one<KS, C, bf16_t>(p, s); \
-        return xna_head_launch_one<KS, C, float>(p, s);                             \
+#define NAF_HEAD_CASE(C)                                                                                               \
+    if (nct == C) {                                                                                                    \
+        if constexpr (sizeof...(Extra) == 0)                                                                           \
+            if (out_dtype == NAF_BF16) return xna_head_launch_one<KS, C, bf16_t>(p, s, what);                          \
+        return xna_head_launch_one<KS, C, float>(p, s, what, extra...);                                                \
     }
     NAF_HEAD_CASE(2)
     NAF_HEAD_CASE(4)
     NAF_HEAD_CASE(10)
     NAF_HEAD_CASE(16)
 #undef NAF_HEAD_CASE
-    naf_set_error("xna_head: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
+    naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", who, KS, nct);
     return NAF_ERR_UNSUPPORTED;
 }
 
-// ---- classification epilogue: one more instantiation per (window, channel-tile count); the optional outputs are run-time NULL checks ----
-template <int KS, int NCT>
-static int xna_head_ce_launch_one(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s) {
-    constexpr size_t lds = xna_head_lds_for(KS, NCT);
-    auto kern = xna_head_kernel<KS, NCT, float, true, XnaHeadCEExtra>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
-            return NAF_ERR_LAUNCH;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, x);
-    return naf_check_launch("xna_head_kernel (classification epilogue)");
-}
-
-template <int KS>
-static int xna_head_ce_launch_ks(const XnaHeadParams& p, const XnaHeadCEExtra& x, hipStream_t s) {
-    const int nct = xna_head_nct(p.npad);
-    if (nct == 2) return xna_head_ce_launch_one<KS, 2>(p, x, s);
-    if (nct == 4) return xna_head_ce_launch_one<KS, 4>(p, x, s);
-    if (nct == 10) return xna_head_ce_launch_one<KS, 10>(p, x, s);
-    if (nct == 16) return xna_head_ce_launch_one<KS, 16>(p, x, s);
-    naf_set_error("xna_head_ce: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
-    return NAF_ERR_UNSUPPORTED;
-}
-
-// ---- ... with a confusion matrix: one more instantiation per (window, channel-tile count), selected only by naf_xna_head_cm_fwd ----
-template <int KS, int NCT>
-static int xna_head_cm_launch_one(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s) {
-    constexpr size_t lds = xna_head_lds_for(KS, NCT);
-    auto kern = xna_head_kernel<KS, NCT, float, true, XnaHeadCMExtra>;
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
-            return NAF_ERR_LAUNCH;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, x);
-    return naf_check_launch("xna_head_kernel (confusion matrix)");
-}
-
-template <int KS>
-static int xna_head_cm_launch_ks(const XnaHeadParams& p, const XnaHeadCMExtra& x, hipStream_t s) {
-    const int nct = xna_head_nct(p.npad);
-    if (nct == 2) return xna_head_cm_launch_one<KS, 2>(p, x, s);
-    if (nct == 4) return xna_head_cm_launch_one<KS, 4>(p, x, s);
-    if (nct == 10) return xna_head_cm_launch_one<KS, 10>(p, x, s);
-    if (nct == 16) return xna_head_cm_launch_one<KS, 16>(p, x, s);
-    naf_set_error("xna_head_cm: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
-    return NAF_ERR_UNSUPPORTED;
-}
+// xna_head_k<KS>.hip defines these three, xna_head.hip declares them (extern) and dispatches on the window.
+#define NAF_XNA_HEAD_WINDOW(LINKAGE, KS)                                                                                                        \
+    LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*);                              \
+    LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadCEExtra&);       \
+    LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadCMExtra&);

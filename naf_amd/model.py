@@ -804,15 +804,18 @@ class NAF(nn.Module):
             x = x.float()
         if x.shape[-2:] != (ho, wo):
             x = F.adaptive_avg_pool2d(x, output_size=(ho, wo))                 # naf.py:34
-        if amp == "hip" and heads_rope == heads and (x.shape[1] // heads_rope) % 32 == 0:
-            # RoPE, key pooling and their backward as HIP kernels too (naf_rope_pool_fwd / naf_rope_pool_bwd): the guidance stays
-            # bf16 channels-last from the stem's last layer to the attention kernel, and so does its gradient on the way back
+
+        def rope_tabs():    # [Ho, 2, P], [Wo, 2, P]; in training mode with the reference's coordinate augmentation (rope.py:107-124)
             if enc.rope.training and enc.rope.cache_train_coords:
                 if (ho, wo) not in enc.rope._train_tables:
                     enc.rope._train_tables[(ho, wo)] = _rope_train_tables(enc.rope, ho, wo)
-                tab_y, tab_x = enc.rope._train_tables[(ho, wo)]
-            else:
-                tab_y, tab_x = _rope_train_tables(enc.rope, ho, wo) if enc.rope.training else enc.rope.tables(ho, wo)
+                return enc.rope._train_tables[(ho, wo)]
+            return _rope_train_tables(enc.rope, ho, wo) if enc.rope.training else enc.rope.tables(ho, wo)
+
+        if amp == "hip" and heads_rope == heads and (x.shape[1] // heads_rope) % 32 == 0:
+            # RoPE, key pooling and their backward as HIP kernels too (naf_rope_pool_fwd / naf_rope_pool_bwd): the guidance stays
+            # bf16 channels-last from the stem's last layer to the attention kernel, and so does its gradient on the way back
+            tab_y, tab_x = rope_tabs()
             xcl = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
             q5, k5 = ops.RopePoolFunction.apply(xcl, tab_y.contiguous(), tab_x.contiguous(), heads_rope, (h, w))
             B, C = features.shape[:2]
@@ -825,13 +828,7 @@ class NAF(nn.Module):
             out = out5.permute(0, 2, 3, 1, 4).reshape(B, ho, wo, C).permute(0, 3, 1, 2)
             return (out, logits) if return_weights else out
         # RoPE (rope.py:15-34,139-153) from the cached tables: angle index t < D/4 -> row, else column
-        # [Ho, 2, P], [Wo, 2, P]; in training mode with the reference's coordinate augmentation (rope.py:107-124)
-        if enc.rope.training and enc.rope.cache_train_coords:
-            if (ho, wo) not in enc.rope._train_tables:
-                enc.rope._train_tables[(ho, wo)] = _rope_train_tables(enc.rope, ho, wo)
-            tab_y, tab_x = enc.rope._train_tables[(ho, wo)]
-        else:
-            tab_y, tab_x = _rope_train_tables(enc.rope, ho, wo) if enc.rope.training else enc.rope.tables(ho, wo)
+        tab_y, tab_x = rope_tabs()
         B, Cq = x.shape[:2]
         D = Cq // heads_rope
         cos = torch.cat([tab_y[:, 0, None, :].expand(ho, wo, -1), tab_x[None, :, 0, :].expand(ho, wo, -1)], dim=-1)
@@ -925,17 +922,44 @@ class NAF(nn.Module):
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)
 
-    def _forward_head(self, image, features, output_size, return_weights, head):
-        """``forward(..., head=head)``: see ``forward``."""
+    def _head_call(self, image, features, output_size, return_weights, head, reduction="mean", target=None, confusion=None):
+        """Host-side validation the three ``head=`` entries share, in the order they raise (nothing has touched the device yet):
+        -> (weight, bias, (ho, wo), target as int64).  ``target`` / ``confusion``: checked where the entry has one; the logits entry has no ``reduction``, the default passes."""
         if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
             raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
-        weight, bias = _linear_head(head, features.shape[1])      # host-side validation first: nothing has touched the device yet
+        weight, bias = _linear_head(head, features.shape[1])
         if return_weights:
             raise ValueError("naf(..., head=...) does not return attention scores: call naf(image, features, size, return_weights=True) for them")
+        if reduction not in ops._REDUCTIONS:
+            raise ValueError(f"reduction must be one of {ops._REDUCTIONS}, got {reduction!r}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        if target is not None:
+            target = ops._check_target(target, (image.shape[0], ho, wo), features.device, "naf(..., target=...)")
+        if confusion is not None and confusion is not True:
+            if not isinstance(confusion, torch.Tensor):
+                raise TypeError(f"confusion must be True or an int64 [N, N] tensor, got {type(confusion).__name__}")
+            ops._check_confusion(confusion, weight.shape[0], features.device, "naf(..., confusion=...)")
         if not (image.is_cuda and features.is_cuda and weight.is_cuda):
             raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
                                f"image on {image.device}, features on {features.device}, head on {weight.device}")
-        ho, wo = int(output_size[0]), int(output_size[1])
+        return weight, bias, (ho, wo), target
+
+    def _head_operands(self, image, features, weight, bias, out_size, head_grad, out_dtype=torch.float32):
+        """The attention's operands of a ``head=`` call: (q5, k5, rope tables or None, pv5, fp32 bias or None).  ``head_grad``: the call
+        records a graph for the head, so the queries are materialised -- rotate-on-load only without a graph: the backward kernels read
+        rotated queries.  Otherwise the geometry decides (``out_dtype``: the logits'), not the outputs asked for."""
+        heads = self.upsampler.num_heads
+        if features.shape[1] % heads:
+            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
+        ksz, lr, N = self.upsampler.kernel_size, features.shape[-2:], weight.shape[0]
+        with torch.no_grad():
+            fusable = None if head_grad else (lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, out_dtype=out_dtype, rope_tables=tabs) == "fused")
+            q5, k5, tabs = self.guidance_qk(image, lr, out_size, fusable=fusable)
+        return (q5, k5, tabs) + ops.project_head_values(weight, bias, features, heads)
+
+    def _forward_head(self, image, features, output_size, return_weights, head):
+        """``forward(..., head=head)``: see ``forward``."""
+        weight, bias, (ho, wo), _ = self._head_call(image, features, output_size, return_weights, head)
         N = weight.shape[0]
         if image.shape[0] == 0:
             return torch.empty((0, ho, wo, N), dtype=weight.dtype, device=features.device).permute(0, 3, 1, 2)
@@ -943,16 +967,9 @@ class NAF(nn.Module):
         if grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
             # a gradient for the upsampler or its inputs: today's differentiable forward, then the head (unfused)
             return _apply_head(head, self.forward_train(image, features, output_size, amp="auto"))
-        heads = self.upsampler.num_heads
-        if features.shape[1] % heads:
-            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
         head_grad = grad and (weight.requires_grad or (bias is not None and bias.requires_grad))
-        ksz, lr = self.upsampler.kernel_size, features.shape[-2:]
-        with torch.no_grad():
-            # rotate-on-load only without a graph: the backward kernels read materialised (rotated) queries
-            fusable = None if head_grad else (lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, out_dtype=weight.dtype, rope_tables=tabs) == "fused")
-            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
-        pv5, b32 = ops.project_head_values(weight, bias, features, heads)
+        q5, k5, tabs, pv5, b32 = self._head_operands(image, features, weight, bias, (ho, wo), head_grad, weight.dtype)
+        ksz = self.upsampler.kernel_size
         with ops._Timed("attention"):
             if head_grad:
                 return ops.XnaHeadFunction.apply(q5, k5, pv5, b32, ksz, N, weight.dtype, "auto", self.upsampler.scale)
@@ -961,21 +978,9 @@ class NAF(nn.Module):
 
     def _forward_head_objective(self, image, features, output_size, return_weights, head, target, ignore_index, reduction, predict):
         """``forward(..., head=head, target=... / predict=True)``: see ``forward``."""
-        if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
-            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
-        weight, bias = _linear_head(head, features.shape[1])      # host-side validation first: nothing has touched the device yet
-        if return_weights:
-            raise ValueError("naf(..., head=...) does not return attention scores: call naf(image, features, size, return_weights=True) for them")
-        if reduction not in ops._REDUCTIONS:
-            raise ValueError(f"reduction must be one of {ops._REDUCTIONS}, got {reduction!r}")
-        ho, wo = int(output_size[0]), int(output_size[1])
+        weight, bias, (ho, wo), target = self._head_call(image, features, output_size, return_weights, head, reduction, target)
         B, N = image.shape[0], weight.shape[0]
         ignore_index = int(ignore_index)
-        if target is not None:
-            target = ops._check_target(target, (B, ho, wo), features.device, "naf(..., target=...)")
-        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
-                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
         pack = lambda loss, labels: (loss, labels) if (target is not None and predict) else (loss if target is not None else labels)
         grad = torch.is_grad_enabled()
         if B == 0 or (grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters())))):
@@ -986,16 +991,9 @@ class NAF(nn.Module):
             if target is not None:      # torch's own cross-entropy, with this call's contract for targets outside the classes
                 loss = F.cross_entropy(logits, ops.head_sanitized_target(target, ignore_index, N), ignore_index=ignore_index, reduction=reduction)
             return pack(loss, logits.detach().argmax(1) if predict else None)
-        heads = self.upsampler.num_heads
-        if features.shape[1] % heads:
-            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
         head_grad = grad and target is not None and (weight.requires_grad or (bias is not None and bias.requires_grad))
-        ksz, lr = self.upsampler.kernel_size, features.shape[-2:]
-        with torch.no_grad():
-            # rotate-on-load only without a graph, as for the logits (the geometry decides, not the outputs asked for)
-            fusable = None if head_grad else (lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, rope_tables=tabs) == "fused")
-            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
-        pv5, b32 = ops.project_head_values(weight, bias, features, heads)
+        q5, k5, tabs, pv5, b32 = self._head_operands(image, features, weight, bias, (ho, wo), head_grad)
+        ksz = self.upsampler.kernel_size
         with ops._Timed("attention"):
             if head_grad:
                 res = ops.XnaHeadCEFunction.apply(q5, k5, pv5, b32, target, ksz, N, ignore_index, reduction, predict, "auto", self.upsampler.scale)
@@ -1010,37 +1008,17 @@ class NAF(nn.Module):
 
     def _forward_head_confusion(self, image, features, output_size, return_weights, head, target, ignore_index, reduction, predict, confusion):
         """``forward(..., head=head, target=..., confusion=True / matrix)``: see ``forward``."""
-        if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
-            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
-        weight, bias = _linear_head(head, features.shape[1])      # host-side validation first: nothing has touched the device yet
-        if return_weights:
-            raise ValueError("naf(..., head=...) does not return attention scores: call naf(image, features, size, return_weights=True) for them")
-        if reduction not in ops._REDUCTIONS:
-            raise ValueError(f"reduction must be one of {ops._REDUCTIONS}, got {reduction!r}")
-        ho, wo = int(output_size[0]), int(output_size[1])
-        B, N = image.shape[0], weight.shape[0]
-        ignore_index = int(ignore_index)
-        target = ops._check_target(target, (B, ho, wo), features.device, "naf(..., target=...)")
-        if confusion is not True:
-            if not isinstance(confusion, torch.Tensor):
-                raise TypeError(f"confusion must be True or an int64 [N, N] tensor, got {type(confusion).__name__}")
-            ops._check_confusion(confusion, N, features.device, "naf(..., confusion=...)")
-        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
-                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
-        heads = self.upsampler.num_heads
-        if features.shape[1] % heads:
-            raise ValueError(f"feature channels {features.shape[1]} not divisible by {heads} heads")
+        weight, bias, (ho, wo), target = self._head_call(image, features, output_size, return_weights, head, reduction, target, confusion)
+        N = weight.shape[0]
+        if features.shape[1] % self.upsampler.num_heads:      # this entry refuses it for an empty batch too
+            raise ValueError(f"feature channels {features.shape[1]} not divisible by {self.upsampler.num_heads} heads")
         with torch.no_grad():
             cm = torch.zeros((N, N), dtype=torch.int64, device=features.device) if confusion is True else confusion
-            if B == 0:
+            if image.shape[0] == 0:
                 return (cm, torch.empty((0, ho, wo), dtype=torch.int64, device=features.device)) if predict else cm
-            ksz, lr = self.upsampler.kernel_size, features.shape[-2:]
-            fusable = lambda q5, tabs: ops.xna_head_select(q5, lr, N, ksz, rope_tables=tabs) == "fused"
-            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
-            pv5, b32 = ops.project_head_values(weight, bias, features, heads)
+            q5, k5, tabs, pv5, b32 = self._head_operands(image, features, weight, bias, (ho, wo), False)
             with ops._Timed("attention"):
-                _, labels, _, _ = ops.xna_head_objective(q5, k5, pv5, b32, ksz, n_out=N, target=target, ignore_index=ignore_index,
+                _, labels, _, _ = ops.xna_head_objective(q5, k5, pv5, b32, self.upsampler.kernel_size, n_out=N, target=target, ignore_index=int(ignore_index),
                                                          want_labels=predict, scale=self.upsampler.scale, rope_tables=tabs, confusion=cm)
             return (cm, labels.long()) if predict else cm
 

@@ -61,6 +61,15 @@ def _strides4(t: torch.Tensor, dims) -> I64x4:
     return I64x4(*[int(t.stride(d)) for d in dims])
 
 
+def _strides3(t: torch.Tensor) -> I64x3:
+    return I64x3(int(t.stride(0)), int(t.stride(1)), int(t.stride(2)))
+
+
+def _ksize(kernel_size):
+    """(ky, kx) of an int or a pair."""
+    return (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+
+
 # ------------------------------------------------------------------------------------------------
 def axis_index_table(L_out: int, L_in: int, k: int) -> torch.Tensor:
     """[L_out, k] int32 CPU tensor of low-res indices (host function of the library, no GPU needed)."""
@@ -157,7 +166,7 @@ def _fill_stem_conv0(image, weight, bias, y, stats_out) -> StemConv0Args:
     a.stats_out = _stats_ptr(stats_out, B, "stem_conv0")
     a.image_dtype, a.ksize, a.B, a.H, a.W = _DT[image.dtype], int(weight.shape[-1]), B, H, W
     a.image_stride = _strides4(image, (0, 1, 2, 3))
-    a.y_stride = I64x3(int(y.stride(0)), int(y.stride(1)), int(y.stride(2))) if y is not None else I64x3(0, 0, 0)
+    a.y_stride = _strides3(y) if y is not None else I64x3(0, 0, 0)
     return a
 
 
@@ -211,8 +220,8 @@ def stem_conv(x: Optional[torch.Tensor], stats_in: torch.Tensor, gn_weight: torc
     a.ksize = {1: 1, 9: 3}[int(taps)]
     a.channels = Cc
     a.B, a.H, a.W, a.eps = B, H, W, float(eps)
-    a.x_stride = I64x3(int(x.stride(0)), int(x.stride(1)), int(x.stride(2)))
-    a.y_stride = I64x3(int(y.stride(0)), int(y.stride(1)), int(y.stride(2)))
+    a.x_stride = _strides3(x)
+    a.y_stride = _strides3(y)
     if keys is not None:
         kp = _fill_key_pool(keys, x)
         with torch.cuda.device(x.device), _Timed("stem_conv%d_keys" % a.ksize):
@@ -234,7 +243,7 @@ def _fill_key_pool(keys, x) -> KeyPoolArgs:
     kp = KeyPoolArgs()
     kp.k_lr, kp.tab_y, kp.tab_x = k_slice.data_ptr(), tab_y.data_ptr(), tab_x.data_ptr()
     kp.h, kp.w = int(k_slice.shape[1]), int(k_slice.shape[2])
-    kp.k_stride = I64x3(int(k_slice.stride(0)), int(k_slice.stride(1)), int(k_slice.stride(2)))
+    kp.k_stride = _strides3(k_slice)
     return kp
 
 
@@ -255,8 +264,8 @@ def stem_conv_plain(x: torch.Tensor, w_packed: torch.Tensor, y: torch.Tensor, bi
     a.ksize = {1: 1, 9: 3}[int(w_packed.shape[0])]
     a.channels = Cc
     a.B, a.H, a.W, a.eps = B, H, W, 0.0
-    a.x_stride = I64x3(int(x.stride(0)), int(x.stride(1)), int(x.stride(2)))
-    a.y_stride = I64x3(int(y.stride(0)), int(y.stride(1)), int(y.stride(2)))
+    a.x_stride = _strides3(x)
+    a.y_stride = _strides3(y)
     with torch.cuda.device(x.device), _Timed("stem_dgrad%d" % a.ksize):
         rc = lib.naf_stem_conv_fwd(C.byref(a), _stream(x))
     _lib.check(rc, "naf_stem_conv_fwd")
@@ -272,8 +281,8 @@ def stem_act(x: torch.Tensor, stats_in: torch.Tensor, gn_weight: torch.Tensor, g
     a = _lib.StemActArgs()
     a.x, a.a, a.gn_weight, a.gn_bias, a.stats_in = x.data_ptr(), out.data_ptr(), gn_weight.data_ptr(), gn_bias.data_ptr(), _stats_ptr(stats_in, B, "stem_act")
     a.B, a.H, a.W, a.channels, a.pad, a.eps = B, H, W, Cc, int(pad), float(eps)
-    a.x_stride = I64x3(int(x.stride(0)), int(x.stride(1)), int(x.stride(2)))
-    a.a_stride = I64x3(int(out.stride(0)), int(out.stride(1)), int(out.stride(2)))
+    a.x_stride = _strides3(x)
+    a.a_stride = _strides3(out)
     with torch.cuda.device(x.device), _Timed("stem_act"):
         rc = lib.naf_stem_act_fwd(C.byref(a), _stream(x))
     _lib.check(rc, "naf_stem_act_fwd")
@@ -310,8 +319,8 @@ def stem_wgrad(dy: torch.Tensor, x: torch.Tensor, stats_in: Optional[torch.Tenso
     else:
         a.gn_weight = a.gn_bias = a.stats_in = None
     a.ksize, a.B, a.H, a.W, a.eps, a.channels = int(ksize), B, H, W, float(eps), Cc
-    a.dy_stride = I64x3(int(dy.stride(0)), int(dy.stride(1)), int(dy.stride(2)))
-    a.x_stride = I64x3(int(x.stride(0)), int(x.stride(1)), int(x.stride(2)))
+    a.dy_stride = _strides3(dy)
+    a.x_stride = _strides3(x)
     with torch.cuda.device(x.device), _Timed("stem_wgrad%d" % ksize):
         rc = lib.naf_stem_wgrad(C.byref(a), _stream(x))
     _lib.check(rc, "naf_stem_wgrad")
@@ -337,7 +346,7 @@ def stem_conv0_wgrad(dy: torch.Tensor, image: torch.Tensor, ksize: int, out: Opt
     a = _lib.StemConv0WgradArgs()
     a.dy, a.image, a.dw, a.db = dy.data_ptr(), image.data_ptr(), buf.data_ptr(), buf[nt * Cc:].data_ptr()
     a.image_dtype, a.ksize, a.B, a.H, a.W, a.channels = _DT[image.dtype], int(ksize), B, H, W, Cc
-    a.dy_stride = I64x3(int(dy.stride(0)), int(dy.stride(1)), int(dy.stride(2)))
+    a.dy_stride = _strides3(dy)
     a.image_stride = _strides4(image, (0, 1, 2, 3))
     with torch.cuda.device(dy.device), _Timed("stem_conv0_wgrad"):
         rc = lib.naf_stem_conv0_wgrad(C.byref(a), _stream(dy))
@@ -358,7 +367,7 @@ def stem_conv0_dgrad(dy: torch.Tensor, weight: torch.Tensor, dimage: torch.Tenso
     a = _lib.StemConv0DgradArgs()
     a.dy, a.weight, a.dimage = dy.data_ptr(), weight.data_ptr(), dimage.data_ptr()
     a.ksize, a.B, a.H, a.W, a.channels, a.accumulate = k, B, H, W, Cc, int(bool(accumulate))
-    a.dy_stride = I64x3(int(dy.stride(0)), int(dy.stride(1)), int(dy.stride(2)))
+    a.dy_stride = _strides3(dy)
     a.dimage_stride = _strides4(dimage, (0, 1, 2, 3))
     with torch.cuda.device(dy.device), _Timed("stem_conv0_dgrad"):
         rc = lib.naf_stem_conv0_dgrad(C.byref(a), _stream(dy))
@@ -385,9 +394,9 @@ def stem_act_bwd(da: torch.Tensor, x: torch.Tensor, stats_in: torch.Tensor, gn_w
     a.da, a.x, a.dx = da.data_ptr(), x.data_ptr(), dx.data_ptr()
     a.gn_weight, a.gn_bias, a.stats_in, a.sums = gn_weight.data_ptr(), gn_bias.data_ptr(), _stats_ptr(stats_in, B, "stem_act_bwd"), sums.data_ptr()
     a.B, a.H, a.W, a.channels, a.fold, a.phase, a.eps = B, H, W, Cc, int(bool(fold)), 0, float(eps)
-    a.da_stride = I64x3(int(da.stride(0)), int(da.stride(1)), int(da.stride(2)))
-    a.x_stride = I64x3(int(x.stride(0)), int(x.stride(1)), int(x.stride(2)))
-    a.dx_stride = I64x3(int(dx.stride(0)), int(dx.stride(1)), int(dx.stride(2)))
+    a.da_stride = _strides3(da)
+    a.x_stride = _strides3(x)
+    a.dx_stride = _strides3(dx)
     with torch.cuda.device(x.device), _Timed("stem_act_bwd"):
         rc = lib.naf_stem_act_bwd(C.byref(a), _stream(x))
     _lib.check(rc, "naf_stem_act_bwd")
@@ -544,7 +553,7 @@ def xna_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_
         if t.dim() != 5 or t.stride(4) != 1:
             raise ValueError(f"xna_forward: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+    ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     _, _, h, w, Dv = v_lr.shape
     if k_lr.shape != (B, heads, h, w, Dq):
@@ -598,16 +607,30 @@ def _scores_args(dlogits: torch.Tensor, q: torch.Tensor, ky: int, kx: int) -> Xn
     return s
 
 
-def xna_backward_supported(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size) -> bool:
-    """True when ``xna_backward`` runs the MFMA cell kernel for these shapes (otherwise: the table-driven one)."""
-    lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
-    a = _fill_xna_bwd(q, k_lr, v_lr, q, q, q, q, ky, kx, None)      # shape / alignment query only
+def _bwd_query_args(q, k_lr, v_lr, kernel_size) -> XnaBwdArgs:
+    """naf_xna_bwd_args of a shape / alignment query: nothing is dereferenced, dout and dq are taken as dense channels-last buffers."""
+    a = _fill_xna_bwd(q, k_lr, v_lr, q, q, q, q, *_ksize(kernel_size), None)
     B, heads, Ho, Wo, Dq = q.shape
     Dv = v_lr.shape[-1]
     a.dout_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
     a.dq_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
-    return lib.naf_xna_bwd_supported(C.byref(a)) == _lib.XNA_MFMA
+    return a
+
+
+def _bwd_supported(lib, a: XnaBwdArgs, sa: Optional[XnaBwdScoresArgs]) -> int:
+    """The kernel the library picks for ``a`` (with the score gradient ``sa``, or None): the matching ``*_supported`` entry, raising on a refusal."""
+    if sa is None:
+        sel, entry = lib.naf_xna_bwd_supported(C.byref(a)), "naf_xna_bwd_supported"
+    else:
+        sel, entry = lib.naf_xna_bwd_scores_supported(C.byref(a), C.byref(sa)), "naf_xna_bwd_scores_supported"
+    if sel < 0:
+        _lib.check(-sel, entry)
+    return sel
+
+
+def xna_backward_supported(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size) -> bool:
+    """True when ``xna_backward`` runs the MFMA cell kernel for these shapes (otherwise: the table-driven one)."""
+    return _lib.load().naf_xna_bwd_supported(C.byref(_bwd_query_args(q, k_lr, v_lr, kernel_size))) == _lib.XNA_MFMA
 
 
 def xna_backward_select(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size, *, dlogits: Optional[torch.Tensor] = None) -> str:
@@ -615,33 +638,16 @@ def xna_backward_select(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor,
     the cell kernel does not take -- the reference's denoising call, its own training geometry, patch-14 backbones) or "generic" (table-driven scalar kernel).
     ``dlogits``: the score gradient ``xna_backward`` would get (``naf_xna_bwd_scores_supported``: non-integer ratios then run the table-driven kernel)."""
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
-    a = _fill_xna_bwd(q, k_lr, v_lr, q, q, q, q, ky, kx, None)      # shape / alignment query only
-    B, heads, Ho, Wo, Dq = q.shape
-    Dv = v_lr.shape[-1]
-    a.dout_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
-    a.dq_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
-    if dlogits is not None:
-        sel = lib.naf_xna_bwd_scores_supported(C.byref(a), C.byref(_scores_args(dlogits, q, ky, kx)))
-        if sel < 0:
-            _lib.check(-sel, "naf_xna_bwd_scores_supported")
-        return {_lib.XNA_MFMA: "mfma", _lib.XNA_ROWS: "rows"}.get(sel, "generic")
-    sel = lib.naf_xna_bwd_supported(C.byref(a))
-    if sel < 0:
-        _lib.check(-sel, "naf_xna_bwd_supported")
-    return {_lib.XNA_MFMA: "mfma", _lib.XNA_ROWS: "rows"}.get(sel, "generic")
+    a = _bwd_query_args(q, k_lr, v_lr, kernel_size)
+    sa = None if dlogits is None else _scores_args(dlogits, q, a.ky, a.kx)
+    return {_lib.XNA_MFMA: "mfma", _lib.XNA_ROWS: "rows"}.get(_bwd_supported(lib, a, sa), "generic")
 
 
 def xna_backward_chunks(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_size) -> list:
     """Channel-chunk widths of the launches the cell backward issues for these shapes (``naf_xna_bwd_chunk_plan``): one entry = the
     whole head in one launch, [] = another kernel serves the call.  dQ carries one bf16 rounding per chunk (include/naf_hip.h)."""
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
-    a = _fill_xna_bwd(q, k_lr, v_lr, q, q, q, q, ky, kx, None)      # shape / alignment query only
-    B, heads, Ho, Wo, Dq = q.shape
-    Dv = v_lr.shape[-1]
-    a.dout_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
-    a.dq_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
+    a = _bwd_query_args(q, k_lr, v_lr, kernel_size)
     out = (C.c_int32 * 16)()
     n = lib.naf_xna_bwd_chunk_plan(C.byref(a), out, 16)
     if n < 0:
@@ -665,7 +671,7 @@ def xna_backward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, dout: 
         if t.dtype != torch.bfloat16 or t.dim() != 5 or t.stride(4) != 1:
             raise TypeError(f"xna_backward: {n} must be a bfloat16 5-D [B, heads, H, W, D] view with D contiguous")
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+    ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     _, _, h, w, Dv = v_lr.shape
     if tuple(dout.shape) != (B, heads, Ho, Wo, Dv):
@@ -680,25 +686,8 @@ def xna_backward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, dout: 
         raise ValueError(f"xna_backward: path must be one of {sorted(_BWD_PATHS)}, got {path!r}")
     a = _fill_xna_bwd(q, k_lr, v_lr, dout, dq, dk, dv, ky, kx, scale)
     a.path = _BWD_PATHS[path]
-    if dlogits is not None:
-        sa = _scores_args(dlogits, q, ky, kx)
-        sel = lib.naf_xna_bwd_scores_supported(C.byref(a), C.byref(sa))
-        if sel < 0:
-            _lib.check(-sel, "naf_xna_bwd_scores_supported")
-        if sel in (_lib.XNA_GENERIC, _lib.XNA_ROWS):
-            iy = device_index_table(Ho, h, ky, dev)
-            ix = device_index_table(Wo, w, kx, dev)
-            a.idx_y, a.idx_x = iy.data_ptr(), ix.data_ptr()
-        if sel == _lib.XNA_ROWS:
-            ws = torch.empty(int(lib.naf_xna_bwd_workspace_bytes(C.byref(a))), dtype=torch.uint8, device=dev)
-            a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        with torch.cuda.device(dev), _Timed("xna_bwd_scores"):
-            rc = lib.naf_xna_bwd_scores(C.byref(a), C.byref(sa), _stream(q))
-        _lib.check(rc, "naf_xna_bwd_scores")
-        return dq, dk.permute(0, 3, 1, 2, 4), dv.permute(0, 3, 1, 2, 4)
-    sel = lib.naf_xna_bwd_supported(C.byref(a))
-    if sel < 0:
-        _lib.check(-sel, "naf_xna_bwd_supported")
+    sa = None if dlogits is None else _scores_args(dlogits, q, ky, kx)
+    sel = _bwd_supported(lib, a, sa)
     if sel in (_lib.XNA_GENERIC, _lib.XNA_ROWS):
         iy = device_index_table(Ho, h, ky, dev)
         ix = device_index_table(Wo, w, kx, dev)
@@ -706,9 +695,10 @@ def xna_backward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, dout: 
     if sel == _lib.XNA_ROWS:    # matrix-core backward of the denoising shapes: per-query softmax statistics live in a workspace
         ws = torch.empty(int(lib.naf_xna_bwd_workspace_bytes(C.byref(a))), dtype=torch.uint8, device=dev)
         a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-    with torch.cuda.device(dev), _Timed("xna_bwd"):
-        rc = lib.naf_xna_bwd(C.byref(a), _stream(q))
-    _lib.check(rc, "naf_xna_bwd")
+    entry = "naf_xna_bwd" if sa is None else "naf_xna_bwd_scores"
+    with torch.cuda.device(dev), _Timed("xna_bwd" if sa is None else "xna_bwd_scores"):
+        rc = lib.naf_xna_bwd(C.byref(a), _stream(q)) if sa is None else lib.naf_xna_bwd_scores(C.byref(a), C.byref(sa), _stream(q))
+    _lib.check(rc, entry)
     return dq, dk.permute(0, 3, 1, 2, 4), dv.permute(0, 3, 1, 2, 4)
 
 
@@ -858,7 +848,7 @@ def _fill_xna_head(q, k, pv, bias, out, n_out, ky, kx, path, scale, rope_tables=
     a.q_stride = _strides4(q, (0, 1, 2, 3))
     a.k_stride = _strides4(k, (0, 1, 2, 3))
     a.pv_stride = _strides4(pv, (0, 1, 2, 3))
-    a.o_stride = I64x3(*[int(out.stride(d)) for d in (0, 1, 2)])
+    a.o_stride = _strides3(out)
     return a
 
 
@@ -869,7 +859,7 @@ def xna_head_select(q: torch.Tensor, lr_size, n_out: int, kernel_size, *, out_dt
     if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or out_dtype not in _DT or not 1 <= int(n_out) <= 256:
         return "composed"
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
+    ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     h, w = int(lr_size[0]), int(lr_size[1])
     npad = head_npad(n_out)
@@ -889,6 +879,32 @@ def xna_head_select(q: torch.Tensor, lr_size, n_out: int, kernel_size, *, out_dt
     return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
 
 
+def _check_head_operands(who: str, q, k_lr, pv_lr, bias, kernel_size, n_out, path):
+    """What ``xna_head_forward`` and ``xna_head_objective`` ask of their operands; ``who`` names the caller in the messages.
+    Returns (ky, kx, B, heads, Ho, Wo, Dq, h, w, npad, n_out)."""
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
+        _gpu(t, n)
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"{who}: {n} must be bfloat16, got {t.dtype}")
+        if t.dim() != 5 or t.stride(4) != 1:
+            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    if path not in _HEAD_PATHS:
+        raise ValueError(f"{who}: path must be one of {_HEAD_PATHS}, got {path!r}")
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w, npad = pv_lr.shape[2:]
+    n_out = int(n_out)
+    if k_lr.shape != (B, heads, h, w, Dq) or pv_lr.shape[:2] != (B, heads):
+        raise ValueError(f"{who}: k_lr {tuple(k_lr.shape)} / pv_lr {tuple(pv_lr.shape)} do not match q {tuple(q.shape)}")
+    if n_out < 1 or npad != head_npad(n_out):
+        raise ValueError(f"{who}: pv_lr holds {npad} channels, n_out = {n_out} needs {head_npad(max(n_out, 1))}")
+    if bias is not None:
+        _gpu(bias, "bias")
+        if bias.dtype != torch.float32 or tuple(bias.shape) != (n_out,) or not bias.is_contiguous():
+            raise ValueError(f"{who}: bias must be a contiguous float32 [{n_out}] tensor")
+    return ky, kx, B, heads, Ho, Wo, Dq, h, w, npad, n_out
+
+
 def xna_head_forward(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, bias: Optional[torch.Tensor], kernel_size, *,
                      n_out: int, out_dtype: torch.dtype = torch.float32, path: str = "auto", scale: Optional[float] = None,
                      rope_tables=None) -> torch.Tensor:
@@ -901,29 +917,10 @@ def xna_head_forward(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, b
     serves every geometry ``xna_forward`` serves -- ``xna_forward`` on ``pv_lr`` with fp32 output, summed over the head axis, plus bias.
     ``path="fused"`` insists on the kernel and raises where it does not serve the call; ``path="composed"`` insists on the composition.
     ``rope_tables``: as in ``xna_forward`` (q is the un-rotated guidance)."""
-    for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
-        _gpu(t, n)
-        if t.dtype != torch.bfloat16:
-            raise TypeError(f"xna_head_forward: {n} must be bfloat16, got {t.dtype}")
-        if t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"xna_head_forward: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
-    if path not in _HEAD_PATHS:
-        raise ValueError(f"xna_head_forward: path must be one of {_HEAD_PATHS}, got {path!r}")
+    ky, kx, B, heads, Ho, Wo, Dq, h, w, npad, n_out = _check_head_operands("xna_head_forward", q, k_lr, pv_lr, bias, kernel_size, n_out, path)
     if out_dtype not in _DT:
         raise TypeError(f"xna_head_forward: out_dtype {out_dtype} not supported (bfloat16 / float32)")
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
-    B, heads, Ho, Wo, Dq = q.shape
-    h, w, npad = pv_lr.shape[2:]
-    n_out = int(n_out)
-    if k_lr.shape != (B, heads, h, w, Dq) or pv_lr.shape[:2] != (B, heads):
-        raise ValueError(f"xna_head_forward: k_lr {tuple(k_lr.shape)} / pv_lr {tuple(pv_lr.shape)} do not match q {tuple(q.shape)}")
-    if n_out < 1 or npad != head_npad(n_out):
-        raise ValueError(f"xna_head_forward: pv_lr holds {npad} channels, n_out = {n_out} needs {head_npad(max(n_out, 1))}")
-    if bias is not None:
-        _gpu(bias, "bias")
-        if bias.dtype != torch.float32 or tuple(bias.shape) != (n_out,) or not bias.is_contiguous():
-            raise ValueError(f"xna_head_forward: bias must be a contiguous float32 [{n_out}] tensor")
     dev = q.device
     if path != "composed" and (n_out <= 256 or path == "fused"):
         out = torch.empty((B, Ho, Wo, n_out), dtype=out_dtype, device=dev)
@@ -943,6 +940,23 @@ def xna_head_forward(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, b
         if bias is not None:
             o = o + bias
         return o.to(out_dtype).contiguous().permute(0, 3, 1, 2)
+
+
+def head_dlogits_channels(n_out: int) -> int:
+    """Channels of a ``dlogits`` row for ``n_out`` classes: the value width the cell backward serves that holds Npad (``_BWD_DV``)."""
+    npad = head_npad(n_out)
+    return next((c for c in _BWD_DV if c >= npad), npad)
+
+
+def _head_values_grad(q, k_lr, pv_lr, g, kernel_size, scale) -> torch.Tensor:
+    """fp32 gradient of ``pv_lr`` [B, heads, h, w, Npad] for ONE gradient of the logits ``g`` (bf16 [B, Ho, Wo, Gc], Gc >= Npad a width the
+    cell backward serves, zero pad channels): ``pv_lr`` is padded to Gc (the pad channels' gradient is zero), ``g`` is the ``dout`` of every
+    head (stride 0), dq / dk are dropped."""
+    B, heads, Ho, Wo, _ = q.shape
+    npad, gc = pv_lr.shape[-1], g.shape[-1]
+    pvp = torch.nn.functional.pad(pv_lr, (0, gc - npad)) if gc != npad else pv_lr
+    _, _, dv = xna_backward(q, k_lr, pvp, g.unsqueeze(1).expand(B, heads, Ho, Wo, gc), kernel_size, scale=scale)
+    return dv[..., :npad]
 
 
 class XnaHeadFunction(torch.autograd.Function):
@@ -966,25 +980,15 @@ class XnaHeadFunction(torch.autograd.Function):
         if need_b:
             dbias = dout.float().sum(dim=(0, 2, 3))
         if need_pv:
-            B, heads, Ho, Wo, _ = q.shape
-            npad = pv_lr.shape[-1]
-            dvp = next((c for c in _BWD_DV if c >= npad), npad)     # a width the cell backward serves; the pad channels' gradient is zero
-            g = torch.zeros((B, Ho, Wo, dvp), dtype=torch.bfloat16, device=q.device)
+            B, _, Ho, Wo, _ = q.shape
+            g = torch.zeros((B, Ho, Wo, head_dlogits_channels(N)), dtype=torch.bfloat16, device=q.device)
             g[..., :N] = dout.permute(0, 2, 3, 1)
-            pvp = torch.nn.functional.pad(pv_lr, (0, dvp - npad)) if dvp != npad else pv_lr
-            _, _, dv = xna_backward(q, k_lr, pvp, g.unsqueeze(1).expand(B, heads, Ho, Wo, dvp), ctx.kernel_size, scale=ctx.scale)
-            dpv = dv[..., :npad].to(pv_lr.dtype)
+            dpv = _head_values_grad(q, k_lr, pv_lr, g, ctx.kernel_size, ctx.scale).to(pv_lr.dtype)
         return None, None, dpv, dbias, None, None, None, None, None
 
 
 # ---- ... and a classification objective in its epilogue (cross-entropy / argmax of the probe's logits) -------------------
 _REDUCTIONS = ("mean", "sum", "none")
-
-
-def head_dlogits_channels(n_out: int) -> int:
-    """Channels of a ``dlogits`` row for ``n_out`` classes: the value width the cell backward serves that holds Npad (``_BWD_DV``)."""
-    npad = head_npad(n_out)
-    return next((c for c in _BWD_DV if c >= npad), npad)
 
 
 def head_valid_pixels(target: torch.Tensor, ignore_index: int, n_out: int) -> torch.Tensor:
@@ -1137,29 +1141,10 @@ def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor,
     launch (``naf_xna_head_cm_fwd``): ``confusion[t, label] += 1`` for every pixel that is not ignored; needs ``target``; the returned
     4-tuple is unchanged and may be all None.  Loss, labels and matrix of one launch are available here together.  The composed route
     counts its labels with ``head_confusion_from_labels``."""
-    for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
-        _gpu(t, n)
-        if t.dtype != torch.bfloat16:
-            raise TypeError(f"xna_head_objective: {n} must be bfloat16, got {t.dtype}")
-        if t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"xna_head_objective: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
-    if path not in _HEAD_PATHS:
-        raise ValueError(f"xna_head_objective: path must be one of {_HEAD_PATHS}, got {path!r}")
+    ky, kx, B, heads, Ho, Wo, Dq, h, w, npad, n_out = _check_head_operands("xna_head_objective", q, k_lr, pv_lr, bias, kernel_size, n_out, path)
     if not (want_loss or want_labels or want_dlogits or return_logits or confusion is not None):
         raise ValueError("xna_head_objective: nothing asked for (want_loss / want_labels / want_dlogits / return_logits / confusion)")
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else (int(kernel_size[0]), int(kernel_size[1]))
-    B, heads, Ho, Wo, Dq = q.shape
-    h, w, npad = pv_lr.shape[2:]
-    n_out = int(n_out)
-    if k_lr.shape != (B, heads, h, w, Dq) or pv_lr.shape[:2] != (B, heads):
-        raise ValueError(f"xna_head_objective: k_lr {tuple(k_lr.shape)} / pv_lr {tuple(pv_lr.shape)} do not match q {tuple(q.shape)}")
-    if n_out < 1 or npad != head_npad(n_out):
-        raise ValueError(f"xna_head_objective: pv_lr holds {npad} channels, n_out = {n_out} needs {head_npad(max(n_out, 1))}")
-    if bias is not None:
-        _gpu(bias, "bias")
-        if bias.dtype != torch.float32 or tuple(bias.shape) != (n_out,) or not bias.is_contiguous():
-            raise ValueError(f"xna_head_objective: bias must be a contiguous float32 [{n_out}] tensor")
     dev = q.device
     if want_loss or want_dlogits:
         if target is None:
@@ -1185,7 +1170,7 @@ def xna_head_objective(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor,
                            (labels, "labels", "labels_stride"), (g, "dlogits", "dlogits_stride")):
             if t is not None:
                 setattr(a, ptr, t.data_ptr())
-                setattr(a, st, I64x3(*[int(t.stride(d)) for d in (0, 1, 2)]))
+                setattr(a, st, _strides3(t))
         if confusion is not None:              # the same epilogue counting into the caller's matrix: an entry point of its own
             m = _lib.XnaHeadCMArgs()
             m.ce, m.confusion, m.cm_stride = a, confusion.data_ptr(), int(confusion.stride(0))
@@ -1257,11 +1242,7 @@ class XnaHeadCEFunction(torch.autograd.Function):
             if factor is not None:
                 dbias = dbias * factor
         if need_pv:
-            B, heads, Ho, Wo, _ = q.shape
-            npad, gc = pv_lr.shape[-1], g.shape[-1]
-            pvp = torch.nn.functional.pad(pv_lr, (0, gc - npad)) if gc != npad else pv_lr
-            _, _, dv = xna_backward(q, k_lr, pvp, g.unsqueeze(1).expand(B, heads, Ho, Wo, gc), ctx.kernel_size, scale=ctx.scale)
-            dv = dv[..., :npad]
+            dv = _head_values_grad(q, k_lr, pv_lr, g, ctx.kernel_size, ctx.scale)
             if factor is not None:
                 dv = dv * factor
             dpv = dv.to(pv_lr.dtype)
@@ -1275,7 +1256,7 @@ def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables
     if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or out_dtype not in _DT:
         return False
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else tuple(kernel_size)
+    ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     h, w = int(lr_size[0]), int(lr_size[1])
     a = XnaArgs()
@@ -1293,7 +1274,7 @@ def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables
 def xna_select(q, k_lr, v_lr, kernel_size, out_dtype=torch.bfloat16, return_logits=False, path="auto") -> str:
     """Name of the kernel ``xna_forward`` would dispatch to ('mfma' / 'generic') -- for tests / bench."""
     lib = _lib.load()
-    ky, kx = (int(kernel_size), int(kernel_size)) if isinstance(kernel_size, int) else tuple(kernel_size)
+    ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     Dv = v_lr.shape[-1]
     out = torch.empty((1, 1, 1, heads, Dv), dtype=out_dtype, device=q.device).permute(0, 3, 1, 2, 4)
