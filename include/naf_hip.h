@@ -63,7 +63,8 @@ extern "C" {
  * naf_xna_head_fwd / naf_xna_head_workspace_bytes -- the attention with a linear head folded in (naf_xna_head_args).  A host detects them by symbol
  * (dlsym), not by naf_version().  Added the same way after them: naf_xna_head_ce_select / naf_xna_head_ce_fwd -- that attention with a
  * cross-entropy / argmax epilogue (naf_xna_head_ce_args, which embeds naf_xna_head_args unchanged); and after those naf_xna_head_cm_select /
- * naf_xna_head_cm_fwd -- that epilogue counting into a confusion matrix (naf_xna_head_cm_args, which embeds naf_xna_head_ce_args unchanged). */
+ * naf_xna_head_cm_fwd -- that epilogue counting into a confusion matrix (naf_xna_head_cm_args, which embeds naf_xna_head_ce_args unchanged); and after
+ * those naf_propagate_select / naf_propagate_fwd / naf_feature_inv_norm -- label propagation for video evaluation (naf_propagate_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -571,6 +572,46 @@ typedef struct naf_xna_head_cm_args {
 } naf_xna_head_cm_args;
 int naf_xna_head_cm_select(const naf_xna_head_cm_args* a);
 int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream);
+
+/* ---- label propagation: windowed top-k affinity over a queue of context frames (added after the confusion entries; detect by symbol) ----
+ * Replaces label_propagation (evaluation/eval_video_seg.py:499-561) after feature extraction: the reference materialises
+ * exp(bmm(feat_tar, feat_sources) / T) as a dense [n * h*w, h*w] matrix, multiplies it by restrict_neighborhood's mask, takes topk along the
+ * source axis, thresholds, normalises and multiplies by the label maps.  Here the affinities are never written.  For a target pixel p = (i, j):
+ *   candidates  every (frame f, pixel (i', j')) with |i - i'| <= radius and |j - j'| <= radius inside the image (window clipped, not shifted)
+ *   score       s = cos(target[p], context[f][i', j']): the raw bf16 dot product on the matrix cores (fp32 accumulation) times the two
+ *               per-pixel inverse norms of naf_feature_inv_norm; on bf16 inputs within (C + 8) * 2^-24 of exact arithmetic
+ *   threshold   the topk-th largest score among the candidates; with fewer than topk candidates all of them are kept
+ *   kept        every candidate with s >= threshold: TIES AT THE THRESHOLD ARE ALL KEPT (as `aff[aff < tk_val_min] = 0` keeps them)
+ *   out[:, p]   sum_kept w * segs[f, i', j', :] / sum_kept w,  w = exp((s - s_max) / temperature), s_max the pixel's largest score
+ * Features are consumed as bf16: a caller holding fp32 features rounds them to bf16 ONCE (no normalise-then-round).
+ *   target, context[f]          bf16, dense channels-last [h, w, C], 16-byte aligned: context frames are separate pointers passed by value,
+ *                               so a caller's frame queue is never stacked or copied
+ *   target_inv, context_inv[f]  fp32 [h, w]: 1 / max(||x||_2, 1e-12) per pixel (naf_feature_inv_norm; F.normalize's eps)
+ *   segs                        fp32, dense channels-last [n, h, w, K]: the context frames' soft label maps
+ *   out                         fp32, dense [K, h, w]
+ * Served: C % 32 == 0 and 32 <= C <= 1024, 1 <= K <= 64, 1 <= topk <= 16, 1 <= radius <= 15, 1 <= n <= 16, any h, w >= 1 (h * w * max(C, K)
+ * below 2^31 elements per frame); anything else that is well formed is NAF_ERR_UNSUPPORTED with the limit named in naf_last_error().
+ * radius = 0 is the reference's "no mask", the dense case: not served.  No atomics: the output is bit-reproducible from run to run.
+ * naf_propagate_select is a host-only query (it reads the scalar fields only and touches no device): NAF_OK, NAF_ERR_UNSUPPORTED or
+ * NAF_ERR_INVALID (NULL args, non-positive sizes, negative radius, temperature not > 0, non-zero reserved).  naf_propagate_fwd additionally
+ * refuses NULL or misaligned pointers.  Caller-owned memory and stream; capturable; no workspace. */
+#define NAF_PROPAGATE_MAX_FRAMES 16
+typedef struct naf_propagate_args {
+    const void* target;
+    const float* target_inv;
+    const void* context[NAF_PROPAGATE_MAX_FRAMES];      /* entries [n .. 16) are ignored */
+    const float* context_inv[NAF_PROPAGATE_MAX_FRAMES];
+    const float* segs;
+    float* out;
+    int32_t n, C, h, w, K, radius, topk;
+    float temperature;
+    int32_t reserved[2]; /* must be 0 */
+} naf_propagate_args;
+int naf_propagate_select(const naf_propagate_args* a);
+int naf_propagate_fwd(const naf_propagate_args* a, naf_stream_t stream);
+/* inv[p] = 1 / max(sqrt(sum_c x[p][c]^2), 1e-12) from an fp32 sum of squares.  x: bf16 dense channels-last [h, w, C], 16-byte aligned,
+ * C % 8 == 0; inv: fp32 [h, w].  NAF_ERR_INVALID on NULL / misaligned pointers or non-positive sizes. */
+int naf_feature_inv_norm(const void* x, float* inv, int32_t h, int32_t w, int32_t C, naf_stream_t stream);
 
 /* ---- cross-scale neighbourhood attention backward --------------------------------------------------
  * Replaces what autograd runs through legacy_attention (attentions.py:16-29: the backward of na2d_qk, the

@@ -8,7 +8,8 @@ attention filtering forward, behind the reference's own API (valeoai/NAF: src/mo
 Kernels live in naf_amd/csrc (HIP, C ABI in include/naf_hip.h); build with ``python -m naf_amd.build``.
 """
 from .model import NAF, CrossAttention, GraphedForward, ImageEncoder, RoPE  # noqa: F401
-from .ops import ConfusionMetrics, confusion_metrics  # noqa: F401
+from .ops import ConfusionMetrics, FrameFeatures, confusion_metrics, pack_frame, propagate_labels  # noqa: F401
 
-__all__ = ["NAF", "CrossAttention", "GraphedForward", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics"]
+__all__ = ["NAF", "CrossAttention", "GraphedForward", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics",
+           "FrameFeatures", "pack_frame", "propagate_labels"]
 __version__ = "0.1.0"

@@ -72,6 +72,20 @@ class XnaHeadCMArgs(C.Structure):
     _fields_ = [("ce", XnaHeadCEArgs), ("confusion", C.c_void_p), ("cm_stride", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
+PROPAGATE_MAX_FRAMES = 16
+
+
+class PropagateArgs(C.Structure):
+    """naf_propagate_args (added after the confusion entries, detected by symbol): label propagation over a queue of context frames."""
+    _fields_ = [
+        ("target", C.c_void_p), ("target_inv", C.c_void_p),
+        ("context", C.c_void_p * PROPAGATE_MAX_FRAMES), ("context_inv", C.c_void_p * PROPAGATE_MAX_FRAMES),
+        ("segs", C.c_void_p), ("out", C.c_void_p),
+        ("n", C.c_int32), ("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("K", C.c_int32), ("radius", C.c_int32),
+        ("topk", C.c_int32), ("temperature", C.c_float), ("reserved", C.c_int32 * 2),
+    ]
+
+
 class StemConv0Args(C.Structure):
     _fields_ = [
         ("image", C.c_void_p), ("y", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("stats_out", C.c_void_p),
@@ -241,6 +255,9 @@ SIGNATURES = {
     "naf_xna_head_ce_fwd": (C.c_int, [C.POINTER(XnaHeadCEArgs), C.c_void_p]),
     "naf_xna_head_cm_select": (C.c_int, [C.POINTER(XnaHeadCMArgs)]),
     "naf_xna_head_cm_fwd": (C.c_int, [C.POINTER(XnaHeadCMArgs), C.c_void_p]),
+    "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
+    "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
+    "naf_feature_inv_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

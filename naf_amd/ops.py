@@ -10,6 +10,7 @@ Reference counterparts (paths relative to the reference repo):
   pack_values        CrossAttention._resize layout/dtype part           src/layers/attentions.py:50-51
   xna_forward        legacy_attention / na2d                            src/layers/attentions.py:16-29,72
   xna_head_forward   the same with the probe's 1x1 convolution folded in  evaluation/eval_seg_probing.py:56,104-111
+  propagate_labels   label_propagation after feature extraction          evaluation/eval_video_seg.py:499-561
 """
 from __future__ import annotations
 
@@ -1478,3 +1479,151 @@ class ForwardPlan:
         _lib.check(rc, "naf_forward_ex")
         out = out.permute(0, 3, 1, 2)
         return (out, logits) if return_logits else out
+
+
+# ---- label propagation for video evaluation (evaluation/eval_video_seg.py:499-561) -----------------------------------------------
+class FrameFeatures:
+    """One frame's features as ``propagate_labels`` consumes them: ``data`` is the dense channels-last bf16 buffer ``[h, w, C]`` and
+    ``inv_norm`` the fp32 ``[h, w]`` map of ``1 / max(||x||, 1e-12)`` (``F.normalize``'s eps).  Built by ``pack_frame``; a caller keeps one
+    per frame of its queue, so that a frame is packed once however many targets it serves as context for."""
+    __slots__ = ("data", "inv_norm")
+
+    def __init__(self, data: torch.Tensor, inv_norm: torch.Tensor):
+        self.data, self.inv_norm = data, inv_norm
+
+    @property
+    def shape(self):
+        """(C, h, w)"""
+        return (int(self.data.shape[2]), int(self.data.shape[0]), int(self.data.shape[1]))
+
+    @property
+    def device(self):
+        return self.data.device
+
+
+def _frame_chw(x, name: str):
+    """(C, h, w) of a frame given as a [C, h, w] / [1, C, h, w] tensor or as FrameFeatures; ValueError on anything else."""
+    if isinstance(x, FrameFeatures):
+        return x.shape
+    if not torch.is_tensor(x):
+        raise ValueError(f"naf_amd: `{name}` must be a tensor or FrameFeatures, got {type(x).__name__}")
+    if x.dim() == 4 and x.shape[0] == 1:
+        shape = x.shape[1:]
+    elif x.dim() == 3:
+        shape = x.shape
+    else:
+        raise ValueError(f"naf_amd: `{name}` must be [C, h, w] or [1, C, h, w], got {tuple(x.shape)}")
+    if x.dtype not in (torch.bfloat16, torch.float32):
+        raise ValueError(f"naf_amd: `{name}` must be bfloat16 or float32 features, got {x.dtype}")
+    C_, h, w = (int(v) for v in shape)
+    if h < 1 or w < 1:
+        raise ValueError(f"naf_amd: `{name}` has an empty grid {h} x {w}")
+    if C_ % 32 != 0 or not 32 <= C_ <= 1024:
+        raise ValueError(f"naf_amd: `{name}` has C = {C_} channels; label propagation serves C % 32 == 0 and 32 <= C <= 1024")
+    return C_, h, w
+
+
+def pack_frame(feats, name: str = "feats") -> FrameFeatures:
+    """Pack one frame's features ``[C, h, w]`` or ``[1, C, h, w]`` (bf16 or fp32, any strides) for ``propagate_labels``.
+
+    fp32 features are rounded to bf16 ONCE, as they are (they are not normalised first): the kernel multiplies the raw bf16 dot products by
+    the inverse norms computed here from those same bf16 values.  When ``feats`` is already a dense channels-last bf16 view -- what
+    ``naf(...)`` returns -- the buffer is used as it is, without a copy."""
+    if isinstance(feats, FrameFeatures):
+        return feats
+    C_, h, w = _frame_chw(feats, name)
+    _gpu(feats, name)
+    x = (feats[0] if feats.dim() == 4 else feats).detach()
+    if x.dtype != torch.bfloat16:
+        x = x.to(torch.bfloat16)
+    hwc = x.permute(1, 2, 0)
+    if not hwc.is_contiguous():
+        hwc = hwc.contiguous()
+    if hwc.data_ptr() % 16:
+        hwc = hwc.clone()
+    inv = torch.empty((h, w), dtype=torch.float32, device=hwc.device)
+    with torch.cuda.device(hwc.device):
+        rc = _lib.load().naf_feature_inv_norm(hwc.data_ptr(), inv.data_ptr(), h, w, C_, _stream(hwc))
+    _lib.check(rc, "naf_feature_inv_norm")
+    return FrameFeatures(hwc, inv)
+
+
+def propagate_labels(target, context, segs, radius: int = 12, topk: int = 5, temperature: float = 0.1) -> torch.Tensor:
+    """Propagate the context frames' label maps to the target frame: the reference's ``label_propagation`` after feature extraction
+    (evaluation/eval_video_seg.py:499-561), with the affinity matrix never materialised.
+
+    ``target`` and each element of ``context`` are ``[C, h, w]`` / ``[1, C, h, w]`` features (bf16, or fp32 that is rounded to bf16 once) or
+    ``FrameFeatures`` from ``pack_frame``; ``context`` may also be one stacked ``[n, C, h, w]`` tensor.  ``segs`` is ``[n, K, h, w]`` or a
+    list of ``[1, K, h, w]`` / ``[K, h, w]`` soft label maps, one per context frame.  For every target pixel the candidates are the pixels
+    of every context frame within ``radius`` in both directions (window clipped at the borders); the ``topk``-th largest cosine similarity
+    is the threshold, every candidate at or above it is kept -- ties at the threshold are ALL kept -- and the output is the
+    ``exp(s / temperature)``-weighted mean of the kept candidates' labels.  Returns ``[1, K, h, w]`` fp32, detached (not differentiable).
+
+    Served: C % 32 == 0 and 32 <= C <= 1024, 1 <= K <= 64, 1 <= topk <= 16, 1 <= radius <= 15, 1 <= n <= 16.  ``radius=0`` is the
+    reference's dense case and is not served.  Anything else raises ``ValueError``; there is no torch fallback."""
+    who = "propagate_labels"
+    if torch.is_tensor(context):
+        if context.dim() != 4:
+            raise ValueError(f"naf_amd.{who}: a `context` tensor must be stacked frames [n, C, h, w], got {tuple(context.shape)}")
+        frames = list(context.unbind(0))
+    elif isinstance(context, FrameFeatures):
+        frames = [context]
+    elif isinstance(context, (list, tuple)):
+        frames = list(context)
+    else:
+        raise ValueError(f"naf_amd.{who}: `context` must be a list of frames or a stacked tensor, got {type(context).__name__}")
+    n = len(frames)
+    if not 1 <= n <= _lib.PROPAGATE_MAX_FRAMES:
+        raise ValueError(f"naf_amd.{who}: n = {n} context frames; served: 1 <= n <= {_lib.PROPAGATE_MAX_FRAMES}")
+    C_, h, w = _frame_chw(target, "target")
+    for i, f in enumerate(frames):
+        if _frame_chw(f, f"context[{i}]") != (C_, h, w):
+            raise ValueError(f"naf_amd.{who}: context[{i}] is (C, h, w) = {_frame_chw(f, 'context')}, the target is {(C_, h, w)}")
+    if torch.is_tensor(segs):
+        if segs.dim() != 4:
+            raise ValueError(f"naf_amd.{who}: a `segs` tensor must be [n, K, h, w], got {tuple(segs.shape)}")
+        seg_list = [segs]
+    elif isinstance(segs, (list, tuple)) and all(torch.is_tensor(s) for s in segs):
+        for i, s in enumerate(segs):
+            if not (s.dim() == 3 or (s.dim() == 4 and s.shape[0] == 1)):
+                raise ValueError(f"naf_amd.{who}: segs[{i}] must be [K, h, w] or [1, K, h, w], got {tuple(s.shape)}")
+        seg_list = [s if s.dim() == 4 else s[None] for s in segs]
+    else:
+        raise ValueError(f"naf_amd.{who}: `segs` must be an [n, K, h, w] tensor or a list of label maps")
+    if sum(int(s.shape[0]) for s in seg_list) != n:
+        raise ValueError(f"naf_amd.{who}: {sum(int(s.shape[0]) for s in seg_list)} label maps for n = {n} context frames")
+    K = int(seg_list[0].shape[1])
+    for s in seg_list:
+        if not s.is_floating_point():
+            raise ValueError(f"naf_amd.{who}: `segs` must be floating-point soft label maps (one-hot for the first frame), got {s.dtype}")
+        if tuple(s.shape[1:]) != (K, h, w):
+            raise ValueError(f"naf_amd.{who}: a label map is (K, h, w) = {tuple(s.shape[1:])}, expected {(K, h, w)}")
+    a = _lib.PropagateArgs()
+    a.n, a.C, a.h, a.w, a.K = n, C_, h, w, K
+    try:
+        a.radius, a.topk, a.temperature = int(radius), int(topk), float(temperature)
+    except (TypeError, OverflowError) as e:
+        raise ValueError(f"naf_amd.{who}: radius, topk and temperature must be numbers: {e}") from e
+    lib = _lib.load()
+    if lib.naf_propagate_select(C.byref(a)) != 0:            # host only: the limits live in one place, the library
+        raise ValueError(f"naf_amd.{who}: {_lib.last_error()}")
+
+    tensors = [t.data if isinstance(t, FrameFeatures) else t for t in [target, *frames]] + seg_list
+    for t in tensors:
+        _gpu(t, "features and segs")
+    dev = tensors[0].device
+    if any(t.device != dev for t in tensors):
+        raise ValueError(f"naf_amd.{who}: target, context and segs must live on one device")
+    tgt = pack_frame(target, "target")
+    ctx = [pack_frame(f, f"context[{i}]") for i, f in enumerate(frames)]
+    sg = (seg_list[0] if len(seg_list) == 1 else torch.cat(seg_list, 0)).detach()
+    sg = sg.to(torch.float32).permute(0, 2, 3, 1).contiguous()           # [n, h, w, K]: one kept candidate's labels are contiguous
+    out = torch.empty((1, K, h, w), dtype=torch.float32, device=dev)
+    a.target, a.target_inv = tgt.data.data_ptr(), tgt.inv_norm.data_ptr()
+    for i, f in enumerate(ctx):
+        a.context[i], a.context_inv[i] = f.data.data_ptr(), f.inv_norm.data_ptr()
+    a.segs, a.out = sg.data_ptr(), out.data_ptr()
+    with torch.cuda.device(dev), _Timed("propagate"):
+        rc = lib.naf_propagate_fwd(C.byref(a), _stream(out))
+    _lib.check(rc, "naf_propagate_fwd")
+    return out
