@@ -64,7 +64,8 @@ extern "C" {
  * (dlsym), not by naf_version().  Added the same way after them: naf_xna_head_ce_select / naf_xna_head_ce_fwd -- that attention with a
  * cross-entropy / argmax epilogue (naf_xna_head_ce_args, which embeds naf_xna_head_args unchanged); and after those naf_xna_head_cm_select /
  * naf_xna_head_cm_fwd -- that epilogue counting into a confusion matrix (naf_xna_head_cm_args, which embeds naf_xna_head_ce_args unchanged); and after
- * those naf_propagate_select / naf_propagate_fwd / naf_feature_inv_norm -- label propagation for video evaluation (naf_propagate_args). */
+ * those naf_propagate_select / naf_propagate_fwd / naf_feature_inv_norm -- label propagation for video evaluation (naf_propagate_args); and after
+ * those naf_denoise_objective / naf_denoise_workspace_bytes -- the denoising loss with its gradient, and the PSNR / SSIM metrics (naf_denoise_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -612,6 +613,57 @@ int naf_propagate_fwd(const naf_propagate_args* a, naf_stream_t stream);
 /* inv[p] = 1 / max(sqrt(sum_c x[p][c]^2), 1e-12) from an fp32 sum of squares.  x: bf16 dense channels-last [h, w, C], 16-byte aligned,
  * C % 8 == 0; inv: fp32 [h, w].  NAF_ERR_INVALID on NULL / misaligned pointers or non-positive sizes. */
 int naf_feature_inv_norm(const void* x, float* inv, int32_t h, int32_t w, int32_t C, naf_stream_t stream);
+
+/* ---- denoising objective: L1 / L2 / SSIM loss with its gradient, PSNR / SSIM metrics (added after the propagation entries; detect by symbol) ----
+ * Replaces DenoisingLoss (denoising.py:129-177) with the backward autograd runs through it, and MetricsCalculator (denoising.py:61-126) with
+ * the clamp in front of it (denoising.py:302): one tile kernel plus a one-workgroup finishing kernel instead of a chain of pools, grouped
+ * convolutions and elementwise passes.  pred and target are [B, C, H, W] given by four ELEMENT strides {b, c, y, x} each (any layout: pred is
+ * usually the logical-NCHW view of a channels-last buffer), fp32 or bf16 independently; any C, H, W >= 1, images smaller than the window
+ * included.  Every (b, c) plane is independent.  All arithmetic is fp32 on the values as given (bf16 is widened, never re-rounded).
+ *
+ * mode NAF_DENOISE_LOSS, per plane, with box(x) = zero-padded 3 x 3 sum / 9 (F.avg_pool2d(x, 3, 1, 1): the divisor is always 9):
+ *     mu1 = box(p), mu2 = box(t), s1 = box(p^2) - mu1^2, s2 = box(t^2) - mu2^2, s12 = box(p t) - mu1 mu2        C1 = 1e-4, C2 = 9e-4
+ *     n1 = 2 mu1 mu2 + C1, n2 = 2 s12 + C2, d1 = mu1^2 + mu2^2 + C1, d2 = s1 + s2 + C2, S = n1 n2 / (d1 d2)
+ *   The (co)variances are evaluated in their centred form, box((p - mu1)(t - mu2)) over the same nine samples (padding zeros included),
+ *   which is the same number without the cancellation of box(p t) - mu1 mu2.
+ *   out[0] = mean |p - t|, out[1] = mean (p - t)^2, out[2] = mean S            (N = B C H W)
+ *   out[3] = l1_weight * out[0], out[4] = l2_weight * out[1], out[5] = ssim_weight * (1 - out[2]), out[6] = out[3] + out[4] + out[5]:
+ *   the reference's dict entries, formed in fp64 from the fp64 sums and rounded once; out[7] = 0
+ *   grad (optional): d out[6] / d pred, ONE map, written in the same launch:
+ *     a = 2 mu2 (n2 - n1) / (d1 d2) - 2 mu1 S (1/d1 - 1/d2),  b = -S / d2,  c = 2 n1 / (d1 d2)
+ *     g = [ l1_weight sign(p - t) + 2 l2_weight (p - t) - ssim_weight ( box(a) + 2 p box(b) + t box(c) ) ] / N,      sign(0) = 0
+ *   in grad_dtype (bf16: rounded once, to nearest even) at grad_stride.
+ * mode NAF_DENOISE_METRICS (forward only; grad must be NULL, the weights are ignored): pred is clamped to [0, 1] on load when clamp != 0; the
+ *   windowed means go through the 11 x 11 window w[i][j] = g[i] g[j], g the fp32 vector exp(-(i - 5)^2 / (2 (11/6)^2)) normalised in fp32,
+ *   with zero padding, evaluated separably; S as above.
+ *   out[0] = PSNR = -10 log10(mse) in dB (+inf for mse = 0), out[1] = mean S, out[2] = mse = mean (p - t)^2, out[3..7] = 0
+ * Summation: no floating-point atomics.  A workgroup owns one 32 x 32 tile of one plane; a thread adds at most five terms, the workgroup's
+ * 256 threads add theirs in a binary tree (at most 13 fp32 additions between a pixel's term and the workgroup's partial), the partial goes to
+ * `workspace`, and the finishing kernel adds all partials in fp64 in a fixed order: two runs give the same bits.
+ *   out        device float[8]
+ *   workspace  device, naf_denoise_workspace_bytes(a) bytes, 16-byte aligned; contents need no initialisation
+ * Argument checks happen before any HIP call: NAF_ERR_INVALID for NULL args / pred / target / out / workspace, B, C, H or W <= 0, an unknown
+ * dtype or mode, a negative (or NaN) weight, a workspace that is too small, grad in metrics mode, non-zero reserved; NAF_ERR_UNSUPPORTED for
+ * 2^24 tiles of 32 x 32 or more.  naf_denoise_workspace_bytes reads B, C, H, W only and returns 0 for arguments that are not valid.
+ * Caller-owned memory, workspace and stream; nothing is allocated or kept; capturable. */
+enum naf_denoise_mode { NAF_DENOISE_LOSS = 0, NAF_DENOISE_METRICS = 1 };
+typedef struct naf_denoise_args {
+    const void* pred;
+    const void* target;
+    void* grad;             /* optional, loss mode: [B, C, H, W] at grad_stride */
+    float* out;             /* float[8] */
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t pred_dtype, target_dtype, grad_dtype; /* naf_dtype */
+    int32_t mode;                                 /* naf_denoise_mode */
+    int32_t B, C, H, W;
+    int32_t clamp;    /* metrics mode: clamp pred to [0, 1] on load */
+    int32_t reserved; /* must be 0 */
+    double l1_weight, l2_weight, ssim_weight;
+    int64_t pred_stride[4], target_stride[4], grad_stride[4]; /* {b, c, y, x} */
+} naf_denoise_args;
+size_t naf_denoise_workspace_bytes(const naf_denoise_args* a);
+int naf_denoise_objective(const naf_denoise_args* a, naf_stream_t stream);
 
 /* ---- cross-scale neighbourhood attention backward --------------------------------------------------
  * Replaces what autograd runs through legacy_attention (attentions.py:16-29: the backward of na2d_qk, the

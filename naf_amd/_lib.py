@@ -86,6 +86,21 @@ class PropagateArgs(C.Structure):
     ]
 
 
+DENOISE_LOSS, DENOISE_METRICS = 0, 1            # naf_denoise_mode
+
+
+class DenoiseArgs(C.Structure):
+    """naf_denoise_args (added after the propagation entries, detected by symbol): the denoising loss with its gradient, or the metrics."""
+    _fields_ = [
+        ("pred", C.c_void_p), ("target", C.c_void_p), ("grad", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t),
+        ("pred_dtype", C.c_int32), ("target_dtype", C.c_int32), ("grad_dtype", C.c_int32), ("mode", C.c_int32),
+        ("B", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("clamp", C.c_int32), ("reserved", C.c_int32),
+        ("l1_weight", C.c_double), ("l2_weight", C.c_double), ("ssim_weight", C.c_double),
+        ("pred_stride", I64x4), ("target_stride", I64x4), ("grad_stride", I64x4),
+    ]
+
+
 class StemConv0Args(C.Structure):
     _fields_ = [
         ("image", C.c_void_p), ("y", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("stats_out", C.c_void_p),
@@ -258,6 +273,8 @@ SIGNATURES = {
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
     "naf_feature_inv_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
+    "naf_denoise_workspace_bytes": (C.c_size_t, [C.POINTER(DenoiseArgs)]),
+    "naf_denoise_objective": (C.c_int, [C.POINTER(DenoiseArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

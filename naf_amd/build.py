@@ -25,8 +25,9 @@ VGPR_FORM = ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]
 NO_VGPR_FORM = {"stem_conv.hip"}
 # Per-file flags.  stem_conv.hip: the schedule's GroupNorm / SiLU / sums arithmetic is written as plain f32 operations on purpose
 # -- a packed v_pk_*_f32 beside an MFMA stalls the matrix pipe ~16 cycles (profiles/r03_mfma_filler_prices.txt) -- and the SLP
-# vectoriser would pack adjacent ones again.
-EXTRA_FLAGS = {"stem_conv.hip": ["-fno-slp-vectorize"]}
+# vectoriser would pack adjacent ones again.  denoise.hip: its fused multiply-adds are written out; with the compiler's own contraction
+# off, expressions that are symmetric in pred and target round symmetrically (the SSIM gradient of identical windows is exactly zero).
+EXTRA_FLAGS = {"stem_conv.hip": ["-fno-slp-vectorize"], "denoise.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc() -> str:

@@ -11,6 +11,8 @@ Reference counterparts (paths relative to the reference repo):
   xna_forward        legacy_attention / na2d                            src/layers/attentions.py:16-29,72
   xna_head_forward   the same with the probe's 1x1 convolution folded in  evaluation/eval_seg_probing.py:56,104-111
   propagate_labels   label_propagation after feature extraction          evaluation/eval_video_seg.py:499-561
+  denoising_loss     DenoisingLoss.forward and its backward               denoising.py:129-177
+  denoising_metrics  MetricsCalculator.calculate_batch_metrics            denoising.py:61-126,302
 """
 from __future__ import annotations
 
@@ -1627,3 +1629,138 @@ def propagate_labels(target, context, segs, radius: int = 12, topk: int = 5, tem
         rc = lib.naf_propagate_fwd(C.byref(a), _stream(out))
     _lib.check(rc, "naf_propagate_fwd")
     return out
+
+
+# ---- denoising objective (denoising.py:61-177) ------------------------------------------------------------------------------------
+def _denoise_check(who: str, pred, target) -> None:
+    """Host-only checks, before any device work: TypeError for non-tensors and dtypes the kernel does not read, ValueError for shapes."""
+    for name, t in (("pred", pred), ("target", target)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"naf_amd.{who}: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype not in _DT:
+            raise TypeError(f"naf_amd.{who}: `{name}` must be a float32 or bfloat16 tensor, got {t.dtype}")
+    if pred.dim() != 4 or tuple(pred.shape) != tuple(target.shape):
+        raise ValueError(f"naf_amd.{who}: pred and target must be [B, C, H, W] of one shape, got {tuple(pred.shape)} and {tuple(target.shape)}")
+    if min(pred.shape) < 1:
+        raise ValueError(f"naf_amd.{who}: empty input {tuple(pred.shape)}")
+    if target.requires_grad:
+        raise ValueError(f"naf_amd.{who}: `target` requires grad; the objective is differentiable with respect to `pred` only")
+
+
+def _denoise_weights(who: str, l1_weight, l2_weight, ssim_weight) -> Tuple[float, float, float]:
+    try:
+        w = (float(l1_weight), float(l2_weight), float(ssim_weight))
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"naf_amd.{who}: the weights must be numbers: {e}") from e
+    if not all(v >= 0.0 for v in w):
+        raise ValueError(f"naf_amd.{who}: l1_weight, l2_weight and ssim_weight must not be negative, got {w}")
+    return w
+
+
+def denoise_objective(pred: torch.Tensor, target: torch.Tensor, weights=(1.0, 1.0, 0.1), *, grad: bool = False, metrics: bool = False,
+                      clamp: bool = False) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """naf_denoise_objective: the tile launch plus the finishing launch.  Returns ``(out, grad_map)``: ``out`` is the entry's fp32 ``[8]``
+    result vector (include/naf_hip.h: loss mode ``mean|p-t|, mean (p-t)^2, mean S, l1, l2, ssim, total, 0``; metrics mode ``psnr, ssim,
+    mse, 0...``) and ``grad_map`` the gradient of ``total`` with respect to ``pred`` when ``grad`` is set -- in ``pred``'s dtype, with
+    ``pred``'s strides when ``pred`` is dense in either memory format and contiguous otherwise -- else ``None``.  Nothing here is recorded
+    by autograd."""
+    who = "denoise_objective"
+    _denoise_check(who, pred, target)
+    w = _denoise_weights(who, *weights)
+    if metrics and grad:
+        raise ValueError(f"naf_amd.{who}: the metrics are forward only")
+    _gpu(pred, "pred")
+    _gpu(target, "target")
+    if pred.device != target.device:
+        raise ValueError(f"naf_amd.{who}: pred is on {pred.device}, target on {target.device}")
+    pred, target = pred.detach(), target.detach()
+    dev = pred.device
+    lib = _lib.load()
+    a = _lib.DenoiseArgs()
+    a.B, a.C, a.H, a.W = (int(v) for v in pred.shape)
+    a.mode = _lib.DENOISE_METRICS if metrics else _lib.DENOISE_LOSS
+    a.clamp = int(bool(clamp))
+    a.pred_dtype, a.target_dtype = _DT[pred.dtype], _DT[target.dtype]
+    a.l1_weight, a.l2_weight, a.ssim_weight = w
+    a.pred_stride, a.target_stride = _strides4(pred, (0, 1, 2, 3)), _strides4(target, (0, 1, 2, 3))
+    nbytes = int(lib.naf_denoise_workspace_bytes(C.byref(a)))
+    if nbytes == 0:
+        raise ValueError(f"naf_amd.{who}: {tuple(pred.shape)} is not a valid shape")
+    out = torch.empty(8, dtype=torch.float32, device=dev)
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    gmap = torch.empty_like(pred) if grad else None            # preserve_format: pred's strides when dense, contiguous otherwise
+    a.pred, a.target, a.out = pred.data_ptr(), target.data_ptr(), out.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+    if gmap is not None:
+        a.grad, a.grad_dtype, a.grad_stride = gmap.data_ptr(), _DT[gmap.dtype], _strides4(gmap, (0, 1, 2, 3))
+    with torch.cuda.device(dev), _Timed("denoise_metrics" if metrics else "denoise_loss"):
+        rc = lib.naf_denoise_objective(C.byref(a), _stream(out))
+    _lib.check(rc, "naf_denoise_objective")
+    return out, gmap
+
+
+class DenoiseLossFunction(torch.autograd.Function):
+    """``total`` of the denoising loss: the forward writes the gradient map in the same launch, the backward scales it."""
+
+    @staticmethod
+    def forward(ctx, pred, target, w1, w2, w3):
+        out, gmap = denoise_objective(pred, target, (w1, w2, w3), grad=ctx.needs_input_grad[0])
+        if gmap is not None:
+            ctx.save_for_backward(gmap)
+        ctx.mark_non_differentiable(out)
+        return out[6], out
+
+    @staticmethod
+    def backward(ctx, g_total, _g_out):
+        (gmap,) = ctx.saved_tensors
+        return gmap * g_total, None, None, None, None
+
+
+def denoising_loss(pred: torch.Tensor, target: torch.Tensor, l1_weight: float = 1.0, l2_weight: float = 1.0,
+                   ssim_weight: float = 0.1) -> Dict[str, torch.Tensor]:
+    """The reference's ``DenoisingLoss.forward`` (denoising.py:161-177) in one kernel launch plus a finishing launch: the dict
+    ``{"l1", "l2", "ssim", "total"}`` of 0-dim fp32 device tensors, each term already multiplied by its weight, a key present only where
+    its weight is > 0, ``total`` their sum.  ``ssim`` is ``ssim_weight * (1 - mean S)`` over zero-padded 3 x 3 windows.
+
+    Only ``total`` carries a gradient, and only to ``pred``: the three terms are detached (the reference's loop only logs them).  The
+    gradient map is written by the forward launch when ``pred`` requires grad; ``backward`` multiplies it by the incoming scalar.
+    ``pred`` and ``target`` are ``[B, C, H, W]``, fp32 or bf16 independently, any strides; all arithmetic is fp32.  A ``target`` that
+    requires grad raises ``ValueError``; CPU tensors raise ``RuntimeError`` (no fallback)."""
+    who = "denoising_loss"
+    _denoise_check(who, pred, target)
+    w = _denoise_weights(who, l1_weight, l2_weight, ssim_weight)
+    _gpu(pred, "pred")
+    _gpu(target, "target")
+    if not any(v > 0.0 for v in w):
+        return {"total": torch.zeros((), dtype=torch.float32, device=pred.device)}
+    if pred.requires_grad and torch.is_grad_enabled():
+        total, out = DenoiseLossFunction.apply(pred, target, *w)
+    else:
+        out, _ = denoise_objective(pred, target, w)
+        total = out[6]
+    losses = {name: out[3 + i] for i, name in enumerate(("l1", "l2", "ssim")) if w[i] > 0.0}
+    losses["total"] = total
+    return losses
+
+
+class DenoisingLoss(torch.nn.Module):
+    """Drop-in for the reference's ``DenoisingLoss`` (denoising.py:129-177): same constructor and call, served by ``denoising_loss``."""
+
+    def __init__(self, l1_weight=1.0, l2_weight=1.0, ssim_weight=0.1):
+        super().__init__()
+        self.l1_weight = l1_weight
+        self.l2_weight = l2_weight
+        self.ssim_weight = ssim_weight
+
+    def forward(self, pred, target):
+        return denoising_loss(pred, target, self.l1_weight, self.l2_weight, self.ssim_weight)
+
+
+def denoising_metrics(pred: torch.Tensor, target: torch.Tensor, clamp: bool = False) -> Dict[str, torch.Tensor]:
+    """The reference's ``MetricsCalculator.calculate_batch_metrics`` (denoising.py:64-126): ``{"psnr", "ssim"}`` as 0-dim fp32 device
+    tensors -- PSNR in dB (``+inf`` for identical inputs), SSIM through the zero-padded 11 x 11 Gaussian window.  ``clamp=True`` folds the
+    ``torch.clamp(pred, 0, 1)`` in front of it (denoising.py:302).  No host synchronisation happens here; ``.item()`` is the caller's."""
+    who = "denoising_metrics"
+    _denoise_check(who, pred, target)
+    out, _ = denoise_objective(pred, target, (0.0, 0.0, 0.0), metrics=True, clamp=clamp)
+    return {"psnr": out[0], "ssim": out[1]}
