@@ -620,9 +620,9 @@ struct StreamJoin {
     }
 };
 struct FwdLayout {
-    size_t stats, steal, buf0, buf1, buf2, buf3, cat, guide, keys, vp, q, idx_y, idx_x, total;
+    size_t stats, buf0, buf1, buf2, buf3, cat, guide, keys, vp, q, idx_y, idx_x, total;
     size_t total_one;   // bytes a ONE-stream forward touches (everything but buf3)
-    size_t zeroed;   // bytes from `stats` the forward's one memset clears: the GroupNorm sums and the attention's claim words behind them
+    size_t zeroed;   // bytes from `stats` the forward's one memset clears: the GroupNorm sums
     bool fused;   // rotate-on-load: the attention kernel reads the un-rotated guidance, no query buffer
     bool pooled;  // image larger than the output: `guide` = adaptive-average-pooled `cat` (naf.py:34), else guide == cat
     int Ho, Wo;   // output size
@@ -645,7 +645,6 @@ FwdLayout fwd_layout(const naf_forward_args* a) {
     L.img = off;
     if (L.shrunk) off = align256(off + px * 3 * sizeof(float));
     L.stats = off; off = align256(off + (size_t)2 * (a->nlayer + 1) * NAF_STATS_SLOTS * a->B * 16 * sizeof(double));
-    L.steal = off; off = align256(off + (size_t)NAF_XNA_STEAL_WORDS * sizeof(uint32_t));   // xna_slide_kernel.h: tail hand-over flags
     L.zeroed = off - L.stats;
     L.buf0 = off;  off = align256(off + px * 128 * 2);
     L.buf1 = off;  off = align256(off + px * 128 * 2);
@@ -863,7 +862,7 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
     // kernel of the 1x1 branch, zeroed the buffers and kept its own sums as per-workgroup partials: G2-k7 0.612-0.615 ms against
     // 0.601-0.603 with the memset, 256^2 0.2448 against 0.2434, interleaved; profiles/r05_negative_results.txt.  The fill kernel
     // overlaps the tail of whatever ran before; the kernel that replaced it did not.)
-    if (hipMemsetAsync(stats, 0, L.zeroed, s) != hipSuccess) {      // the sums and, right behind them, the attention's claim words
+    if (hipMemsetAsync(stats, 0, L.zeroed, s) != hipSuccess) {
         naf_set_error("naf_forward: hipMemsetAsync failed");
         return NAF_ERR_LAUNCH;
     }
@@ -895,10 +894,10 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
     // key-pooling pass follows a 3x3 layer.  The whole forward runs on the package's power cap; alternating the
     // memory-heavy and the matrix-heavy kernels measured 1.5 % faster than one branch after the other (same kernels, bit-identical
     // output; NAF_STEM_ORDER=0 with NAF_HIP_KNOBS=1 restores the sequential order).  Three rotating activation buffers.
-    static const bool sequential = [] { const char* e = naf_knob("NAF_STEM_ORDER"); return e && atoi(e) == 0; }();
+    const bool sequential = fwd_sequential();
     naf_stem_conv0_args c0s[2];
     // first convolution of branch br into y (NULL: statistics only -- the 1x1 branch's first block layer recomputes it)
-    naf_stream_t lstream = stream;   // the stream run_conv0 / run_layer launch on (two-stream mode switches it per branch)
+    naf_stream_t lstream = stream;   // the stream run_layer launches on: the second stream for the HBM-bound branch's block layers in two-stream mode
     auto run_conv0 = [&](int br, void* y) -> int {
         const naf_stem_branch& b = a->branch[br];
         naf_stem_conv0_args& c0 = c0s[br];
@@ -909,7 +908,7 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
         c0.y = y;
         for (int i = 0; i < 3; ++i) c0.y_stride[i] = dense[i];
         c0.flags = (flags & NAF_FWD_CONV0_EXACT) ? NAF_CONV0_EXACT : 0;
-        return naf_stem_conv0_fwd(&c0, lstream);
+        return naf_stem_conv0_fwd(&c0, stream);
     };
     // Key pooling rides on the branches' LAST layers (naf_stem_conv_keys_fwd: axial RoPE split, no pass over the guidance) when
     // every query is rotated on load, the guidance is not pooled, the cells are 16 x 16 pixels and the RoPE heads are 64 wide;
@@ -982,24 +981,18 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
             if (prc != NAF_OK) return prc;
             values_packed = true;
         }
-        // Both first convolutions on the caller's stream, the fork behind them.  Measured against the alternative (NAF_STEM_FORK_EARLY=1,
-        // A/B knob): each branch on one stream from its first convolution on, so that the 1x1 branch's statistics kernels and first
-        // layer run beside the 3x3 first convolution -- 1.923-1.927 ms against 1.907-1.909 per step (interleaved): the two
-        // write-heavy kernels slow each other down by more than the overlap brings.
-        static const bool fork_late = [] { const char* e = naf_knob("NAF_STEM_FORK_EARLY"); return !(e && atoi(e) != 0); }();
+        // Both first convolutions on the caller's stream, the fork behind them.  Each branch on one stream from its first convolution on
+        // measured 1 % slower per step (the two write-heavy kernels slow each other down by more than the overlap brings), and not even
+        // the statistics-only first convolution gains from the second stream; nor does swapping the streams of the block layers below
+        // (profiles/r04_negative_results.txt).
         for (int k = 0; k < 2; ++k) {
             const int br = k == 0 ? first : 1 - first;
-            // Not even the statistics-only first convolution (the image's moments: two small kernels, 18 us) gains from the second
-            // stream (NAF_STEM_MOMENTS_AUX=1, A/B knob): G1 1.924-1.925 against 1.904-1.907 ms, G2 the same (profiles/r04_negative_results.txt)
-            static const bool moments_aux = [] { const char* e = naf_knob("NAF_STEM_MOMENTS_AUX"); return e && atoi(e) != 0; }();
-            lstream = (k == 0 && (!fork_late || (rec[br] && moments_aux))) ? static_cast<naf_stream_t>(axs) : stream;
             cur[br] = rec[br] ? nullptr : pp[br][0];
             const int rc = run_conv0(br, cur[br]);
-            lstream = stream;
             if (rc != NAF_OK) return rc;
         }
         if (!mark(1)) return NAF_ERR_LAUNCH;      // behind the caller's stream's first convolution(s)
-        if (fork_late && (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(axs, ev_fork, 0) != hipSuccess)) {
+        if (hipEventRecord(ev_fork, s) != hipSuccess || hipStreamWaitEvent(axs, ev_fork, 0) != hipSuccess) {
             (void)hipGetLastError();
             naf_set_error("naf_forward: stream fork failed");
             return NAF_ERR_LAUNCH;
@@ -1007,10 +1000,7 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
         for (int l = 0; l < a->nlayer; ++l)
             for (int k = 0; k < 2; ++k) {
                 const int br = k == 0 ? first : 1 - first;
-                // A/B knob: the 1x1 branch on the caller's stream, the 3x3 branch on the second one (so that the stem ends on the caller's
-                // stream and the attention kernel does not wait for a cross-queue signal): G1 +0.3 %, G2 -1 % -- not adopted
-                static const bool swap_streams = [] { const char* e = naf_knob("NAF_STEM_SWAP"); return e && atoi(e) != 0; }();
-                lstream = ((k == 0) != swap_streams) ? static_cast<naf_stream_t>(axs) : stream;
+                lstream = k == 0 ? static_cast<naf_stream_t>(axs) : stream;
                 void* y = (l == a->nlayer - 1) ? nullptr : pp[br][cur[br] == pp[br][0] ? 1 : 0];
                 if (l == timed && k == 1 && !mark_on(2, s)) return NAF_ERR_LAUNCH;
                 const int rc = run_layer(br, l, cur[br], y);
@@ -1100,15 +1090,7 @@ int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32
         naf_set_error("naf_forward: hipEventRecord failed");
         return NAF_ERR_LAUNCH;
     }
-    {   // naf_xna_fwd(&x, stream), with the forward's zeroed claim words lent to the sliding-window kernel
-        const int sel = naf_xna_select(&x);
-        if (sel < 0) return -sel;
-        if (sel == NAF_XNA_MFMA) {
-            rc = naf_launch_xna_mfma(&x, xna_scale(x.scale, x.Dq), s, reinterpret_cast<uint32_t*>(ws + L.steal));
-        } else {
-            rc = naf_xna_fwd(&x, stream);
-        }
-    }
+    rc = naf_xna_fwd(&x, stream);
     if (rc != NAF_OK) return rc;
     if (a->events[1] && hipEventRecord(static_cast<hipEvent_t>(a->events[1]), s) != hipSuccess) {
         naf_set_error("naf_forward: hipEventRecord failed");

@@ -552,8 +552,7 @@ int naf_launch_stem_conv0_wgrad(const naf_stem_conv0_wgrad_args* a, hipStream_t 
     p.cw_log2 = p.C <= 64 ? 6 : (p.C <= 128 ? 7 : 8);
     for (int i = 0; i < 3; ++i) p.dys[i] = a->dy_stride[i];
     for (int i = 0; i < 4; ++i) p.is[i] = a->image_stride[i];
-    static const bool v1 = [] { const char* e = naf_knob("NAF_CONV0_WGRAD_V1"); return e && atoi(e) != 0; }();   // A/B knob: the scalar kernel
-    if (!v1 && p.C >= 32) {
+    if (p.C >= 32) {      // the matrix-pipe kernel; narrower layers: the scalar kernel below
         const int CP = (p.C + 31) & ~31, IW = 32 + 2 * (a->ksize / 2) + 2;
         size_t lds = (size_t)2 * 32 * (CP + 32) * 2 + (size_t)2 * a->ksize * 3 * IW * 4;
         const size_t redb = (size_t)(3 * a->ksize * a->ksize + 1) * CP * 4;

@@ -576,8 +576,7 @@ int naf_launch_stem_wgrad(const naf_stem_wgrad_args* a, hipStream_t s) {
     p.nranges = 0;
     const bool act = a->stats_in != nullptr;
     // the pipelined kernel: rows of at least one segment whose last segment holds its own reflection pixel (W mod 32 not in 1 .. 3)
-    static const bool v1 = [] { const char* e = naf_knob("NAF_WGRAD_V1"); return e && atoi(e) != 0; }();   // A/B knob
-    if (!v1 && a->W >= SEG && !((a->W % SEG) >= 1 && (a->W % SEG) <= 3) && a->H >= 2) {
+    if (a->W >= SEG && !((a->W % SEG) >= 1 && (a->W % SEG) <= 3) && a->H >= 2) {
         if (a->ksize == 3) return act ? stem_wgrad2_launch<3, true>(p, a, s) : stem_wgrad2_launch<3, false>(p, a, s);
         return act ? stem_wgrad2_launch<1, true>(p, a, s) : stem_wgrad2_launch<1, false>(p, a, s);
     }

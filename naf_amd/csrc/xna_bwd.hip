@@ -1,5 +1,5 @@
-// Eligibility + dispatcher of the attention backward (see xna_bwd_kernel.h).
-#include "xna_bwd_kernel.h"
+// Eligibility + dispatcher of the attention backward (mathematics: xna_bwd_params.h; the cell kernel: xna_bwd2_kernel.h).
+#include "xna_bwd2_kernel.h"
 
 #define NAF_DECL(K) int naf_xna_bwd_launch_k##K(const XnaBwdParams& p, int Dv, hipStream_t s); \
     int naf_xna_bwd_scores_launch_k##K(const XnaBwdScoresParams& p, int Dv, hipStream_t s);
@@ -10,32 +10,43 @@ static bool bwd_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) 
 
 // Value channels per launch.  A window whose K / V tiles, round buffers or accumulators do not fit at the full Dv is served in CHANNEL CHUNKS:
 // the softmax depends on q and k only, dV splits by channel, and dQ / dK are sums over channels of V -- so the backward for a slice of V
-// (and of dO) is a complete backward, and the slices' dQ / dK add up (XnaBwdParams::dq_accum; dK through the atomics).  The chunk is what the EIGHT-wave
-// kernel (xna_bwd2_kernel.h, more than twice as fast per channel as the four-wave one) takes at the window: 11 x 11 up to 128 channels (Dv 192 = 96 + 96,
-// 256 = 128 + 128; the four-wave kernel would fit the whole head), 13 x 13 and 15 x 15 (BASELINE configs[2]'s largest window) up to 64 -- twelve / sixteen
-// key tiles of S^T / dP^T leave its query waves no room for more, and at 15 x 15 the LDS is full (163.1 of 163.8 KB).  The four-wave kernel's chunks (NAF_BWD_BIG8=0): 128 / 64, 15 x 15 in the swept S / dP
-// form of xna_bwd_kernel.h.  0 = whole Dv.
-static int bwd_chunk_limit(int ks) {
-    // NAF_BWD_CHUNK11=0 (with NAF_HIP_KNOBS=1): 11 x 11 whole on the four-wave kernel, as before the chunks (A/B measurements)
-    static const bool whole11 = [] { const char* e = naf_knob("NAF_BWD_CHUNK11"); return e != nullptr && atoi(e) == 0; }();
-    // 13 x 13 / 15 x 15: chunks of 64 on the eight-wave kernel (NAF_BWD_BIG8=0 with NAF_HIP_KNOBS=1: 128 / 64 on the four-wave one, the first form --
-    // 11-33 % slower, profiles/r05_bwd_large_windows.txt)
-    static const bool big8 = [] { const char* e = naf_knob("NAF_BWD_BIG8"); return !(e != nullptr && atoi(e) == 0); }();
-    // NAF_BWD_K15_C32=1: 15 x 15 in chunks of 32 on the eight-wave kernel, the form before its P / dS rows were cut to 240 slots (A/B)
-    static const bool k15c32 = [] { const char* e = naf_knob("NAF_BWD_K15_C32"); return e != nullptr && atoi(e) != 0; }();
-    return ks >= 15 ? (big8 && k15c32 ? 32 : 64) : ks >= 13 ? (big8 ? 64 : 128) : (ks >= 11 && !whole11) ? 128 : 0;
-}
-static int bwd_next_chunk(int ks, int dv, int left) {
+// (and of dO) is a complete backward, and the slices' dQ / dK add up (XnaBwdParams::dq_accum; dK through the atomics).  The chunk is what the
+// cell kernel takes at the window: 11 x 11 up to 128 channels (Dv 192 = 96 + 96, 256 = 128 + 128), 13 x 13 and 15 x 15 (BASELINE configs[2]'s
+// largest window) up to 64 -- twelve / sixteen key tiles of S^T / dP^T leave its query waves no room for more, and at 15 x 15 the LDS is full
+// (163.1 of 163.8 KB; profiles/r05_bwd_large_windows.txt).  0 = whole Dv.
+static constexpr int bwd_chunk_limit(int ks) { return ks >= 13 ? 64 : ks >= 11 ? 128 : 0; }
+static constexpr int bwd_next_chunk(int ks, int dv, int left) {
     const int lim = bwd_chunk_limit(ks);
     if (lim == 0 || dv <= lim) return left;
     const int n = (dv + lim - 1) / lim;                   // equal chunks where they are multiples of 32 (192 = 96 + 96: the 64-channel
-    if (dv % n == 0 && (dv / n) % 32 == 0) return dv / n; // instantiation of the eight-wave kernel at 11 x 11 carries 3 registers of scratch)
+    if (dv % n == 0 && (dv / n) % 32 == 0) return dv / n; // instantiation of the cell kernel at 11 x 11 carries 3 registers of scratch)
     return left < lim ? left : lim;
 }
 
+// Every chunk width the plan above emits, for every window and every Dv the backward takes, is a width the cell kernel is built for at that
+// window (xna_bwd2_serves: registers and LDS) -- so eligibility below needs no LDS test and the launchers no fall-back.
+template <int KS>
+static constexpr bool bwd_chunk_served(int dvc) {
+    return dvc == 32 ? xna_bwd2_serves<KS, 32>() : dvc == 64 ? xna_bwd2_serves<KS, 64>() : dvc == 96 ? xna_bwd2_serves<KS, 96>()
+         : dvc == 128 ? xna_bwd2_serves<KS, 128>() : dvc == 192 ? xna_bwd2_serves<KS, 192>() : dvc == 256 ? xna_bwd2_serves<KS, 256>() : false;
+}
+template <int KS>
+static constexpr bool bwd_plan_served() {
+    for (const int dv : {32, 64, 96, 128, 192, 256})
+        for (int c0 = 0; c0 < dv;) {
+            const int dvc = bwd_next_chunk(KS, dv, dv - c0);
+            if (dvc <= 0 || !bwd_chunk_served<KS>(dvc)) return false;
+            c0 += dvc;
+        }
+    return true;
+}
+static_assert(bwd_plan_served<3>() && bwd_plan_served<5>() && bwd_plan_served<7>() && bwd_plan_served<9>() && bwd_plan_served<11>() &&
+                  bwd_plan_served<13>() && bwd_plan_served<15>(),
+              "the chunk plan emits a (window, channels per launch) combination xna_bwd2_kernel does not serve");
+
 // 1 when the cell kernel serves the request: the forward's MFMA conditions (square odd window 3..15, Dq = 64, integer
-// ratio, h, w >= window) plus row tiles (Wo/w % 16 == 0; up to 9 x 9 also 14, 15, 28, 30 ...), Dv in {32, 64, 96, 128, 192, 256} and K/V windows + round buffers
-// within 160 KB of LDS (all Dv up to k = 9 in one launch; wider heads at k = 11, 13 and 15 in channel chunks, above).
+// ratio, h, w >= window) plus row tiles (Wo/w % 16 == 0; up to 9 x 9 also 14, 15, 28, 30 ...) and Dv in {32, 64, 96, 128, 192, 256}
+// (all Dv up to k = 9 in one launch; wider heads at k = 11, 13 and 15 in channel chunks, above).
 int naf_xna_bwd_eligible(const naf_xna_bwd_args* a) {
     if (a->ky != a->kx) return 0;
     const int ks = a->ky;
@@ -51,7 +62,6 @@ int naf_xna_bwd_eligible(const naf_xna_bwd_args* a) {
         case 32: case 64: case 96: case 128: case 192: case 256: break;
         default: return 0;
     }
-    if (xna_bwd_lds_for(ks, bwd_next_chunk(ks, a->Dv, a->Dv)) > 160 * 1024) return 0;
     if (!bwd_aligned(a->q) || !bwd_aligned(a->k_lr) || !bwd_aligned(a->v_lr) || !bwd_aligned(a->dout) || !bwd_aligned(a->dq)) return 0;
     for (int i = 0; i < 4; ++i)
         if (a->q_stride[i] % 8 || a->k_stride[i] % 8 || a->v_stride[i] % 8 || a->dout_stride[i] % 8 || a->dq_stride[i] % 8) return 0;

@@ -1,12 +1,12 @@
 // Cross-scale neighbourhood attention BACKWARD, wave-specialised cell kernel (gfx950 / CDNA4), round 5.
 //
-// Same mathematics and the same operand tricks as xna_bwd_kernel.h, which this kernel replaces for EVERY window the cell backward serves
+// The mathematics is in xna_bwd_params.h.  This is the ONE cell kernel of the backward: it serves every window the cell backward takes
 // (dispatch, xna_bwd.hip: 3 x 3 ... 9 x 9 whole at every Dv; 11 x 11 whole up to Dv = 128 and in two channel chunks above; 13 x 13 and
-// 15 x 15 in channel chunks of <= 64; the four-wave kernel only behind the A/B knobs NAF_BWD_V1 / NAF_BWD_BIG8=0 / NAF_BWD_CHUNK11=0);
-// what changes is WHO does what and WHEN ("change the round
-// structure").  The four-wave kernel ran every wave through [S / dP MFMAs behind 32 LDS fragment reads, softmax, dQ, P / dS -> LDS |
-// barrier | dK / dV MFMAs | barrier]: all eight waves of a CU in the same phase at the same time, 1.7 k cycles of MFMAs in a
-// 10 k-cycle round (profiles/r02_xna_bwd_phase.txt).  Here one workgroup = EIGHT waves = one (batch, cell, head), and the waves have roles:
+// 15 x 15 in channel chunks of <= 64).  Its predecessor, a four-wave kernel (retired; 11-33 % to more than 2x slower,
+// profiles/r05_bwd2_ab.txt, profiles/r05_bwd_large_windows.txt), ran every wave through the same phases at the same time
+// ("change the round structure"):
+// 1.7 k cycles of MFMAs in a 10 k-cycle round (profiles/r02_xna_bwd_phase.txt).
+// Here one workgroup = EIGHT waves = one (batch, cell, head), and the waves have roles:
 //
 //   waves 0-3 ("query waves"): one 16-query row tile per round each.  They hold the cell's K and V windows as MFMA operand
 //       FRAGMENTS IN REGISTERS for the whole cell (32 + Dv/2 registers at k = 7: they carry no accumulators), so the 64 S / dP
@@ -17,9 +17,9 @@
 //
 // The round buffers are double: ONE barrier per round instead of two, and on every SIMD (a workgroup's waves w and w + 4 share
 // one) a wave in its VALU / store phase sits beside a wave in its MFMA phase.  Reference: what autograd runs through
-// attentions.py:16-29 in train.py:127-137 / test/backward_speed.py:22-69, as xna_bwd_kernel.h.
+// attentions.py:16-29 in train.py:127-137 / test/backward_speed.py:22-69, as xna_bwd_params.h.
 #pragma once
-#include "xna_bwd_kernel.h"
+#include "xna_bwd_params.h"
 
 // tools/xna_bwd2_probe.hip (-DNAF_BWD_TIMING): s_memtime stamps of a round are TAKEN where the phases change and only USED behind the
 // round's barrier (an s_memtime result is waited for with lgkmcnt(0), which would also drain the wave's LDS queue in mid-phase)
@@ -67,8 +67,8 @@ struct XnaBwd2Geom {
     static constexpr int v_res_mt = (v_budget / ((DV / 32) * 4)) < G::MT ? (v_budget / ((DV / 32) * 4)) : G::MT;
 };
 
-// CH: a CHANNEL CHUNK of a wider head (xna_bwd.hip: 11 x 11 beyond Dv = 128 runs as chunks of <= 128 on this kernel instead of whole on the four-wave
-// one): dV rows are p.dv_pitch channels apart instead of DV, and launches after the first add their dQ to what is there (p.dq_accum).  A
+// CH: a CHANNEL CHUNK of a wider head (xna_bwd.hip: 11 x 11 beyond Dv = 128 runs as chunks of <= 128, 13 x 13 and 15 x 15 as chunks
+// of <= 64): dV rows are p.dv_pitch channels apart instead of DV, and launches after the first add their dQ to what is there (p.dq_accum).  A
 // template parameter so that the whole-head instantiations keep their code (their query waves sit at 229-253 of 256 registers).
 // PT (round 6): PARTIAL row tiles -- cells whose rows are not a multiple of 16 pixels wide (the 14-pixel cells of patch-14 backbones, DINOv2's;
 // 15, 28, 30 ...: xna_row_tiles_ok, as in the forward): the last tile of a row holds fewer than 16 queries.  Its idle lanes load the row's last
@@ -454,7 +454,7 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParamsT<SG
 
                 // P and dS for the key waves: row-major [query][slot] -- a lane holds four consecutive slots of ITS query per key tile, one
                 // 8-byte store each; the key waves read them back transposed (ds_read_tr) as the A operands of the contractions over queries.
-                // (The four-wave kernel evaluated S and dP a second time with the operands swapped to get that layout out of the MFMA: 32
+                // (The retired four-wave kernel evaluated S and dP a second time with the operands swapped to get that layout out of the MFMA: 32
                 // more MFMAs, 16 more exponentials and a statistics exchange per tile.)
                 if constexpr (!SG) {
 #pragma unroll
@@ -843,8 +843,8 @@ __global__ __launch_bounds__(512, 2) void xna_bwd2_kernel(const XnaBwdParamsT<SG
 #endif
 }
 
-// Windows up to 9 x 9 whose buffers fit the LDS (all of them since the single P / dS buffer mode); everything else stays with the four-wave
-// kernel.  Where the whole window's V fragments do not fit beside a query wave's working set (7 x 7 at Dv = 256: 128 registers of them, hipcc 7.2
+// The (window, channels per launch) combinations this kernel is built for; the planner (xna_bwd.hip) emits no other -- a static_assert there.
+// Where the whole window's V fragments do not fit beside a query wave's working set (7 x 7 at Dv = 256: 128 registers of them, hipcc 7.2
 // spilled 50) the last key tile's come from the LDS in every round (v_res_mt): 253 registers, no scratch.
 template <int KS, int DV>
 constexpr bool xna_bwd2_serves() {
@@ -854,65 +854,63 @@ constexpr bool xna_bwd2_serves() {
 
 template <int KS, int DV, bool SG = false>
 static int xna_bwd2_launch_one(const XnaBwdParamsT<SG>& p, hipStream_t s) {
-    if constexpr (!xna_bwd2_serves<KS, DV>()) {
-        return xna_bwd_launch_one<KS, DV, SG>(p, s);
-    } else {
-        constexpr size_t lds = XnaBwd2Geom<KS, DV>::lds_bytes();
-        auto kern = xna_bwd2_kernel<KS, DV, false, false, SG>;
-        if ((p.dx & 15) != 0) {      // partial row tiles (patch-14 cells ...): windows up to 9 x 9, whole heads (naf_xna_bwd_eligible)
-            if constexpr (KS <= 9) {
-                if (p.dv_pitch == DV) kern = xna_bwd2_kernel<KS, DV, false, true, SG>;
-            }
-            if (KS > 9 || p.dv_pitch != DV) {
-                naf_set_error("xna_bwd2: cells of %d pixels per row (not a multiple of 16) need a window <= 9 x 9 and the whole head", p.dx);
-                return NAF_ERR_UNSUPPORTED;
-            }
-        } else
-        if constexpr ((KS == 11 && DV <= 128) || (KS == 13 && DV <= 64) || (KS == 15 && DV <= 64)) {
-            if (p.dv_pitch != DV) kern = xna_bwd2_kernel<KS, DV, true, false, SG>;     // a channel chunk of a wider head
-        } else if (p.dv_pitch != DV) {
-            naf_set_error("xna_bwd2: no channel-chunk instantiation for window %d, chunk %d of %d", KS, DV, p.dv_pitch);
+    static_assert(xna_bwd2_serves<KS, DV>(), "no cell kernel for this window at this many value channels per launch");
+    constexpr size_t lds = XnaBwd2Geom<KS, DV>::lds_bytes();
+    auto kern = xna_bwd2_kernel<KS, DV, false, false, SG>;
+    if ((p.dx & 15) != 0) {      // partial row tiles (patch-14 cells ...): windows up to 9 x 9, whole heads (naf_xna_bwd_eligible)
+        if constexpr (KS <= 9) {
+            if (p.dv_pitch == DV) kern = xna_bwd2_kernel<KS, DV, false, true, SG>;
+        }
+        if (KS > 9 || p.dv_pitch != DV) {
+            naf_set_error("xna_bwd2: cells of %d pixels per row (not a multiple of 16) need a window <= 9 x 9 and the whole head", p.dx);
             return NAF_ERR_UNSUPPORTED;
         }
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) {
-            naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
-            return NAF_ERR_LAUNCH;
-        }
-        // runs of cells: whole cell rows when they fill the chip evenly, otherwise the segment length with the least estimated time
-        // (a run costs its cells plus ~1.5 cells of window staging and final flush)
-        const int ncu = naf_cu_count();
-        const int64_t rows = (int64_t)p.B * p.h * p.heads;
-        int best_len = p.w;
-        double best = 1e300;
-        for (int len = p.w; len >= 1; --len) {
-            const int64_t runs = rows * ((p.w + len - 1) / len);
-            const double cost = (double)((runs + ncu - 1) / ncu) * (len + 1.5);
-            if (cost < best * 0.999) { best = cost; best_len = len; }
-        }
-        XnaBwdParamsT<SG> q = p;
-        q.seg_len = best_len;
-        q.nseg = (p.w + best_len - 1) / best_len;
-        const int64_t runs = rows * q.nseg;
-        q.nblocks = (uint32_t)runs;
-        hipLaunchKernelGGL(kern, dim3((unsigned)(runs < ncu ? runs : ncu)), dim3(512), lds, s, q);   // one resident workgroup per CU
-        return naf_check_launch("xna_bwd2_kernel");
+    } else
+    if constexpr ((KS == 11 && DV <= 128) || (KS == 13 && DV <= 64) || (KS == 15 && DV <= 64)) {
+        if (p.dv_pitch != DV) kern = xna_bwd2_kernel<KS, DV, true, false, SG>;     // a channel chunk of a wider head
+    } else if (p.dv_pitch != DV) {
+        naf_set_error("xna_bwd2: no channel-chunk instantiation for window %d, chunk %d of %d", KS, DV, p.dv_pitch);
+        return NAF_ERR_UNSUPPORTED;
     }
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) {
+        naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+        return NAF_ERR_LAUNCH;
+    }
+    // runs of cells: whole cell rows when they fill the chip evenly, otherwise the segment length with the least estimated time
+    // (a run costs its cells plus ~1.5 cells of window staging and final flush)
+    const int ncu = naf_cu_count();
+    const int64_t rows = (int64_t)p.B * p.h * p.heads;
+    int best_len = p.w;
+    double best = 1e300;
+    for (int len = p.w; len >= 1; --len) {
+        const int64_t runs = rows * ((p.w + len - 1) / len);
+        const double cost = (double)((runs + ncu - 1) / ncu) * (len + 1.5);
+        if (cost < best * 0.999) { best = cost; best_len = len; }
+    }
+    XnaBwdParamsT<SG> q = p;
+    q.seg_len = best_len;
+    q.nseg = (p.w + best_len - 1) / best_len;
+    const int64_t runs = rows * q.nseg;
+    q.nblocks = (uint32_t)runs;
+    hipLaunchKernelGGL(kern, dim3((unsigned)(runs < ncu ? runs : ncu)), dim3(512), lds, s, q);   // one resident workgroup per CU
+    return naf_check_launch("xna_bwd2_kernel");
 }
 
-// NAF_BWD_V1=1 (with NAF_HIP_KNOBS=1): the four-wave kernel for every shape (A/B measurements)
+// Dv: the value channels of the launch (a whole head or a channel chunk).  Only the widths the kernel serves at the window are instantiated.
 template <int KS, bool SG = false>
 static int xna_bwd2_launch_ks(const XnaBwdParamsT<SG>& p, int Dv, hipStream_t s) {
-    static const bool v1 = [] { const char* e = naf_knob("NAF_BWD_V1"); return e != nullptr && atoi(e) != 0; }();
-    if (v1 && (p.dx & 15) == 0) return xna_bwd_launch_ks<KS, SG>(p, Dv, s);      // (the four-wave kernel has whole row tiles only)
-    switch (Dv) {
-        case 32: return xna_bwd2_launch_one<KS, 32, SG>(p, s);
-        case 64: return xna_bwd2_launch_one<KS, 64, SG>(p, s);
-        case 96: return xna_bwd2_launch_one<KS, 96, SG>(p, s);
-        case 128: return xna_bwd2_launch_one<KS, 128, SG>(p, s);
-        case 192: return xna_bwd2_launch_one<KS, 192, SG>(p, s);
-        case 256: return xna_bwd2_launch_one<KS, 256, SG>(p, s);
+#define NAF_BWD2_CASE(D)                                                            \
+    if constexpr (xna_bwd2_serves<KS, D>()) {                                       \
+        if (Dv == D) return xna_bwd2_launch_one<KS, D, SG>(p, s);                   \
     }
-    naf_set_error("naf_xna_bwd: no kernel for Dv = %d (32, 64, 96, 128, 192, 256)", Dv);
+    NAF_BWD2_CASE(32)
+    NAF_BWD2_CASE(64)
+    NAF_BWD2_CASE(96)
+    NAF_BWD2_CASE(128)
+    NAF_BWD2_CASE(192)
+    NAF_BWD2_CASE(256)
+#undef NAF_BWD2_CASE
+    naf_set_error("naf_xna_bwd: no kernel for window %d with %d value channels per launch", KS, Dv);
     return NAF_ERR_UNSUPPORTED;
 }

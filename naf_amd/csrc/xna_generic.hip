@@ -140,7 +140,7 @@ int naf_launch_xna_generic(const naf_xna_args* a, float scale, hipStream_t s) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Table-driven BACKWARD (any sizes): what naf_xna_bwd runs when the MFMA cell kernel (xna_bwd_kernel.h) does not
+// Table-driven BACKWARD (any sizes): what naf_xna_bwd runs when the MFMA cell kernel (xna_bwd2_kernel.h) does not
 // serve the shapes.  One wave per (batch, head, query): recompute the scores and P, dP[key] = dO . v[key],
 // delta = sum P dP, dS = scale P (dP - delta); dq = sum_key dS k[key] is written, dk[key] += dS q and
 // dv[key] += P dO go to the fp32 accumulators with atomics.  Correctness path, not a speed path.

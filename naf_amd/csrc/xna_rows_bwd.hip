@@ -1,4 +1,4 @@
-// Cross-scale neighbourhood attention BACKWARD on the matrix cores for everything the cell kernel (xna_bwd_kernel.h) does not
+// Cross-scale neighbourhood attention BACKWARD on the matrix cores for everything the cell kernel (xna_bwd2_kernel.h) does not
 // serve with a square window: what autograd runs through legacy_attention (attentions.py:16-29) in
 //   * the reference's denoising loop (denoising.py:213,301 -- NAF(dim = 96 ... 512) on a 3-channel image: ratio 1, ONE head of
 //     dim up to 512, three value channels, window 15),
@@ -32,7 +32,7 @@
 // have a lane per stationary element holding 8 streamed slots -- which IS the A-operand layout of the second products
 // (contraction over the streamed slots).  Those need the streamed row transposed (B operand [slot][d] with a lane per d): the
 // fragments just loaded are also written to the wave's LDS segment [32 slots][D], and ds_read_b64_tr_b16 returns them
-// transposed (as xna_bwd_kernel.h does for the cell shapes).  No barrier: every wave works on its own segment.
+// transposed (as xna_bwd2_kernel.h does for the cell shapes).  No barrier: every wave works on its own segment.
 // NDV = Dv / 32 value k-steps; NDV = 0 is the few-channel form (Dv <= 32, any value: 2-byte gathers, one k-step).
 #include <type_traits>
 

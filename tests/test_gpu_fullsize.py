@@ -631,16 +631,6 @@ def _forward_hashes(cases, env_extra):
     return got
 
 
-def test_tail_handover_arm_of_the_sliding_kernel_is_bit_identical(dev):
-    """the sliding-window kernel's tail hand-over (xna_slide_kernel.h, STEAL: the last cells of every segment claimed
-    cell by cell, finished workgroups take other runs' unclaimed tail cells) was built, measured slower and left OFF
-    (profiles/r06_other_workloads.txt); it stays as an A/B arm behind NAF_XNA_STEAL=1.  Which workgroup computes a cell must not change a
-    single bit of it: G2-k11, a 13 x 13 window and a non-square grid with uneven segments (12, 12, 12, 10 cells) through the whole forward,
-    default vs the arm, in two processes."""
-    cases = ((512, 512, 32, 32, 1024, 11), (512, 512, 32, 32, 768, 13), (256, 736, 16, 46, 1024, 11))
-    assert _forward_hashes(cases, {"NAF_XNA_STEAL": "0"}) == _forward_hashes(cases, {"NAF_XNA_STEAL": "1"})
-
-
 def test_half_row_staging_of_the_cell_kernel_is_bit_identical(dev):
     """Round 6: where the whole-row store tiles of the cell kernel leave fewer than sixteen waves per CU in flight -- Dv = 256 at 7 x 7
     (BASELINE's G2 / G3 width), the reference's default 9 x 9 window at Dv = 192 / 256 -- the planner takes eight-wave workgroups with store

@@ -15,7 +15,7 @@ that the reference with those roundings stays inside each bound and that two pla
 n per kernel path, read from the sources:
   forward, out = sum_j P_j v_j                                                                                         n   stores
     cell      xna_mfma_kernel.h:625-629   s *= 1 / sum, then pf = (bf16_t) s: the normalised weight, once               1   fp32 0 / bf16 1 (:125-128)
-    sliding   xna_slide_kernel.h:360-364  the same two statements                                                        1   fp32 0 / bf16 1
+    sliding   xna_slide_kernel.h:341-345  the same two statements                                                        1   fp32 0 / bf16 1
     union     xna_union_kernel.h:281      pf = (bf16_t)(s * inv)                                                         1   fp32 0 / bf16 1 (:310-311)
     rows      xna_rows.hip:131-133        pa = (bf16_t) e with e = weight * exp2(s - running max): rounded BEFORE the     1   fp32 0 / bf16 1 (:166)
               division by the fp32 sum of the unrounded e (:135, :158); the running-max rescale (:151) is fp32

@@ -859,8 +859,7 @@ def test_cell_backward_fuzz_against_table_driven_kernel(dev):
     """Seeded random geometries of the MFMA cell backward -- every window 3 .. 15, every Dv (13 x 13 and 15 x 15 in channel chunks), row-tile counts that are not multiples of the
     four tiles of a round (dead query waves), one-row cells, several images and heads -- against the independent scalar table-driven
     kernel (fp32 throughout) on the same bf16 inputs.  Every window runs the wave-specialised eight-wave kernel (xna_bwd2_kernel.h: query
-    waves / key waves): 3 ... 11 whole (11 x 11 beyond Dv = 128 in two chunks), 13 x 13 / 15 x 15 in channel chunks of <= 64; the four-wave
-    kernel of xna_bwd_kernel.h only behind the A/B knobs NAF_BWD_V1 / NAF_BWD_BIG8=0 / NAF_BWD_CHUNK11=0."""
+    waves / key waves): 3 ... 11 whole (11 x 11 beyond Dv = 128 in two chunks), 13 x 13 / 15 x 15 in channel chunks of <= 64 (xna_bwd.hip)."""
     from naf_amd import ops
     seed, want = int(os.environ.get("NAF_FUZZ_BWD_SEED", "9753")), int(os.environ.get("NAF_FUZZ_BWD_CASES", "70"))   # campaigns: profiles/r05_fuzz_backward.txt
     rng = np.random.RandomState(seed)
@@ -1453,6 +1452,7 @@ def test_full_forward_odd_shapes_match_oracle(dev, img_hw, lr, C, ksz):
     (1, 1024, (15, 17), (240, 272), 15, torch.bfloat16),   # 15x15, Dv = 256: 155 KB window, 8 waves
     (1, 1024, (12, 13), (192, 208), 11, torch.bfloat16),   # 11x11, Dv = 256: stores staged 128 channels at a time (round 4)
     (2, 1024, (13, 14), (208, 448), 13, torch.bfloat16),   # 13x13, Dv = 256: staged 64 channels at a time, dx = 32, two images
+    (1, 1024, (16, 46), (256, 736), 11, torch.bfloat16),   # 11x11 on a non-square grid: segments of 12, 12, 12, 10 cells, the ring turns right round
 ])
 def test_sliding_window_kernel_matches_oracle(dev, B, C, lr, out_sz, ksz, out_dtype):
     """xna_slide_kernel (plans without staged stores): ring-of-columns window, per-cell column refresh, segment borders."""
