@@ -65,7 +65,8 @@ extern "C" {
  * cross-entropy / argmax epilogue (naf_xna_head_ce_args, which embeds naf_xna_head_args unchanged); and after those naf_xna_head_cm_select /
  * naf_xna_head_cm_fwd -- that epilogue counting into a confusion matrix (naf_xna_head_cm_args, which embeds naf_xna_head_ce_args unchanged); and after
  * those naf_propagate_select / naf_propagate_fwd / naf_feature_inv_norm -- label propagation for video evaluation (naf_propagate_args); and after
- * those naf_denoise_objective / naf_denoise_workspace_bytes -- the denoising loss with its gradient, and the PSNR / SSIM metrics (naf_denoise_args). */
+ * those naf_denoise_objective / naf_denoise_workspace_bytes -- the denoising loss with its gradient, and the PSNR / SSIM metrics (naf_denoise_args); and after
+ * those naf_feature_moments (+ _workspace_bytes, _plan) / naf_pca_project (+ _workspace_bytes) / naf_pca_minmax -- feature PCA for display. */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -664,6 +665,87 @@ typedef struct naf_denoise_args {
 } naf_denoise_args;
 size_t naf_denoise_workspace_bytes(const naf_denoise_args* a);
 int naf_denoise_objective(const naf_denoise_args* a, naf_stream_t stream);
+
+/* ---- feature PCA for display: second moments, projection, min-max (added after the denoising entries; detect by symbol) ----
+ * The device side of the reference's pca() (utils/visualization.py:135-190: every map copied to the host, torch.pca_lowrank(niter=20) on the
+ * CPU, a projection on three components, a min-max per component).  Here the fit needs the Gram matrix and the channel sums of each map
+ * (naf_feature_moments; the C x C eigen-decomposition is the caller's), a map's picture is its projection (naf_pca_project) scaled by the
+ * minima and maxima the same call returns.  A projection that came out of the head kernel (naf_xna_head_fwd with weight = V^T and
+ * bias = -mean V) gets its minima and maxima from naf_pca_minmax.
+ *
+ * A map is P rows ("pixels") of C contiguous bf16 values -- dense channels-last memory, what naf_forward writes -- at a constant row stride
+ * `ld` in elements, ld >= C and ld % 8 == 0, base pointer 16-byte aligned.  Served: C % 32 == 0 and 32 <= C <= NAF_PCA_MAX_C, any
+ * 1 <= P < 2^31, 1 <= n <= NAF_PCA_MAX_COMPONENTS.  Inputs are assumed finite.
+ *
+ * naf_feature_moments:   gram[i][j] = sum_p x[p][i] x[p][j]  (fp64 [C][C], the FULL matrix: gram[i][j] and gram[j][i] are the same bits)
+ *                        sum[i]     = sum_p x[p][i]          (fp64 [C])
+ * Summation contract.  The pixels are cut into `nsplit` slabs of `slab_pixels` consecutive pixels (the last one may be shorter;
+ * naf_feature_moments_plan names both numbers, from P and C alone).  A product x[p][i] x[p][j] of two bf16 values is exact in fp32.  Within a
+ * slab the products of one entry are added in fp32 on the matrix cores (v_mfma_f32_16x16x32_bf16 chains, pixels in order); the channel sums are
+ * products with 1.0 on the same path.  The slabs' fp32 partials go to `workspace`, and a finishing kernel adds them in fp64 in slab order.  So
+ * at most L = min(P, NAF_MOMENTS_CHAIN) fp32 additions lie between a product and the fp64 sum (slab_pixels <= NAF_MOMENTS_CHAIN always), the
+ * fp64 stage adds at most nsplit terms, and |gram[i][j] - exact| <= L 2^-24 sum_p |x[p][i] x[p][j]| to first order (likewise for sum).
+ * No floating-point atomics: two runs give the same bits.  An entry and its mirror image are written from one register.
+ * Slab count: the library aims at 512 workgroups (one per 128 x 128 block of the upper triangle and slab) with slabs of at least 256 pixels,
+ * keeps the workspace at or below NAF_MOMENTS_WORKSPACE_CAP bytes, and -- taking precedence over that cap -- never lets a slab exceed
+ * NAF_MOMENTS_CHAIN pixels.  (At C = 4096 a slab's partials are 34.6 MB, so the cap holds up to P = 7 * 65536 there; at C <= 2048 up to 2^21 pixels.)
+ *   workspace  device, naf_feature_moments_workspace_bytes(a) bytes, 16-byte aligned; contents need no initialisation
+ *
+ * naf_pca_project:       y[p][r] = b[r] + sum_c x[p][c] V[c][r],  r < n         V fp32 [C][n] dense, b fp32 [n], y fp32 [P][n] dense
+ *                        minmax[0][r] = min_p y[p][r], minmax[1][r] = max_p y[p][r]            fp32 [2][n]
+ * fp32 fused multiply-adds in a fixed order: lane k of the 16 lanes that share a pixel takes the 8-channel chunks k, k + 16, ... in ascending
+ * channel order, the 16 lane sums are added in a four-step butterfly, the bias comes last: at most C / 16 + 5 roundings per element.
+ * The minima and maxima are exact (of the y written).  Two launches: the projection with per-workgroup minima and maxima, a one-workgroup finish.
+ *   workspace  device, naf_pca_project_workspace_bytes(a) bytes (it reads P only; at most 64 KiB), 16-byte aligned; no initialisation needed
+ * naf_pca_minmax:        the same minima and maxima of an existing fp32 buffer y[p * ld + r], r < n, ld >= n in elements (so a [.., Npad] logits
+ *                        buffer of the head kernel is read in place).  workspace: as naf_pca_project_workspace_bytes says for the same P.
+ * Normalisation, (y - min) / (max - min) per component as visualization.py:166-167 does, is left to the caller (two elementwise operations); a
+ * constant component divides by zero there as it does in the reference.
+ * Argument checks happen before any HIP call: NAF_ERR_INVALID for NULL args or pointers, misaligned pointers, P, C or n <= 0, ld < C (ld < n) or
+ * ld % 8 != 0, a workspace that is too small, non-zero reserved; NAF_ERR_UNSUPPORTED, with the limit named in naf_last_error(), for C or n
+ * outside the served range.  The _workspace_bytes queries return 0 for arguments that are not valid.  naf_feature_moments_plan is host-only
+ * (it reads P, C, ld and reserved). Caller-owned memory, workspace and stream; nothing is allocated or kept; capturable. */
+#define NAF_MOMENTS_CHAIN 65536                        /* L: most fp32 additions between a product and the fp64 sum */
+#define NAF_MOMENTS_WORKSPACE_CAP ((size_t)256 << 20) /* bytes */
+#define NAF_PCA_MAX_C 4096
+#define NAF_PCA_MAX_COMPONENTS 8
+typedef struct naf_feature_moments_args {
+    const void* x; /* bf16 [P][ld] */
+    double* gram;  /* [C][C] */
+    double* sum;   /* [C] */
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t P, ld;
+    int32_t C;
+    int32_t reserved; /* must be 0 */
+} naf_feature_moments_args;
+size_t naf_feature_moments_workspace_bytes(const naf_feature_moments_args* a);
+int naf_feature_moments_plan(const naf_feature_moments_args* a, int32_t* nsplit, int32_t* slab_pixels);
+int naf_feature_moments(const naf_feature_moments_args* a, naf_stream_t stream);
+typedef struct naf_pca_project_args {
+    const void* x;  /* bf16 [P][ld] */
+    const float* V; /* [C][n] */
+    const float* b; /* [n] */
+    float* y;       /* [P][n] */
+    float* minmax;  /* [2][n] */
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t P, ld;
+    int32_t C, n;
+    int32_t reserved[2]; /* must be 0 */
+} naf_pca_project_args;
+size_t naf_pca_project_workspace_bytes(const naf_pca_project_args* a);
+int naf_pca_project(const naf_pca_project_args* a, naf_stream_t stream);
+typedef struct naf_pca_minmax_args {
+    const float* y; /* y[p * ld + r] */
+    float* minmax;  /* [2][n] */
+    void* workspace;
+    size_t workspace_bytes;
+    int64_t P, ld;
+    int32_t n;
+    int32_t reserved; /* must be 0 */
+} naf_pca_minmax_args;
+int naf_pca_minmax(const naf_pca_minmax_args* a, naf_stream_t stream);
 
 /* ---- cross-scale neighbourhood attention backward --------------------------------------------------
  * Replaces what autograd runs through legacy_attention (attentions.py:16-29: the backward of na2d_qk, the

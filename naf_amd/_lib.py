@@ -101,6 +101,35 @@ class DenoiseArgs(C.Structure):
     ]
 
 
+MOMENTS_CHAIN = 65536                           # NAF_MOMENTS_CHAIN: most fp32 additions between a product and the fp64 sum
+MOMENTS_WORKSPACE_CAP = 256 << 20               # NAF_MOMENTS_WORKSPACE_CAP
+PCA_MAX_C, PCA_MAX_COMPONENTS = 4096, 8
+
+
+class FeatureMomentsArgs(C.Structure):
+    """naf_feature_moments_args (added after the denoising entries, detected by symbol): Gram matrix and channel sums of one feature map."""
+    _fields_ = [
+        ("x", C.c_void_p), ("gram", C.c_void_p), ("sum", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("P", C.c_int64), ("ld", C.c_int64), ("C", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
+class PcaProjectArgs(C.Structure):
+    """naf_pca_project_args: a map's projection on n components with the components' minima and maxima."""
+    _fields_ = [
+        ("x", C.c_void_p), ("V", C.c_void_p), ("b", C.c_void_p), ("y", C.c_void_p), ("minmax", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t), ("P", C.c_int64), ("ld", C.c_int64), ("C", C.c_int32), ("n", C.c_int32), ("reserved", C.c_int32 * 2),
+    ]
+
+
+class PcaMinmaxArgs(C.Structure):
+    """naf_pca_minmax_args: minima and maxima of an existing fp32 projection."""
+    _fields_ = [
+        ("y", C.c_void_p), ("minmax", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("P", C.c_int64), ("ld", C.c_int64), ("n", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 class StemConv0Args(C.Structure):
     _fields_ = [
         ("image", C.c_void_p), ("y", C.c_void_p), ("weight", C.c_void_p), ("bias", C.c_void_p), ("stats_out", C.c_void_p),
@@ -275,6 +304,12 @@ SIGNATURES = {
     "naf_feature_inv_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "naf_denoise_workspace_bytes": (C.c_size_t, [C.POINTER(DenoiseArgs)]),
     "naf_denoise_objective": (C.c_int, [C.POINTER(DenoiseArgs), C.c_void_p]),
+    "naf_feature_moments_workspace_bytes": (C.c_size_t, [C.POINTER(FeatureMomentsArgs)]),
+    "naf_feature_moments_plan": (C.c_int, [C.POINTER(FeatureMomentsArgs), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "naf_feature_moments": (C.c_int, [C.POINTER(FeatureMomentsArgs), C.c_void_p]),
+    "naf_pca_project_workspace_bytes": (C.c_size_t, [C.POINTER(PcaProjectArgs)]),
+    "naf_pca_project": (C.c_int, [C.POINTER(PcaProjectArgs), C.c_void_p]),
+    "naf_pca_minmax": (C.c_int, [C.POINTER(PcaMinmaxArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -13,6 +13,7 @@ Reference counterparts (paths relative to the reference repo):
   propagate_labels   label_propagation after feature extraction          evaluation/eval_video_seg.py:499-561
   denoising_loss     DenoisingLoss.forward and its backward               denoising.py:129-177
   denoising_metrics  MetricsCalculator.calculate_batch_metrics            denoising.py:61-126,302
+  feature_moments / pca_project / pca_minmax  pca() and TorchPCA          utils/visualization.py:135-190
 """
 from __future__ import annotations
 
@@ -1764,3 +1765,159 @@ def denoising_metrics(pred: torch.Tensor, target: torch.Tensor, clamp: bool = Fa
     _denoise_check(who, pred, target)
     out, _ = denoise_objective(pred, target, (0.0, 0.0, 0.0), metrics=True, clamp=clamp)
     return {"psnr": out[0], "ssim": out[1]}
+
+
+# ---- feature PCA for display (include/naf_hip.h, "feature PCA for display") ----------------------------------------------------------
+def _pca_map_shape(x, who: str, name: str = "map"):
+    """(C, H, W) of one feature map given as [C, H, W] or [1, C, H, W]; TypeError / ValueError before any device work."""
+    if not torch.is_tensor(x):
+        raise TypeError(f"naf_amd.{who}: `{name}` must be a tensor, got {type(x).__name__}")
+    if x.dtype not in _DT:
+        raise TypeError(f"naf_amd.{who}: `{name}` must be a float32 or bfloat16 tensor, got {x.dtype}")
+    if x.dim() == 4:
+        if x.shape[0] != 1:
+            raise ValueError(f"naf_amd.{who}: `{name}` has B = {x.shape[0]}; like the reference's pca(), one map at a time (B = 1)")
+        shape = x.shape[1:]
+    elif x.dim() == 3:
+        shape = x.shape
+    else:
+        raise ValueError(f"naf_amd.{who}: `{name}` must be [C, H, W] or [1, C, H, W], got {tuple(x.shape)}")
+    C_, H, W = (int(v) for v in shape)
+    if H < 1 or W < 1:
+        raise ValueError(f"naf_amd.{who}: `{name}` has an empty grid {H} x {W}")
+    if C_ % 32 != 0 or not 32 <= C_ <= _lib.PCA_MAX_C:
+        raise ValueError(f"naf_amd.{who}: `{name}` has C = {C_} channels; served: C % 32 == 0 and 32 <= C <= {_lib.PCA_MAX_C}")
+    return C_, H, W
+
+
+def _pca_rows(x: torch.Tensor, who: str, name: str = "map"):
+    """The map as the kernels read it: ``(hwc, C, H, W, ld)`` with ``hwc`` a bf16 [H, W, C] tensor whose pixels are rows of C contiguous
+    values at one constant stride ``ld``.  A bf16 channels-last view -- what ``naf(...)`` returns -- is used as it is, without a copy;
+    anything else (fp32, NCHW) is converted ONCE to a dense bf16 channels-last buffer (fp32 values are rounded to bf16 once, as
+    ``pack_frame`` documents)."""
+    C_, H, W = _pca_map_shape(x, who, name)
+    _gpu(x, name)
+    x = (x[0] if x.dim() == 4 else x).detach()
+    hwc = x.permute(1, 2, 0)
+    ld = int(hwc.stride(1)) if W > 1 else (int(hwc.stride(0)) if H > 1 else C_)
+    as_is = (x.dtype == torch.bfloat16 and hwc.stride(2) == 1 and ld >= C_ and ld % 8 == 0 and (W == 1 or hwc.stride(1) == ld)
+             and (H == 1 or hwc.stride(0) == W * ld) and hwc.data_ptr() % 16 == 0)
+    if not as_is:
+        hwc = hwc.to(torch.bfloat16).contiguous()
+        if hwc.data_ptr() % 16:
+            hwc = hwc.clone()
+        ld = C_
+    return hwc, C_, H, W, ld
+
+
+def feature_moments_plan(P: int, C_: int) -> Tuple[int, int]:
+    """``(nsplit, slab_pixels)`` of naf_feature_moments for P pixels of C channels (host only)."""
+    a = _lib.FeatureMomentsArgs()
+    a.P, a.C, a.ld = int(P), int(C_), int(C_)
+    ns, slab = C.c_int32(0), C.c_int32(0)
+    _lib.check(_lib.load().naf_feature_moments_plan(C.byref(a), C.byref(ns), C.byref(slab)), "naf_feature_moments_plan")
+    return int(ns.value), int(slab.value)
+
+
+def feature_moments(map: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, int]:
+    """naf_feature_moments: ``(gram fp64 [C, C], sum fp64 [C], P)`` of one map ``[1, C, H, W]`` or ``[C, H, W]`` -- ``gram[i, j]`` the sum
+    over the P = H W pixels of ``x[i] x[j]``, exactly symmetric, and the channel sums, of the map's bf16 values (see ``_pca_rows`` for what
+    is copied).  Summation contract: include/naf_hip.h.  Two launches, no atomics: a second call gives the same bits."""
+    who = "feature_moments"
+    hwc, C_, H, W, ld = _pca_rows(map, who)
+    dev = hwc.device
+    lib = _lib.load()
+    a = _lib.FeatureMomentsArgs()
+    a.P, a.ld, a.C = H * W, ld, C_
+    nbytes = int(lib.naf_feature_moments_workspace_bytes(C.byref(a)))
+    if nbytes == 0:
+        raise ValueError(f"naf_amd.{who}: {(C_, H, W)} is not a served shape")
+    gram = torch.empty((C_, C_), dtype=torch.float64, device=dev)
+    total = torch.empty(C_, dtype=torch.float64, device=dev)
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=dev)
+    a.x, a.gram, a.sum = hwc.data_ptr(), gram.data_ptr(), total.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+    with torch.cuda.device(dev), _Timed("feature_moments"):
+        rc = lib.naf_feature_moments(C.byref(a), _stream(hwc))
+    _lib.check(rc, "naf_feature_moments")
+    return gram, total, H * W
+
+
+def _minmax_workspace(lib, P: int, dev) -> Tuple[torch.Tensor, int]:
+    q = _lib.PcaProjectArgs()
+    q.P = P
+    nbytes = int(lib.naf_pca_project_workspace_bytes(C.byref(q)))
+    return torch.empty(max(nbytes // 4, 4), dtype=torch.float32, device=dev), nbytes
+
+
+def pca_project(map: torch.Tensor, V: torch.Tensor, b: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """naf_pca_project: ``(raw, minmax)`` with ``raw[0, r, y, x] = b[r] + sum_c map[0, c, y, x] V[c, r]`` in fp32 -- a logical
+    ``[1, n, H, W]`` view of the dense ``[P][n]`` buffer the kernel writes -- and ``minmax`` fp32 ``[2, n]``, the exact minima and maxima
+    of ``raw`` per component.  ``V`` is fp32 ``[C, n]``, ``b`` fp32 ``[n]``, 1 <= n <= 8, on the map's device."""
+    who = "pca_project"
+    C_, H, W = _pca_map_shape(map, who)
+    for name, t in (("V", V), ("b", b)):
+        if not torch.is_tensor(t):
+            raise TypeError(f"naf_amd.{who}: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype != torch.float32:
+            raise TypeError(f"naf_amd.{who}: `{name}` must be float32, got {t.dtype}")
+    if V.dim() != 2 or V.shape[0] != C_ or not 1 <= V.shape[1] <= _lib.PCA_MAX_COMPONENTS:
+        raise ValueError(f"naf_amd.{who}: `V` must be [C = {C_}, n] with 1 <= n <= {_lib.PCA_MAX_COMPONENTS}, got {tuple(V.shape)}")
+    n = int(V.shape[1])
+    if tuple(b.shape) != (n,):
+        raise ValueError(f"naf_amd.{who}: `b` must be [{n}], got {tuple(b.shape)}")
+    hwc, C_, H, W, ld = _pca_rows(map, who)
+    dev = hwc.device
+    _gpu(V, "V")
+    _gpu(b, "b")
+    if V.device != dev or b.device != dev:
+        raise ValueError(f"naf_amd.{who}: map is on {dev}, V on {V.device}, b on {b.device}")
+    V, b = V.detach().contiguous(), b.detach().contiguous()
+    lib = _lib.load()
+    y = torch.empty((1, H, W, n), dtype=torch.float32, device=dev)
+    minmax = torch.empty((2, n), dtype=torch.float32, device=dev)
+    workspace, nbytes = _minmax_workspace(lib, H * W, dev)
+    a = _lib.PcaProjectArgs()
+    a.x, a.V, a.b, a.y, a.minmax = hwc.data_ptr(), V.data_ptr(), b.data_ptr(), y.data_ptr(), minmax.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+    a.P, a.ld, a.C, a.n = H * W, ld, C_, n
+    with torch.cuda.device(dev), _Timed("pca_project"):
+        rc = lib.naf_pca_project(C.byref(a), _stream(hwc))
+    _lib.check(rc, "naf_pca_project")
+    return y.permute(0, 3, 1, 2), minmax                   # strides (P n, 1, W n, n): the batch stride of the dense buffer
+
+
+def pca_minmax(raw: torch.Tensor) -> torch.Tensor:
+    """naf_pca_minmax: fp32 ``[B, 2, n]``, the minima and maxima per image and component of an fp32 projection ``[B, n, H, W]`` (or
+    ``[n, H, W]``: then ``[2, n]``).  A channels-last view whose pixels lie at one constant stride -- ``pca_project``'s result, or the head
+    kernel's ``[B, Ho, Wo, Npad]`` logits -- is read in place; any other layout is copied to channels-last once."""
+    who = "pca_minmax"
+    if not torch.is_tensor(raw):
+        raise TypeError(f"naf_amd.{who}: `raw` must be a tensor, got {type(raw).__name__}")
+    if raw.dtype != torch.float32:
+        raise TypeError(f"naf_amd.{who}: `raw` must be float32, got {raw.dtype}")
+    if raw.dim() not in (3, 4) or min(raw.shape) < 1:
+        raise ValueError(f"naf_amd.{who}: `raw` must be a non-empty [B, n, H, W] or [n, H, W], got {tuple(raw.shape)}")
+    x = raw.detach() if raw.dim() == 4 else raw.detach().unsqueeze(0)
+    B, n, H, W = (int(v) for v in x.shape)
+    if n > _lib.PCA_MAX_COMPONENTS:
+        raise ValueError(f"naf_amd.{who}: n = {n} components; served: 1 <= n <= {_lib.PCA_MAX_COMPONENTS}")
+    _gpu(x, "raw")
+    ld = int(x.stride(3)) if W > 1 else (int(x.stride(2)) if H > 1 else n)
+    if not (x.stride(1) == 1 and ld >= n and (W == 1 or x.stride(3) == ld) and (H == 1 or x.stride(2) == W * ld) and x.data_ptr() % 4 == 0):
+        x = x.contiguous(memory_format=torch.channels_last)
+        if x.stride(1) != 1:                               # n = 1 or a 1 x 1 grid: torch reports such a tensor dense either way
+            x = x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+        ld = n
+    dev = x.device
+    lib = _lib.load()
+    out = torch.empty((B, 2, n), dtype=torch.float32, device=dev)
+    workspace, nbytes = _minmax_workspace(lib, H * W, dev)
+    with torch.cuda.device(dev), _Timed("pca_minmax"):
+        for i in range(B):
+            a = _lib.PcaMinmaxArgs()
+            a.y, a.minmax = x[i].data_ptr(), out[i].data_ptr()
+            a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+            a.P, a.ld, a.n = H * W, ld, n
+            _lib.check(lib.naf_pca_minmax(C.byref(a), _stream(x)), "naf_pca_minmax")
+    return out if raw.dim() == 4 else out[0]
