@@ -1,19 +1,20 @@
-// GroupNorm -> SiLU -> Conv3x3(128 -> 128, reflect), weight-stationary on the matrix pipe, ROW-STREAMING (round 3).
+// GroupNorm -> SiLU -> Conv3x3(128 -> 128, reflect), weight-stationary on the matrix pipe, ROW-STREAMING.
 // Kernel of naf_stem_conv_fwd for ksize 3 (convolutions.py:52-61); a header so that tools/stem_rows_probe.hip can instantiate
 // ablation variants.
 //
-// Why this shape.  The chip is power-limited under this layer (tools/mfma_chain_probe.hip: the matrix pipe issues every
-// 32.3 cycles whatever sits between two MFMAs, and the clock drops to 1.4-1.8 GHz), so what buys time is energy per pixel:
-// LDS reads and side instructions, not issue slots.  The round-1/2 kernel (stem_conv_kernel.h) computed two output rows per
-// step from four input rows: a B fragment (16 input channels x 32 pixels of one input row at one tap column) fed 1.5 MFMAs on
-// average.  Here ONE input row is streamed per row-step and every fragment feeds the three output rows it touches --
-// MFMAs (tap row 2 -> output row r-1, tap row 1 -> r, tap row 0 -> r+1) back to back from the same registers: 24 fragment
-// reads per 72 MFMAs (was 48), and an input row is read from the LDS exactly once per wave.
-//   * wave w owns output channels [32w, 32w+32) and keeps all its weights in registers (9 taps x 8 k-steps x 4 = 288);
-//   * three accumulators are live (rows r-1, r, r+1) and a fourth is in its epilogue (row r-2): the four names rotate with
-//     period 4 input rows, so the generated body (tools/gen_stem_rows.py -> stem_rows_sched.inc) covers four input rows =
-//     two "double-steps" of 144 MFMAs with one barrier each; an accumulator is re-initialised with the conv bias straight
-//     from the LDS (no VALU) after its epilogue;
+// Why this shape.  The chip is power-limited under this layer (the clock drops to 1.6-2.2 GHz), so what buys time is energy per
+// pixel and the clock the chip holds, not issue slots.  ONE input row is streamed per row-step and every B fragment (32 input
+// channels x 16 pixels of one input row at one tap column) feeds the three output rows it touches and both of the wave's channel
+// tiles: six MFMAs (tap row 2 -> output row r-1, tap row 1 -> r, tap row 0 -> r+1) back to back from the same registers, 24
+// fragment reads per 144 MFMAs, and an input row is read from the LDS exactly once per wave.  The instruction is
+// v_mfma_f32_16x16x32_bf16: same cycles per FLOP as the 32x32x16 form this kernel used before, but under the power cap the chip
+// holds a higher clock on it (profiles/stem_rows_16x16x32.txt).
+//   * wave w owns output channels [32w, 32w+32) as two channel tiles of 16 (one GroupNorm group each) and keeps all its weights
+//     in registers (9 taps x 2 channel tiles x 4 k-steps of 32 x 4 = 288);
+//   * an output row is four 16x16 accumulator tiles (channel tile x pixel tile, 16 registers); three rows are live (r-1, r, r+1)
+//     and a fourth is in its epilogue (row r-2): the four names rotate with period 4 input rows, so the generated body
+//     (tools/gen_stem_rows.py -> stem_rows_sched.inc) covers four input rows = two "double-steps" of 288 MFMAs with one barrier
+//     each; an output row is re-initialised with the conv bias straight from the LDS (no VALU) after its epilogue;
 //   * ring of 8 input rows in the LDS: a batch of two rows is loaded (global -> registers) three double-steps ahead,
 //     normalised + activated + written two double-steps ahead, so the rows a double-step reads have been in the ring for
 //     a whole double-step and the first fragments of the next double-step are requested before the barrier;
@@ -34,7 +35,7 @@ constexpr int ROWE = PXR * PXE; // elements per ring row
 constexpr int RING = 8;         // ring rows
 constexpr int NLD = 5;          // 16-byte load pieces per thread per batch of two rows
 constexpr int NST = 4;          // 16-byte store pieces per thread per output tile of two rows
-constexpr int NB = 3;           // B-fragment register buffers (a fragment is requested 4 fragments = 12 MFMAs ahead)
+constexpr int NB = 3;           // B-fragment register buffers (a fragment is requested 3 fragments = 18 MFMAs ahead)
 constexpr size_t LDS_BYTES = (size_t)(RING * ROWE + 2 * 2 * TW * PXE) * 2 + 3 * C * sizeof(float);
 // POOL: + the strip's column tables [32][32], the segment's row tables [<= POOL_ROWS][32] (fp32 cos | sin) and the two
 // indicator operands [2][64 lanes][8] bf16
@@ -42,7 +43,6 @@ constexpr size_t LDS_BYTES = (size_t)(RING * ROWE + 2 * 2 * TW * PXE) * 2 + 3 * 
 constexpr int POOL_ROWS = 128;  // tallest segment of a POOL launch
 constexpr size_t LDS_BYTES_POOL = LDS_BYTES + (size_t)(TW * 32 + POOL_ROWS * 32 + 4 * 4 * 4 * 64) * sizeof(float) + 2 * 64 * 4 * 2;
 
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
 
 // sum over the four 16-lane rows of a wave (lanes l, l ^ 16, l ^ 32, l ^ 48), every lane gets it (cf. naf_rows_max)
 __device__ __forceinline__ float rows_sum(float v) {
@@ -95,7 +95,15 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
     bf16_t* pind = reinterpret_cast<bf16_t*>(psum + 4 * 4 * 4 * 64);    // POOL: [2 types][64 lanes][4] indicator operands
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n32 = lane & 31, half = lane >> 5;
+    // MFMA lane roles (v_mfma_f32_16x16x32_bf16): column lane & 15, k-group lane >> 4.  A ds_read_b128 is served in the lane
+    // groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32): each takes 8 columns of one k-group and the OTHER 8 columns of the
+    // next.  With 272-byte pixels (bank block = pixel mod 16) and k-groups 16 bytes apart that is 2-way; conflict-free needs the
+    // two column sets on pixels of different parity and the two k-groups an even number of 16-byte chunks apart.  So columns
+    // 4..11 stand for the even pixels of a 16-pixel tile, the others for the odd ones, and k-groups 0, 1, 2, 3 hold input
+    // channels 0-7, 16-23, 8-15, 24-31 of a k-step (the same in the weights' A fragments, so the contraction is unchanged).
+    const int c16 = lane & 15, kgrp = lane >> 4;
+    const int pix = (c16 >= 4 && c16 < 12) ? 2 * (c16 - 4) : (c16 < 4 ? 2 * c16 + 1 : 2 * c16 - 15);   // pixel of the tile
+    const int kq = ((kgrp & 1) << 1) | (kgrp >> 1);                                                   // 8-channel chunk of the k-step
     long long rt_in = 0;
     if constexpr ((ABL & 1024) != 0) rt_in = (long long)__builtin_amdgcn_s_memrealtime();   // probe: 100 MHz wall clock at entry
     // Workgroup -> tile: consecutive workgroups land on different XCDs (blockIdx % 8), each with its own L2.  Strips that are
@@ -230,19 +238,24 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
         ld1[n] = *reinterpret_cast<const u32x4_t*>(xbu + (int64_t)reflect(sy - 1 + 2 + rr, p.H) * p.xs[1] * 2 + col_off[n]);
     }
     __builtin_amdgcn_sched_barrier(0);
-    // ---- weights -> registers (A fragments): lane (oc = 32*wave + n32, kg = half) holds 8 consecutive ic; w_packed is in exactly that
-    // order (naf_stem_weight_index), so every load instruction of a wave reads one contiguous KB.  Requested behind
+    // ---- weights -> registers (A fragments): fragment (tap, channel tile a, k-step ks of 32) = lane (oc = 32 wave + 16 a + c16,
+    // 8 consecutive ic at 32 ks + 8 kq).  w_packed (naf_stem_weight_index) is ordered [tap][wave][ic / 16][(ic / 8) & 1][oc % 32][8]:
+    // a load instruction gathers four 256-byte runs, one per k-group (whole lines, each fetched once per wave).  Requested behind
     // the prologue's input loads (memory operations retire in order: the prologue must not wait for 295 KB of weights) and
     // ahead of its arithmetic; they land in AGPRs (the asm MFMAs' operand class), so that arithmetic does not compete with them.
     bf16x8_t wreg[72];
     {
-        const bf16_t* wp = p.w + (size_t)(wave * 32 + n32) * C + half * 8;
+        const bf16_t* wp = p.w + (size_t)(wave * 32 + c16) * C + kq * 8;
+        const int wl = ((kq >> 1) * 64 + (kq & 1) * 32 + c16) * 8;   // the lane inside its (tap, wave, k-step of 32): two 16-channel blocks of 64 x 8
 #pragma unroll
         for (int t = 0; t < 9; ++t)
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks)
-                wreg[t * 8 + ks] = (ABL & 4096) ? *reinterpret_cast<const bf16x8_t*>(wp + (size_t)t * C * C + ks * 16)
-                                                : *reinterpret_cast<const bf16x8_t*>(p.w + ((ABL & 512) ? (size_t)lane * 8 : (size_t)(((t * 4 + wave) * 8 + ks) * 64 + lane) * 8));
+            for (int a = 0; a < 2; ++a)
+#pragma unroll
+                for (int ks = 0; ks < 4; ++ks)
+                    wreg[(t * 2 + a) * 4 + ks] =
+                        (ABL & 4096) ? *reinterpret_cast<const bf16x8_t*>(wp + (size_t)t * C * C + (size_t)a * 16 * C + ks * 32)
+                                     : *reinterpret_cast<const bf16x8_t*>(p.w + ((ABL & 512) ? (size_t)lane * 8 : (size_t)((t * 4 + wave) * 8 + 2 * ks) * 512 + a * 128 + wl));
     }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -260,27 +273,29 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
     for (int n = 0; n < NLD; ++n) issue_one(2, n);
 
     float s1p[2] = {0.f, 0.f}, s2p[2] = {0.f, 0.f};  // GroupNorm sums of the wave's two groups (plain f32: no packed VALU beside MFMAs)
-    const int lane_b = n32 * PXE + half * 8;  // B-fragment lane offset inside a ring row (before the tap-column shift)
+    const int lane_b = pix * PXE + kq * 8;  // B-fragment lane offset inside a ring row (before the tap-column and pixel-tile shift)
+    const int lane_o = pix * PXE + wave * 32 + 4 * kgrp;   // the lane's place in an output tile row (before the pixel / channel tile shift)
 
-    // Accumulator row 4j + r of a 32x32 tile = output channel 32 wave + 8 j + 4 half + r.  All four start as the bias (finite
-    // values: rows outside the segment are computed like the others and masked out of the sums by a multiplier).
-    f32x16_t acc[4];
+    // Output row nm is four 16x16 tiles j = 2 a + b (channel tile a, pixel tile b): register r of the lane = output channel
+    // 32 wave + 16 a + 4 kgrp + r at pixel 16 b + pix.  All start as the bias (finite values: rows outside the segment are
+    // computed like the others and masked out of the sums by a multiplier).
+    f32x4_t acc[4][4];
     auto acc_init = [&](int nm, int j) __attribute__((always_inline)) {
-        const f32x4_t bv = *reinterpret_cast<const f32x4_t*>(cvec + wave * 32 + 8 * j + 4 * half);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[nm][j * 4 + r] = bv[r];
+        acc[nm][j] = *reinterpret_cast<const f32x4_t*>(cvec + wave * 32 + 16 * (j >> 1) + 4 * kgrp);
     };
 #pragma unroll
     for (int nm = 0; nm < 4; ++nm)
 #pragma unroll
         for (int j = 0; j < 4; ++j) acc_init(nm, j);
 
-    const float lane_m = sx + n32 < p.W ? 1.f : 0.f;   // EDGE: pixels of the strip past the image do not count in the sums
+    // EDGE: pixels of the strip past the image do not count in the sums (one mask per pixel tile)
+    const float lane_m[2] = {sx + pix < p.W ? 1.f : 0.f, sx + 16 + pix < p.W ? 1.f : 0.f};
     bf16x8_t bb[NB] = {};
-    // fragment f of a row: tap column f / 8, k-step f % 8.  base = ring row base (elements) of the row
+    // fragment f of a row (32 input channels x 16 pixels): tap column f / 8, pixel tile (f / 4) % 2, k-step f % 4.  base = ring
+    // row base (elements) of the row
     auto load_frag = [&](int base, int f, bf16x8_t& dst) __attribute__((always_inline)) {
         if (ABL & 4) return;
-        dst = *reinterpret_cast<const bf16x8_t*>(ring + base + (f >> 3) * PXE + lane_b + (f & 7) * 16);
+        dst = *reinterpret_cast<const bf16x8_t*>(ring + base + ((f >> 3) + 16 * ((f >> 2) & 1)) * PXE + lane_b + (f & 3) * 32);
     };
 #pragma unroll
     for (int f = 0; f < NB; ++f) load_frag(0, f, bb[f]);
@@ -438,7 +453,7 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
 // previous gap, and two gaps' worth of transcendentals then sit between one pair of MFMAs
 #define NAF_MFMA(accv, wv, bv, wcls)                                                                              \
     do {                                                                                                          \
-        asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %0" : "+v"(accv) : wcls(wv), "v"(bv));              \
+        asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(accv) : wcls(wv), "v"(bv));              \
         if constexpr (!(ABL & 64)) __builtin_amdgcn_sched_barrier(0);                                             \
     } while (0)
 // 16 bytes into the ring as two ds_write_b64: a ds_write_b128 beside an MFMA stalls the matrix pipe ~21 cycles, a ds_write_b64 does
@@ -451,39 +466,54 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
         *((volatile NAF_LDS u32x2_t*)(d_)) = u32x2_t{a0, a1};                                     \
         *((volatile NAF_LDS u32x2_t*)(d_ + 4)) = u32x2_t{a2, a3};                                 \
     } while (0)
+#define NAF_LDS_WRITE_64(ptr, a0, a1) *((volatile NAF_LDS u32x2_t*)(ptr)) = u32x2_t{a0, a1}
 #define NAF_PIN1(a) asm volatile("" : "+v"(a))
 #define NAF_PIN2(a, b) asm volatile("" : "+v"(a), "+v"(b))
-            // epilogue slice: accumulator rows 4j..4j+3 of accumulator `nm` (output row g of this double-step's tile) ->
-            // GroupNorm sums, bf16, LDS tile; three micro-ops of four plain VALU instructions each
+            // epilogue slice: tile j = 2 a + b of output row `nm` (row g of this double-step's tile) -> GroupNorm sums (channel tile
+            // a is one group), bf16, LDS tile; six micro-ops of at most two plain VALU instructions each
             float e_a = 0.f, e_q = 0.f;
+            bf16x4_t e_o = {};
             auto epi0 = [&](int nm, int g, int j) __attribute__((always_inline)) {
                 if (ABL & 2) {
-                    asm volatile("" ::"v"(acc[nm][j * 4]), "v"(acc[nm][j * 4 + 1]), "v"(acc[nm][j * 4 + 2]), "v"(acc[nm][j * 4 + 3]));
+                    asm volatile("" ::"v"(acc[nm][j]));
                     return;
                 }
-                bf16x4_t o;
 #pragma unroll
-                for (int r = 0; r < 4; ++r) o[r] = (bf16_t)acc[nm][j * 4 + r];
-                *reinterpret_cast<bf16x4_t*>(ot + (g * TW + n32) * PXE + wave * 32 + 8 * j + 4 * half) = o;
-                if constexpr (POOL) return;   // the last layer: no GroupNorm behind it, no sums
-                e_a = acc[nm][j * 4] + acc[nm][j * 4 + 1];
-                NAF_PIN1(e_a);
+                for (int r = 0; r < 4; ++r) e_o[r] = (bf16_t)acc[nm][j][r];
+                asm volatile("" : "+v"(e_o));
             };
             auto epi1 = [&](int nm, int g, int j) __attribute__((always_inline)) {
                 if (ABL & 2) return;
-                if constexpr (POOL) return;
-                e_a += acc[nm][j * 4 + 2];
-                e_a += acc[nm][j * 4 + 3];
-                e_q = acc[nm][j * 4] * acc[nm][j * 4];
-                e_q = __builtin_fmaf(acc[nm][j * 4 + 1], acc[nm][j * 4 + 1], e_q);
-                NAF_PIN2(e_a, e_q);
+                *reinterpret_cast<bf16x4_t*>(ot + (g * TW + 16 * (j & 1)) * PXE + 16 * (j >> 1) + lane_o) = e_o;
+                if constexpr (POOL) return;   // the last layer: no GroupNorm behind it, no sums
+                e_a = acc[nm][j][0] + acc[nm][j][1];
+                NAF_PIN1(e_a);
             };
             auto epi2 = [&](int nm, int g, int j) __attribute__((always_inline)) {
                 if (ABL & 2) return;
                 if constexpr (POOL) return;
-                e_q = __builtin_fmaf(acc[nm][j * 4 + 2], acc[nm][j * 4 + 2], e_q);
-                e_q = __builtin_fmaf(acc[nm][j * 4 + 3], acc[nm][j * 4 + 3], e_q);
-                const float m = EDGE ? mrow[g] * lane_m : mrow[g];
+                e_a += acc[nm][j][2];
+                e_a += acc[nm][j][3];
+                NAF_PIN1(e_a);
+            };
+            auto epi3 = [&](int nm, int g, int j) __attribute__((always_inline)) {
+                if (ABL & 2) return;
+                if constexpr (POOL) return;
+                e_q = acc[nm][j][0] * acc[nm][j][0];
+                e_q = __builtin_fmaf(acc[nm][j][1], acc[nm][j][1], e_q);
+                NAF_PIN1(e_q);
+            };
+            auto epi4 = [&](int nm, int g, int j) __attribute__((always_inline)) {
+                if (ABL & 2) return;
+                if constexpr (POOL) return;
+                e_q = __builtin_fmaf(acc[nm][j][2], acc[nm][j][2], e_q);
+                e_q = __builtin_fmaf(acc[nm][j][3], acc[nm][j][3], e_q);
+                NAF_PIN1(e_q);
+            };
+            auto epi5 = [&](int nm, int g, int j) __attribute__((always_inline)) {
+                if (ABL & 2) return;
+                if constexpr (POOL) return;
+                const float m = EDGE ? mrow[g] * lane_m[j & 1] : mrow[g];
                 s1p[j >> 1] = __builtin_fmaf(e_a, m, s1p[j >> 1]);
                 s2p[j >> 1] = __builtin_fmaf(e_q, m, s2p[j >> 1]);
                 NAF_PIN2(s1p[j >> 1], s2p[j >> 1]);
@@ -509,6 +539,7 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
 #undef NAF_PIN2
 #undef NAF_MFMA
 #undef NAF_LDS_WRITE_2X64
+#undef NAF_LDS_WRITE_64
             if (!(ABL & 32)) __syncthreads();
         };
         dstep(std::integral_constant<int, 0>{});
@@ -557,7 +588,7 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
                 float a = 0.f, q = 0.f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float v = acc[0][j * 4 + r];
+                    const float v = acc[0][j][r];
                     o[r] = (bf16_t)v;
                     if constexpr (!POOL) {
                         a += v;
@@ -568,7 +599,7 @@ __global__ __launch_bounds__(256, 1) void stem_conv_rows_kernel(const StemConvPa
                     s1p[j >> 1] += a;
                     s2p[j >> 1] += q;
                 }
-                *reinterpret_cast<bf16x4_t*>(t1 + n32 * PXE + wave * 32 + 8 * j + 4 * half) = o;
+                *reinterpret_cast<bf16x4_t*>(t1 + 16 * (j & 1) * PXE + 16 * (j >> 1) + lane_o) = o;
             }
         }
         __syncthreads();

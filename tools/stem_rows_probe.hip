@@ -1,7 +1,7 @@
 // Stand-alone ablation probe of the row-streaming 3x3 stem layer (stem_rows_kernel.h): time and shader cycles per double-step with
 // parts of the step switched off.  Not part of the library.  (Round 3 also ran the two-row-step kernel of rounds 1-2 beside it,
 // interleaved on one lease: profiles/r03_stem_rows_probe.txt.)
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Inaf_amd/csrc tools/stem_rows_probe.hip -o tools/bin/stem_rows_probe
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize -Iinclude -Inaf_amd/csrc tools/stem_rows_probe.hip -o tools/bin/stem_rows_probe
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -91,7 +91,7 @@ int main(int argc, char** argv) {
         printf("\n");
     }
     for (int i = 0; i < na; ++i)
-        printf("row-streaming %-40s %.4f ms  %7.1f TFLOP/s  %7.0f cycles per double-step (144 MFMAs = 4608)  => %.2f GHz\n", abl[i].name, abl[i].ms,
+        printf("row-streaming %-40s %.4f ms  %7.1f TFLOP/s  %7.0f cycles per double-step (288 MFMAs = 4608)  => %.2f GHz\n", abl[i].name, abl[i].ms,
                flops / abl[i].ms / 1e9, abl[i].cyc, abl[i].cyc * 2.0 * ((p.seg_h + 6) / 4) / (abl[i].ms * 1e6));
     return 0;
 }
