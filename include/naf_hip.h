@@ -392,6 +392,23 @@ int naf_preshrink_image(float* out, const void* image, int32_t image_dtype, int3
 int naf_pool_guidance(void* y, const void* x, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t C,
                       naf_stream_t stream);
 
+/* ---- backward of the guidance pooling and of the image pre-shrink (new entry points; detect by symbol, version number unchanged) ----
+ * What train.py:126-137 differentiates when the guidance image is larger than the output (its own call: 4x per axis).
+ * naf_pool_guidance_bwd is the adjoint of naf_pool_guidance: dy device bf16 dense channels-last [B, Ho, Wo, C] -> dx device bf16 dense
+ * channels-last [B, H, W, C], C % 8 == 0, both 16-byte aligned.  Gather form: dx[y, x] = sum over the windows that hold (y, x) of
+ * float(dy) * (1.0f / area), output rows floor(y*Ho/H) .. ceil((y+1)*Ho/H) - 1 ascending, then columns ascending, fp32, one rounding to
+ * bf16; no atomics, bit-reproducible.  Any H, Ho (an output larger than the image too).
+ * naf_preshrink_image_bwd is the adjoint of naf_preshrink_image with respect to the image: dout device float dense [B, 3, Hs, Ws] ->
+ * dimage device f32 / bf16 [B, 3, H, W], strides {b, c, y, x}; every element is written, zeros included.  The weights are the forward's own
+ * fp32 expressions; each term is fl(fl(h * w) * g), summed in fp32 in a fixed order (output rows ascending, columns ascending); no atomics,
+ * bit-reproducible.  Serves Hs <= H and Ws <= W (all naf.py:39-48 produces); NAF_ERR_UNSUPPORTED otherwise.
+ * Both: NAF_ERR_INVALID, before any device work and with naf_last_error() set, for NULL pointers, sizes <= 0, C % 8 != 0, a misaligned
+ * buffer, an unknown dtype or more than 2^31 - 1 workgroups.  Caller-owned memory and stream; capturable; no workspace. */
+int naf_pool_guidance_bwd(void* dx, const void* dy, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t C,
+                          naf_stream_t stream);
+int naf_preshrink_image_bwd(void* dimage, const float* dout, int32_t image_dtype, int32_t B, int32_t H, int32_t W, int32_t Hs,
+                            int32_t Ws, const int64_t image_stride[4], naf_stream_t stream);
+
 /* ---- value packing --------------------------------------------------------------------------------
  * Replaces the rearrange + dtype cast of the value tensor in CrossAttention._resize
  * (attentions.py:50-51) WITHOUT the nearest-exact upsampling (values stay low-res).

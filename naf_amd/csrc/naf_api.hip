@@ -151,6 +151,25 @@ int naf_pool_guidance(void* y, const void* x, int32_t B, int32_t H, int32_t W, i
     return naf_launch_pool_guidance(y, x, B, H, W, Ho, Wo, C, static_cast<hipStream_t>(stream));
 }
 
+int naf_pool_guidance_bwd(void* dx, const void* dy, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t C, naf_stream_t stream) {
+    NAF_REQUIRE(dx && dy, "naf_pool_guidance_bwd: NULL pointer");
+    NAF_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0, "naf_pool_guidance_bwd: non-positive size");
+    NAF_REQUIRE(C % 8 == 0 && al16(dx) && al16(dy), "naf_pool_guidance_bwd: needs C %% 8 == 0 and 16-byte aligned buffers (C=%d)", C);
+    return naf_launch_pool_guidance_bwd(dx, dy, B, H, W, Ho, Wo, C, static_cast<hipStream_t>(stream));
+}
+
+int naf_preshrink_image_bwd(void* dimage, const float* dout, int32_t image_dtype, int32_t B, int32_t H, int32_t W, int32_t Hs, int32_t Ws,
+                            const int64_t image_stride[4], naf_stream_t stream) {
+    NAF_REQUIRE(dimage && dout && image_stride, "naf_preshrink_image_bwd: NULL pointer");
+    NAF_REQUIRE(image_dtype == NAF_BF16 || image_dtype == NAF_F32, "naf_preshrink_image_bwd: image_dtype %d", image_dtype);
+    NAF_REQUIRE(B > 0 && H > 0 && W > 0 && Hs > 0 && Ws > 0, "naf_preshrink_image_bwd: non-positive size");
+    if (Hs > H || Ws > W) {
+        naf_set_error("naf_preshrink_image_bwd: serves shrinking only (%dx%d -> %dx%d)", H, W, Hs, Ws);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    return naf_launch_preshrink_bwd(dimage, dout, image_dtype, B, H, W, Hs, Ws, image_stride, static_cast<hipStream_t>(stream));
+}
+
 int naf_stem_conv0_fwd(const naf_stem_conv0_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a != nullptr, "naf_stem_conv0_fwd: args is NULL");
     NAF_REQUIRE(a->image && a->weight && a->bias && a->stats_out, "naf_stem_conv0_fwd: NULL pointer");   // y may be NULL: statistics only

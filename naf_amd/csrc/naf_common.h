@@ -60,6 +60,8 @@ int naf_launch_pack_values(void* vp, const void* v, int v_dtype, int B, int C, i
 
 int naf_launch_preshrink(float* out, const void* img, int dtype, int B, int H, int W, int Hs, int Ws, const int64_t* st, hipStream_t s);   // resize.hip
 int naf_launch_pool_guidance(void* y, const void* x, int B, int H, int W, int Ho, int Wo, int C, hipStream_t s);   // pool.hip
+int naf_launch_preshrink_bwd(void* dimg, const float* dout, int dtype, int B, int H, int W, int Hs, int Ws, const int64_t* st, hipStream_t s);   // resize.hip
+int naf_launch_pool_guidance_bwd(void* dx, const void* dy, int B, int H, int W, int Ho, int Wo, int C, hipStream_t s);   // pool.hip
 
 int naf_launch_stem_conv0(const naf_stem_conv0_args* a, hipStream_t s);            // stem_conv0.hip
 int naf_launch_stem_conv(const naf_stem_conv_args* a, hipStream_t s, const naf_key_pool_args* kp = nullptr);   // stem_conv.hip

@@ -758,7 +758,11 @@ class NAF(nn.Module):
         and the features.  The attention and its backward are the HIP kernels (naf_xna_fwd / naf_xna_bwd through
         ``ops.XnaFunction``); the conv stem runs as ``_HipStem`` (HIP forward and backward kernels) or, as the A/B arm, as torch ops
         (``amp`` below); RoPE and key pooling run as HIP kernels with their own backward (``ops.RopePoolFunction``) where the stem is
-        ``_HipStem`` and the RoPE heads are the attention heads with a head dim that is a multiple of 32, as torch ops otherwise.  In ``.train()`` mode the RoPE coordinates get the
+        ``_HipStem`` and the RoPE heads are the attention heads with a head dim that is a multiple of 32, as torch ops otherwise.  On that
+        branch the pooling of a guidance image larger than the output (naf.py:34; the reference trains at 4x, train.py:126-127) is
+        ``ops.pool_guidance`` with its backward ``naf_pool_guidance_bwd`` (bf16 channels-last in both directions, no fp32 copy of the
+        full-resolution guidance), and with ``_HipStem`` the pre-shrink of an image more than 4x the output (naf.py:39-48) is
+        ``ops.preshrink_image`` with ``naf_preshrink_image_bwd`` (a gather, bit-reproducible); the torch arms keep ATen's ops.  In ``.train()`` mode the RoPE coordinates get the
         reference's random rescale (rope.py:107-124, NAF's rope_rescale); in ``.eval()`` mode they are deterministic.  Every geometry
         has a backward kernel (``ops.xna_backward_select``): the MFMA cell kernel (integer ratio, Wo/w a multiple of 16, window <= 13
         with K/V windows inside the LDS), the row-streaming matrix-core kernel (every other integer ratio: the reference's own training
@@ -782,28 +786,18 @@ class NAF(nn.Module):
         h, w = features.shape[-2:]
         heads_rope, heads = enc.rope.num_heads, self.upsampler.num_heads
         x = image
-        if x.shape[-2] > 4 * ho or x.shape[-1] > 4 * wo:                       # naf.py:39-48
-            x = F.interpolate(x.float(), size=(min(x.shape[-2], 4 * ho, 4 * wo), min(x.shape[-1], 4 * wo, 4 * ho)),
-                              mode="bilinear", align_corners=False)
         if amp == "auto":
             if enc.use_encoder and enc.stem_impl == "hip" and enc._hip_train_stem_ok():
                 amp = "hip"
             else:
                 amp = bool(torch.is_autocast_enabled() and torch.get_autocast_dtype("cuda") == torch.bfloat16)
-        if enc.use_encoder and amp == "hip":
-            if not enc._hip_train_stem_ok():
-                raise RuntimeError("forward_train(amp='hip'): the differentiable HIP stem serves hidden widths that are multiples of 16 "
-                                   f"up to 256 with GroupNorm(8) (got {enc.encoder[0].out_channels})")
-            x = _HipStem.apply(enc, x, *_hip_stem_params(enc))
-            if x.shape[-2:] != (ho, wo):
-                x = x.float()
-        elif enc.use_encoder:
-            x = x.float().contiguous(memory_format=torch.channels_last)
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(amp)):
-                x = torch.cat([enc._branch_train(x, enc.encoder), enc._branch_train(x, enc.sem_encoder)], dim=1)
-            x = x.float()
-        if x.shape[-2:] != (ho, wo):
-            x = F.adaptive_avg_pool2d(x, output_size=(ho, wo))                 # naf.py:34
+        if x.shape[-2] > 4 * ho or x.shape[-1] > 4 * wo:                       # naf.py:39-48
+            size = (min(x.shape[-2], 4 * ho, 4 * wo), min(x.shape[-1], 4 * wo, 4 * ho))
+            if enc.use_encoder and amp == "hip" and x.dim() == 4 and x.shape[1] == 3:
+                # naf_preshrink_image, and naf_preshrink_image_bwd when the image wants a gradient (a gather: no atomic scatter)
+                x = ops.preshrink_image(x if x.dtype in (torch.float32, torch.bfloat16) else x.float(), size)
+            else:
+                x = F.interpolate(x.float(), size=size, mode="bilinear", align_corners=False)
 
         def rope_tabs():    # [Ho, 2, P], [Wo, 2, P]; in training mode with the reference's coordinate augmentation (rope.py:107-124)
             if enc.rope.training and enc.rope.cache_train_coords:
@@ -812,10 +806,35 @@ class NAF(nn.Module):
                 return enc.rope._train_tables[(ho, wo)]
             return _rope_train_tables(enc.rope, ho, wo) if enc.rope.training else enc.rope.tables(ho, wo)
 
+        tabs = None
+        if enc.use_encoder and amp == "hip":
+            if not enc._hip_train_stem_ok():
+                raise RuntimeError("forward_train(amp='hip'): the differentiable HIP stem serves hidden widths that are multiples of 16 "
+                                   f"up to 256 with GroupNorm(8) (got {enc.encoder[0].out_channels})")
+            rope_hip = heads_rope == heads and (2 * enc.encoder[0].out_channels // heads_rope) % 32 == 0
+            if rope_hip:
+                # before the stem: its last layer, the pooling and naf_rope_pool_fwd then follow one another on the stream
+                tabs = tuple(t.contiguous() for t in rope_tabs())
+            x = _HipStem.apply(enc, x, *_hip_stem_params(enc))
+            if x.shape[-2:] != (ho, wo):
+                if rope_hip:
+                    # naf.py:34 as naf_pool_guidance / naf_pool_guidance_bwd: bf16 channels-last from the stem's last layer into
+                    # RopePoolFunction below, and the gradient the same way back (no fp32 copy of the full-resolution guidance)
+                    x = ops.pool_guidance(x, (ho, wo))
+                else:
+                    x = x.float()
+        elif enc.use_encoder:
+            x = x.float().contiguous(memory_format=torch.channels_last)
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=bool(amp)):
+                x = torch.cat([enc._branch_train(x, enc.encoder), enc._branch_train(x, enc.sem_encoder)], dim=1)
+            x = x.float()
+        if x.shape[-2:] != (ho, wo):
+            x = F.adaptive_avg_pool2d(x, output_size=(ho, wo))                 # naf.py:34
+
         if amp == "hip" and heads_rope == heads and (x.shape[1] // heads_rope) % 32 == 0:
             # RoPE, key pooling and their backward as HIP kernels too (naf_rope_pool_fwd / naf_rope_pool_bwd): the guidance stays
             # bf16 channels-last from the stem's last layer to the attention kernel, and so does its gradient on the way back
-            tab_y, tab_x = rope_tabs()
+            tab_y, tab_x = tabs if tabs is not None else rope_tabs()
             xcl = x.to(torch.bfloat16).contiguous(memory_format=torch.channels_last)
             q5, k5 = ops.RopePoolFunction.apply(xcl, tab_y.contiguous(), tab_x.contiguous(), heads_rope, (h, w))
             B, C = features.shape[:2]

@@ -464,8 +464,7 @@ def rope_pool(x: torch.Tensor, tab_y: torch.Tensor, tab_x: torch.Tensor, heads: 
     return q, k
 
 
-def preshrink_image(image: torch.Tensor, size) -> torch.Tensor:
-    """F.interpolate(image, size, mode="bilinear", align_corners=False) of naf.py:39-48 -> fp32 [B, 3, Hs, Ws]."""
+def _preshrink_image(image: torch.Tensor, size) -> torch.Tensor:
     _gpu(image, "image")
     if image.dtype not in _DT or image.dim() != 4 or image.shape[1] != 3:
         raise ValueError("preshrink_image: expected a [B, 3, H, W] float32 / bfloat16 image")
@@ -480,9 +479,58 @@ def preshrink_image(image: torch.Tensor, size) -> torch.Tensor:
     return out
 
 
-def pool_guidance(x: torch.Tensor, output_size) -> torch.Tensor:
-    """adaptive_avg_pool2d of the bf16 channels-last guidance [B, C, H, W] (logical) to ``output_size`` (naf.py:34);
-    returns a logical [B, C, Ho, Wo] view of a dense channels-last buffer."""
+def preshrink_image_bwd(dout: torch.Tensor, image_like: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Adjoint of ``preshrink_image`` with respect to the image (``naf_preshrink_image_bwd``): dout [B, 3, Hs, Ws] (cast to dense fp32)
+    -> the gradient of an image of ``image_like``'s shape and dtype (float32 / bfloat16; only those two are read, a meta tensor will do),
+    laid out like it when it is dense (``torch.empty_like``).  ``out``: write into this tensor instead, whatever its strides.  Gather form,
+    no atomics: bit-reproducible, unlike ATen's scatter."""
+    _gpu(dout, "dout")
+    if image_like.dtype not in _DT or image_like.dim() != 4 or image_like.shape[1] != 3:
+        raise ValueError("preshrink_image_bwd: expected a [B, 3, H, W] float32 / bfloat16 image")
+    B, _, H, W = image_like.shape
+    if dout.dim() != 4 or dout.shape[0] != B or dout.shape[1] != 3:
+        raise ValueError(f"preshrink_image_bwd: gradient {tuple(dout.shape)} does not belong to an image {tuple(image_like.shape)}")
+    Hs, Ws = int(dout.shape[2]), int(dout.shape[3])
+    if dout.dtype != torch.float32 or not dout.is_contiguous():
+        dout = dout.float().contiguous()
+    if out is None:
+        dimage = torch.empty_like(image_like, device=dout.device)
+    else:
+        _gpu(out, "out")
+        if out.shape != image_like.shape or out.dtype != image_like.dtype:
+            raise ValueError(f"preshrink_image_bwd: out is {tuple(out.shape)} {out.dtype}, the image {tuple(image_like.shape)} {image_like.dtype}")
+        dimage = out
+    st = _strides4(dimage, (0, 1, 2, 3))
+    lib = _lib.load()
+    with torch.cuda.device(dout.device), _Timed("preshrink_bwd"):
+        rc = lib.naf_preshrink_image_bwd(dimage.data_ptr(), dout.data_ptr(), _DT[dimage.dtype], B, H, W, Hs, Ws, C.byref(st), _stream(dout))
+    _lib.check(rc, "naf_preshrink_image_bwd")
+    return dimage
+
+
+class PreshrinkFunction(torch.autograd.Function):
+    """Differentiable ``preshrink_image``: forward = naf_preshrink_image, backward = naf_preshrink_image_bwd (gradient in the image's dtype)."""
+
+    @staticmethod
+    def forward(ctx, image, size):
+        ctx.like = torch.empty_like(image, device="meta")     # shape, dtype and layout are all the backward reads
+        return _preshrink_image(image, size)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return preshrink_image_bwd(dout, ctx.like), None
+
+
+def preshrink_image(image: torch.Tensor, size) -> torch.Tensor:
+    """F.interpolate(image, size, mode="bilinear", align_corners=False) of naf.py:39-48 -> fp32 [B, 3, Hs, Ws].  Differentiable with
+    respect to the image (``PreshrinkFunction``) when autograd is on and the image requires grad."""
+    if torch.is_grad_enabled() and image.requires_grad:
+        _gpu(image, "image")
+        return PreshrinkFunction.apply(image, size)
+    return _preshrink_image(image, size)
+
+
+def _pool_guidance(x: torch.Tensor, output_size) -> torch.Tensor:
     _gpu(x, "x")
     B, Cc, H, W = x.shape
     Ho, Wo = int(output_size[0]), int(output_size[1])
@@ -495,6 +543,50 @@ def pool_guidance(x: torch.Tensor, output_size) -> torch.Tensor:
         rc = lib.naf_pool_guidance(y.data_ptr(), xc.data_ptr(), B, H, W, Ho, Wo, Cc, _stream(x))
     _lib.check(rc, "naf_pool_guidance")
     return y.permute(0, 3, 1, 2)
+
+
+def pool_guidance_bwd(dy: torch.Tensor, in_size) -> torch.Tensor:
+    """Adjoint of ``pool_guidance`` (``naf_pool_guidance_bwd``): dy logical [B, C, Ho, Wo] (any dtype / strides; cast or copied to dense
+    channels-last bf16 only when it is not that already) -> dx, a logical [B, C, H, W] view of a dense channels-last bf16 buffer.
+    Gather form, no atomics: bit-reproducible."""
+    _gpu(dy, "dy")
+    B, Cc, Ho, Wo = dy.shape
+    H, W = int(in_size[0]), int(in_size[1])
+    if Cc % 8:
+        raise ValueError("pool_guidance_bwd: needs C % 8 == 0")
+    dc = dy.permute(0, 2, 3, 1)
+    if dy.dtype != torch.bfloat16 or not dc.is_contiguous():
+        dc = dc.to(torch.bfloat16).contiguous()
+    dx = torch.empty((B, H, W, Cc), dtype=torch.bfloat16, device=dy.device)
+    lib = _lib.load()
+    with torch.cuda.device(dy.device), _Timed("pool_guidance_bwd"):
+        rc = lib.naf_pool_guidance_bwd(dx.data_ptr(), dc.data_ptr(), B, H, W, Ho, Wo, Cc, _stream(dy))
+    _lib.check(rc, "naf_pool_guidance_bwd")
+    return dx.permute(0, 3, 1, 2)
+
+
+class PoolGuidanceFunction(torch.autograd.Function):
+    """Differentiable ``pool_guidance``: forward = naf_pool_guidance, backward = naf_pool_guidance_bwd.  x: logical [B, C, H, W] bf16,
+    channels-last; the gradient comes back in the same layout."""
+
+    @staticmethod
+    def forward(ctx, x, output_size):
+        ctx.size = tuple(x.shape[-2:])
+        return _pool_guidance(x, output_size)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return pool_guidance_bwd(dy, ctx.size), None
+
+
+def pool_guidance(x: torch.Tensor, output_size) -> torch.Tensor:
+    """adaptive_avg_pool2d of the bf16 channels-last guidance [B, C, H, W] (logical) to ``output_size`` (naf.py:34);
+    returns a logical [B, C, Ho, Wo] view of a dense channels-last buffer.  Differentiable (``PoolGuidanceFunction``) when autograd is on
+    and ``x`` requires grad."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        _gpu(x, "x")
+        return PoolGuidanceFunction.apply(x, output_size)
+    return _pool_guidance(x, output_size)
 
 
 def pack_values(v: torch.Tensor) -> torch.Tensor:
