@@ -66,7 +66,9 @@ extern "C" {
  * naf_xna_head_cm_fwd -- that epilogue counting into a confusion matrix (naf_xna_head_cm_args, which embeds naf_xna_head_ce_args unchanged); and after
  * those naf_propagate_select / naf_propagate_fwd / naf_feature_inv_norm -- label propagation for video evaluation (naf_propagate_args); and after
  * those naf_denoise_objective / naf_denoise_workspace_bytes -- the denoising loss with its gradient, and the PSNR / SSIM metrics (naf_denoise_args); and after
- * those naf_feature_moments (+ _workspace_bytes, _plan) / naf_pca_project (+ _workspace_bytes) / naf_pca_minmax -- feature PCA for display. */
+ * those naf_feature_moments (+ _workspace_bytes, _plan) / naf_pca_project (+ _workspace_bytes) / naf_pca_minmax -- feature PCA for display; and after
+ * those naf_xna_mse_supported / naf_xna_mse_workspace_bytes / naf_xna_mse_fwd -- the attention forward with the training objective (mean squared error
+ * against a target) in its epilogue (naf_xna_mse_args, which embeds naf_xna_args unchanged). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -982,6 +984,48 @@ int naf_forward_aux_destroy(naf_forward_aux* aux);
  * stream, 0 / negative as naf_forward_supported. */
 int naf_forward_streams(const naf_forward_args* a, uint32_t flags);
 int naf_forward_ex(const naf_forward_args* a, const naf_forward_aux* aux, uint32_t flags, naf_stream_t stream);
+
+/* ---- attention forward with the training objective in its epilogue (added after the PCA entries; detect by symbol) ----------------
+ * The reference's training step (train.py:127-132) is
+ *     pred = model(img, lr_feats, hr_feats.shape[-2:]);  loss = mse(pred.float(), hr_feats.float())
+ * and the gradient of that loss with respect to pred is (2/N)(pred - hr_feats), N = B*C*Ho*Wo.  The table-driven MFMA kernel
+ * (NAF_XNA_UNION) holds every output element in an fp32 accumulator just before it stores it; this entry subtracts the target there,
+ *     e = acc - target (fp32),   loss = sum e^2 / N,   dout = bf16(e * (2/N))      (2/N applied in fp32, ONE rounding to bf16)
+ * and writes dout where naf_xna_fwd writes out: the prediction, its fp32 copy and the fp32 gradient never exist, and dout -- computed
+ * from the UNROUNDED prediction -- is the `dout` of naf_xna_bwd as it stands.
+ *   a          naf_xna_args as for naf_xna_fwd on the NAF_XNA_UNION path (a.path is ignored: this entry has no other kernel; idx_y / idx_x
+ *              required and canonical; logits and rope_tab_* must be NULL).  a.out is the GRADIENT buffer: [B, heads, Ho, Wo, Dv] by
+ *              o_stride, a.out_dtype must be NAF_BF16.  a.out == NULL: loss only (validation), nothing but loss / workspace is written
+ *   target     device, target_dtype (NAF_F32 / NAF_BF16), logical [B, C, Ho, Wo] with C = heads * Dv (head g owns channels [g*Dv, (g+1)*Dv)),
+ *              ELEMENT strides target_stride = {b, c, y, x}, any values: plain NCHW, a channels-last view (c stride 1: what a ViT wrapper's
+ *              "b (h w) c -> b c h w" gives), a channel slice of a wider tensor.  With c stride 1, the other strides multiples of 4 and the
+ *              pointer 16-byte (fp32) / 8-byte (bf16) aligned a lane's four channels are one load; every other target is read element by
+ *              element.  The pointer must be aligned to its element size (NAF_ERR_INVALID otherwise).  Never written
+ *   loss       device float[1]: sum e^2 / N
+ *   workspace  device, naf_xna_mse_workspace_bytes(a) bytes, 4-byte aligned, caller-owned, needs no clearing: one fp32 partial sum per
+ *              wave of the attention launch.  A second, one-workgroup launch adds them in fp64 in a fixed order and writes loss.  No
+ *              atomics anywhere: two calls on the same inputs give bit-equal loss and dout
+ * naf_xna_mse_supported: 1 when naf_xna_mse_fwd serves the arguments (Dq = 64, Dv % 16 == 0, square odd window 3 .. 15, Ho >= h, Wo >= w,
+ * 16-byte aligned q / k_lr / v_lr / out with the stride rules of NAF_XNA_UNION), else a negative naf_status with naf_last_error():
+ * -NAF_ERR_INVALID for arguments no kernel could serve (NULL q / k_lr / v_lr / target, bad sizes or dtypes, a gradient buffer that is
+ * not bf16, logits or rope_tab_* given, a misaligned target), -NAF_ERR_UNSUPPORTED for a valid request outside the list -- the caller
+ * then composes naf_xna_fwd with its own loss.  A pure host-side query: pointers are checked, never read; idx_y / idx_x, loss and the
+ * workspace are not looked at.  naf_xna_mse_fwd additionally wants idx_y / idx_x, loss and a workspace of at least
+ * naf_xna_mse_workspace_bytes(a) bytes (NAF_ERR_INVALID).  naf_xna_mse_workspace_bytes is 0 for arguments that are not served.
+ * scale <= 0 selects Dq^-0.5.  Caller-owned memory and stream; capturable. */
+typedef struct naf_xna_mse_args {
+    naf_xna_args a; /* a.out: the gradient (bf16) or NULL */
+    const void* target;
+    float* loss;
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t target_dtype; /* naf_dtype */
+    int32_t reserved;     /* must be 0 */
+    int64_t target_stride[4];
+} naf_xna_mse_args;
+int naf_xna_mse_supported(const naf_xna_mse_args* a);
+size_t naf_xna_mse_workspace_bytes(const naf_xna_mse_args* a);
+int naf_xna_mse_fwd(const naf_xna_mse_args* a, naf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ attention filtering forward, behind the reference's own API (valeoai/NAF: src/mo
     from naf_amd import NAF            # same constructor / state_dict as the reference
     naf = NAF().to("cuda").eval()
     hr = naf(image, lr_features, (H, W))
+    loss = naf.train()(image, lr_features, (H, W), regress=hr_features)   # the training step's objective, from the attention kernel
 
 Kernels live in naf_amd/csrc (HIP, C ABI in include/naf_hip.h); build with ``python -m naf_amd.build``.
 """

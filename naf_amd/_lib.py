@@ -72,6 +72,14 @@ class XnaHeadCMArgs(C.Structure):
     _fields_ = [("ce", XnaHeadCEArgs), ("confusion", C.c_void_p), ("cm_stride", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
+class XnaMSEArgs(C.Structure):
+    """naf_xna_mse_args (added after the PCA entries, detected by symbol): naf_xna_args plus the regression target of the training objective."""
+    _fields_ = [
+        ("a", XnaArgs), ("target", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("target_dtype", C.c_int32), ("reserved", C.c_int32), ("target_stride", I64x4),
+    ]
+
+
 PROPAGATE_MAX_FRAMES = 16
 
 
@@ -313,6 +321,9 @@ SIGNATURES = {
     "naf_pca_project_workspace_bytes": (C.c_size_t, [C.POINTER(PcaProjectArgs)]),
     "naf_pca_project": (C.c_int, [C.POINTER(PcaProjectArgs), C.c_void_p]),
     "naf_pca_minmax": (C.c_int, [C.POINTER(PcaMinmaxArgs), C.c_void_p]),
+    "naf_xna_mse_supported": (C.c_int, [C.POINTER(XnaMSEArgs)]),
+    "naf_xna_mse_workspace_bytes": (C.c_size_t, [C.POINTER(XnaMSEArgs)]),
+    "naf_xna_mse_fwd": (C.c_int, [C.POINTER(XnaMSEArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -40,13 +40,31 @@ struct XnaUnionParams {
     int64_t qs[4], ks[4], vs[4], os[4];
 };
 
+// Objective epilogue (P = XnaUnionMseParams, xna_union_mse.hip): the kernel subtracts a regression target from every output element while it is
+// still an fp32 accumulator, adds the squared difference to a per-lane sum and stores the gradient of the mean squared error,
+// bf16((acc - target) * 2/N), where the plain kernel stores the output.  One fp32 partial sum per wave goes to `partial`.
+struct XnaUnionObjective {
+    const void* target;     // [B, C, Ho, Wo] by element strides ts = {b, c, y, x}, C = heads * Dv
+    float* partial;         // [nblocks][NW]
+    int64_t ts[4];
+    float gscale;           // 2 / N
+    int32_t tdtype;         // naf_dtype of target
+    int32_t tvec;           // ts[1] == 1 and every group of four channels is one aligned 8- / 16-byte load
+    int32_t grad;           // 0: loss only, nothing is stored through XnaUnionParams::out
+};
+struct XnaUnionMseParams : XnaUnionParams {
+    XnaUnionObjective o;
+};
+
 // LDS bytes: K and V rectangles (+32 rows that tiles at the right edge read past the end) + the tables
 constexpr size_t xna_union_lds(int ks, int dvt, int ry, int seg, int hub, int wub) {
     return (size_t)(hub * wub + 32) * (72 + dvt + 16) * 2 + (size_t)(seg / 16) * (64 * 8 + 4) + (size_t)ry * (ks + 1) * 4 + 16;
 }
 
-template <int KS, typename OutT, int WT, int NW>
-__global__ __launch_bounds__(NW * 64) void xna_union_kernel(const XnaUnionParams p) {
+// P = XnaUnionParams (the default): the attention output is stored.  P = XnaUnionMseParams: the objective epilogue above.
+template <int KS, typename OutT, int WT, int NW, typename P = XnaUnionParams>
+__global__ __launch_bounds__(NW * 64) void xna_union_kernel(const P p) {
+    constexpr bool OBJ = !std::is_same<P, XnaUnionParams>::value;
     constexpr int NT = NW * 64, KROW = 72;
     constexpr int HH = WT / 16;             // 16-key MFMA tiles per window row
     constexpr int MT = KS * HH;
@@ -204,6 +222,9 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const XnaUnionParams
     const uint32_t v_lane = (uint32_t)((grp * 4 + (col >> 2)) * VROW + (col & 3) * 4) * 2u;
     const uint32_t o_lane = (uint32_t)(col * (int)p.os[3]) * (uint32_t)sizeof(OutT);
     const int CT = p.dvt >> 4;
+    float sq = 0.f;                                                 // OBJ: this lane's sum of squared differences
+    int64_t tbb = 0;                                                // OBJ: element offset of the lane's first target channel
+    if constexpr (OBJ) tbb = b * p.o.ts[0] + (int64_t)((head * p.nchunk + chunk) * p.dvt + grp * 4) * p.o.ts[1];
 
     for (int t = wave; t < ntile; t += NW) {
         bf16x8_t qn[2];
@@ -300,10 +321,47 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const XnaUnionParams
             }
             return acc;
         };
+        // OBJ: e = acc - target in fp32, e^2 into the lane's sum (not for the lanes past the row's end), returns e * 2/N
+        int64_t toff = 0;
+        if constexpr (OBJ) toff = tbb + (int64_t)(y0 + ty) * p.o.ts[2] + (int64_t)min(x0 + tx * 16 + col, p.Wo - 1) * p.o.ts[3];
+        auto objective = [&](int c, f32x4_t acc) __attribute__((always_inline)) {
+            if constexpr (OBJ) {
+                const XnaUnionObjective& o = p.o;
+                f32x4_t tg;
+                if (o.tvec) {
+                    if (o.tdtype == NAF_F32) {
+                        tg = *reinterpret_cast<const f32x4_t*>(static_cast<const float*>(o.target) + toff + c * 16);
+                    } else {
+                        const bf16x4_t tb = *reinterpret_cast<const bf16x4_t*>(static_cast<const bf16_t*>(o.target) + toff + c * 16);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) tg[i] = (float)tb[i];
+                    }
+                } else {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int64_t e = toff + (int64_t)(c * 16 + i) * o.ts[1];
+                        tg[i] = o.tdtype == NAF_F32 ? static_cast<const float*>(o.target)[e] : (float)static_cast<const bf16_t*>(o.target)[e];
+                    }
+                }
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const float e = acc[i] - tg[i];
+                    sq = okv ? fmaf(e, e, sq) : sq;
+                    acc[i] = e * o.gscale;
+                }
+            }
+            return acc;
+        };
+        (void)objective;
         int ct = 0;
         if constexpr (sizeof(OutT) == 2) {
             for (; ct + 1 < CT; ct += 2) {
-                const f32x4_t a0 = pv_tile(ct), a1 = pv_tile(ct + 1);
+                f32x4_t a0 = pv_tile(ct), a1 = pv_tile(ct + 1);
+                if constexpr (OBJ) {
+                    a0 = objective(ct, a0);
+                    a1 = objective(ct + 1, a1);
+                    if (!p.o.grad) continue;
+                }
                 bf16x4_t ab, bb;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -317,7 +375,11 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const XnaUnionParams
             }
         }
         for (; ct < CT; ++ct) {
-            const f32x4_t acc = pv_tile(ct);
+            f32x4_t acc = pv_tile(ct);
+            if constexpr (OBJ) {
+                acc = objective(ct, acc);
+                if (!p.o.grad) continue;
+            }
             if (okv) xna_store4(op + grp * 4 + ct * 16, acc);
         }
 
@@ -326,6 +388,12 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const XnaUnionParams
         qf[1] = qn[1];
     }
     asm volatile("; xna union loop drained" ::"v"(qf[0]), "v"(qf[1]));
+    if constexpr (OBJ) {
+        // the wave's partial sum: a fixed butterfly, one store per wave, no atomics -> bit-reproducible
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) sq += __shfl_xor(sq, m);
+        if (lane == 0) p.o.partial[(size_t)blockIdx.x * NW + wave] = sq;
+    }
 }
 
 // Waves per workgroup: the staged rectangle usually leaves room for one or two workgroups per CU, so the waves that

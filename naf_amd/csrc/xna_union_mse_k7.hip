@@ -1,0 +1,4 @@
+// Instantiations of the table-driven MFMA attention kernel with the regression objective for kernel_size = 7.
+#include "xna_union_mse_kernel.h"
+
+int naf_xna_union_mse_launch_k7(const XnaUnionMseParams& p, int wt, size_t lds, hipStream_t s) { return xna_union_mse_launch_ks<7>(p, wt, lds, s); }

@@ -753,7 +753,7 @@ class NAF(nn.Module):
         """Capture this forward for the given shapes in a hipGraph; see ``GraphedForward``."""
         return GraphedForward(self, image, features, output_size, capture_error_mode=capture_error_mode)
 
-    def forward_train(self, image, features, output_size, amp="auto", return_weights=False):
+    def forward_train(self, image, features, output_size, amp="auto", return_weights=False, regress=None, regress_path="auto"):
         """Differentiable forward for training (train.py:127-137): gradients reach the encoder parameters, the image
         and the features.  The attention and its backward are the HIP kernels (naf_xna_fwd / naf_xna_bwd through
         ``ops.XnaFunction``); the conv stem runs as ``_HipStem`` (HIP forward and backward kernels) or, as the A/B arm, as torch ops
@@ -778,7 +778,16 @@ class NAF(nn.Module):
         explicit A/B arm: ``amp=False`` = fp32 MIOpen convolutions, ``amp=True`` = the reference's ``use_bf16`` mode (bf16 stem
         convolutions under ``torch.autocast``, train.py:120, denoising.py:209; GroupNorm statistics, RoPE and pooling fp32);
         ``stem_impl = "torch"`` makes "auto" choose between those two by the ambient autocast state.  ``amp="hip"`` insists on
-        ``_HipStem`` (raises when the width is not served)."""
+        ``_HipStem`` (raises when the width is not served).
+        ``regress`` / ``regress_path``: the objective of ``forward(..., regress=...)`` -- the call returns the 0-dim fp32 mean squared error
+        against ``regress`` instead of the feature map.  On the HIP branch (``_HipStem`` + ``ops.RopePoolFunction``), where
+        ``ops.xna_mse_auto`` says so (or ``regress_path="fused"`` insists), ``ops.XnaMSEFunction`` stands in place of ``ops.XnaFunction``:
+        the attention kernel's epilogue computes the loss and leaves its gradient for naf_xna_bwd, and nothing of the step between the
+        attention forward and backward is a torch op.  Otherwise: ``F.mse_loss`` on the map this method computes."""
+        if regress is not None and return_weights:
+            raise ValueError("forward_train(regress=...) returns the loss alone: the scores belong to the features' call")
+        if regress_path not in ("auto", "fused", "composed"):
+            raise ValueError(f"regress_path must be 'auto', 'fused' or 'composed', got {regress_path!r}")
         if not (image.is_cuda and features.is_cuda):
             raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback)")
         enc = self.image_encoder
@@ -840,12 +849,29 @@ class NAF(nn.Module):
             B, C = features.shape[:2]
             v5 = features.reshape(B, heads, C // heads, h, w).permute(0, 1, 3, 4, 2).to(torch.bfloat16).contiguous()
             out_dtype = torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32
+            if regress is not None and regress_path != "composed" and C % heads == 0:
+                ksz = self.upsampler.kernel_size
+                if regress_path == "fused":
+                    fused = ops.xna_mse_supported(q5, k5, v5, regress, ksz)
+                    if not fused:
+                        raise ops._lib.NafHipError(f"naf(..., regress_path='fused'): {ops._lib.last_error()}")
+                else:
+                    fused = ops.xna_mse_auto(B, heads, q5.shape[-1], C // heads, (h, w), (ho, wo), ksz, out_dtype, regress) \
+                        and ops.xna_mse_supported(q5, k5, v5, regress, ksz)
+                if fused:
+                    with ops._Timed("attention"):
+                        return ops.XnaMSEFunction.apply(q5, k5, v5, regress, ksz, self.upsampler.scale)
             res = ops.XnaFunction.apply(q5, k5, v5, self.upsampler.kernel_size, self.upsampler.scale, out_dtype, _scores_mode(return_weights))
             out5, logits = res if return_weights else (res, None)
             # [B, heads, Ho, Wo, Dv] is a view of a [B, Ho, Wo, heads * Dv] buffer: hand it out as a logical NCHW view of that
             # (channels-last memory, no transpose copy of the largest tensor of the step)
             out = out5.permute(0, 2, 3, 1, 4).reshape(B, ho, wo, C).permute(0, 3, 1, 2)
+            if regress is not None:
+                return F.mse_loss(out.float(), regress.float())
             return (out, logits) if return_weights else out
+        if regress is not None and regress_path == "fused":
+            raise ops._lib.NafHipError("naf(..., regress_path='fused'): the fused objective follows the HIP stem and ops.RopePoolFunction; this "
+                                       "configuration trains through torch ops there (regress_path='auto' composes the loss)")
         # RoPE (rope.py:15-34,139-153) from the cached tables: angle index t < D/4 -> row, else column
         tab_y, tab_x = rope_tabs()
         B, Cq = x.shape[:2]
@@ -867,10 +893,12 @@ class NAF(nn.Module):
         res = ops.XnaFunction.apply(q5, k5, v5, self.upsampler.kernel_size, self.upsampler.scale, out_dtype, _scores_mode(return_weights))
         out5, logits = res if return_weights else (res, None)
         out = out5.permute(0, 1, 4, 2, 3).reshape(B, C, ho, wo)
+        if regress is not None:
+            return F.mse_loss(out.float(), regress.float())
         return (out, logits) if return_weights else out
 
     def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
-                reduction="mean", predict=False, confusion=None, **kwargs):
+                reduction="mean", predict=False, confusion=None, regress=None, regress_path="auto", **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -921,7 +949,29 @@ class NAF(nn.Module):
         Geometries or class counts the kernel does not serve count the labels of the composed path, same contract.  An empty batch leaves
         the matrix as it was.  Loss and matrix from ONE launch stay available one level down: ``ops.xna_head_objective(..., want_loss=True,
         confusion=cm)``.
-        Not offered: class weights, label smoothing, soft targets, ``capture()`` of this call."""
+        Not offered: class weights, label smoothing, soft targets, ``capture()`` of this call.
+
+        ``regress``, ``regress_path`` (keyword only): the objective of the reference's own training step (train.py:127-132,
+        ``loss = mse(model(img, lr_feats, size).float(), hr_feats.float())``) instead of the feature map.  ``regress`` is a float32 /
+        bfloat16 tensor [B, C, Ho, Wo] on the features' device (any strides: a ViT wrapper's ``b (h w) c -> b c h w`` view is read
+        with vector loads), without a gradient of its own; the call returns the 0-dim fp32 value
+        ``F.mse_loss(naf(image, features, size).float(), regress.float())``.  ``regress_path="auto"`` takes that value from the attention
+        kernel's epilogue (``ops.xna_mse_forward``: the kernel subtracts the target from its fp32 accumulators, writes the loss's gradient
+        in bf16 where it would write the features, and sums the squared error -- the prediction, its fp32 copy and the fp32 gradient never
+        exist) wherever the plain forward of these shapes runs the table-driven MFMA kernel (``naf_xna_select`` says NAF_XNA_UNION: the
+        reference's training geometry 16^2 -> 32^2, non-integer ratios, ratio 1, small integer ratios; head dim 64, C / heads a multiple
+        of 16) and the stem is the HIP stem; everywhere else it is the composed expression above.  ``"fused"`` insists (NafHipError where
+        ``naf_xna_mse_supported`` refuses, or where the torch stem arms run); ``"composed"`` is the A/B arm.  On a gradient-enabled call
+        (as defined above) this is ``forward_train`` with ``ops.XnaMSEFunction`` in place of ``ops.XnaFunction``: ``loss.backward()`` trains
+        the encoder as today's step does, from a ``dout`` that carries one bf16 rounding instead of two.  Without a gradient the inference stem
+        and materialised queries feed the loss-only launch (nothing but the loss is written).  ``regress`` together with ``head``,
+        ``target``, ``predict``, ``confusion`` or ``return_weights`` raises ValueError; shape, dtype and device mismatches raise before any
+        device work.  Not offered: other losses, the reference's unused ``normalize=True``, ``capture()`` of this call."""
+        if regress is not None:
+            if head is not None or target is not None or predict or (confusion is not None and confusion is not False) or return_weights:
+                raise ValueError("naf(..., regress=...) is the regression objective of the features themselves: it does not combine with "
+                                 "head / target / predict / confusion / return_weights")
+            return self._forward_regress(image, features, output_size, regress, regress_path)
         if confusion is not None and confusion is not False:
             if head is None or target is None:
                 raise ValueError("naf(..., confusion=...) is the evaluation of a probe against a target: pass head=probe and target=... as well")
@@ -940,6 +990,41 @@ class NAF(nn.Module):
             return self.forward_train(image, features, output_size, amp="auto", return_weights=return_weights)
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)
+
+    def _forward_regress(self, image, features, output_size, regress, regress_path):
+        """``forward(..., regress=regress)``: see ``forward``."""
+        if regress_path not in ("auto", "fused", "composed"):
+            raise ValueError(f"regress_path must be 'auto', 'fused' or 'composed', got {regress_path!r}")
+        if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, C = features.shape[:2]
+        ops._check_regress_target("naf(..., regress=...)", regress, (B, C, ho, wo), features.device)
+        if not (image.is_cuda and features.is_cuda):
+            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
+                               f"image on {image.device}, features on {features.device}")
+        composed = lambda: F.mse_loss(self.forward(image, features, output_size).float(), regress.float())
+        if regress_path == "composed" or (B == 0 and regress_path == "auto"):
+            return composed()
+        if torch.is_grad_enabled() and (image.requires_grad or features.requires_grad or
+                                        (self.training and any(p.requires_grad for p in self.parameters()))):
+            return self.forward_train(image, features, output_size, amp="auto", regress=regress, regress_path=regress_path)
+        enc, heads, ksz = self.image_encoder, self.upsampler.num_heads, self.upsampler.kernel_size
+        hip_stem = enc.use_encoder and enc.stem_impl == "hip" and enc._hip_stem_ok() and enc.rope.num_heads == heads
+        if regress_path == "auto":
+            out_dtype = torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32
+            if not (hip_stem and C % heads == 0 and B > 0 and
+                    ops.xna_mse_auto(B, heads, enc.out_channels // heads, C // heads, features.shape[-2:], (ho, wo), ksz, out_dtype, regress)):
+                return composed()
+        elif C % heads:
+            raise ValueError(f"feature channels {C} not divisible by {heads} heads")
+        with torch.no_grad():
+            q5, k5, _ = self.guidance_qk(image, features.shape[-2:], (ho, wo))       # materialised queries: the union kernel takes no rotate-on-load
+            h, w = features.shape[-2:]
+            v5 = ops.pack_values(features).view(B, h, w, heads, C // heads).permute(0, 3, 1, 2, 4)
+            with ops._Timed("attention"):
+                loss, _ = ops.xna_mse_forward(q5, k5, v5, regress, ksz, scale=self.upsampler.scale, grad=False)
+        return loss
 
     def _head_call(self, image, features, output_size, return_weights, head, reduction="mean", target=None, confusion=None):
         """Host-side validation the three ``head=`` entries share, in the order they raise (nothing has touched the device yet):

@@ -886,6 +886,150 @@ class XnaFunction(torch.autograd.Function):
                 None, None, None) + (None,) * ctx.nrest
 
 
+# ---- attention forward with the training objective in its epilogue ---------------------------------
+def _check_regress_target(who: str, target, shape, device) -> None:
+    """Host-side checks of a regression target against the prediction's [B, C, Ho, Wo] (nothing touches the device)."""
+    if not isinstance(target, torch.Tensor):
+        raise TypeError(f"{who}: the target must be a tensor, got {type(target).__name__}")
+    if target.dtype not in _DT:
+        raise TypeError(f"{who}: the target must be float32 or bfloat16, got {target.dtype}")
+    if tuple(target.shape) != tuple(shape):
+        raise ValueError(f"{who}: target shape {tuple(target.shape)} != prediction shape {tuple(shape)}")
+    if target.requires_grad:
+        raise ValueError(f"{who}: the target gets no gradient; detach it")
+    if target.device != device:
+        raise ValueError(f"{who}: the target is on {target.device}, the features on {device}")
+
+
+def _check_mse_operands(who: str, q, k_lr, v_lr, target) -> None:
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
+        if t.dtype != torch.bfloat16:
+            raise TypeError(f"{who}: {n} must be bfloat16, got {t.dtype}")
+        if t.dim() != 5 or t.stride(4) != 1:
+            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    B, heads, Ho, Wo, Dq = q.shape
+    _, _, h, w, Dv = v_lr.shape
+    if tuple(k_lr.shape) != (B, heads, h, w, Dq) or v_lr.shape[:2] != (B, heads):
+        raise ValueError(f"{who}: k_lr shape {tuple(k_lr.shape)} / v_lr shape {tuple(v_lr.shape)} do not match q {tuple(q.shape)}")
+    _check_regress_target(who, target, (B, heads * Dv, Ho, Wo), q.device)
+
+
+def _fill_xna_mse(q, k_lr, v_lr, target, dout, ky, kx, scale) -> "_lib.XnaMSEArgs":
+    B, heads, Ho, Wo, _ = q.shape
+    Dv = v_lr.shape[-1]
+    m = _lib.XnaMSEArgs()
+    m.a = _fill_xna(q, k_lr, v_lr, dout if dout is not None else q, None, None, None, ky, kx, "union", scale)
+    m.a.out_dtype = _lib.NAF_BF16
+    if dout is None:
+        m.a.out = None
+        m.a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    m.target, m.target_dtype = target.data_ptr(), _DT[target.dtype]
+    m.target_stride = _strides4(target, (0, 1, 2, 3))
+    return m
+
+
+def xna_mse_supported(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, target: torch.Tensor, kernel_size) -> bool:
+    """True when ``xna_mse_forward`` serves these operands (``naf_xna_mse_supported``: the table-driven MFMA kernel's shapes -- Dq = 64,
+    Dv % 16 == 0, square odd window 3 .. 15, any ratio >= 1).  Operands of the wrong kind raise as they do there."""
+    _check_mse_operands("xna_mse_supported", q, k_lr, v_lr, target)
+    ky, kx = _ksize(kernel_size)
+    return _lib.load().naf_xna_mse_supported(C.byref(_fill_xna_mse(q, k_lr, v_lr, target, None, ky, kx, None))) == 1
+
+
+def xna_mse_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, target: torch.Tensor, kernel_size, *,
+                    scale: Optional[float] = None, grad: bool = True, out: Optional[torch.Tensor] = None):
+    """The training objective of the reference's step (train.py:127-132) from the attention kernel's epilogue:
+    ``loss = F.mse_loss(xna_forward(q, k_lr, v_lr).float(), target.float())`` as a 0-dim fp32 tensor, and with ``grad`` its gradient with
+    respect to the attention output, ``dout5`` -- a [B, heads, Ho, Wo, Dv] bf16 view of a [B, Ho, Wo, C] buffer that ``xna_backward``
+    takes as it is.  The prediction is never written: the kernel subtracts the target from its fp32 accumulators, so ``dout5`` carries
+    one bf16 rounding (of (out - target) * 2/N) instead of the two of the composed step.  ``grad=False``: loss only, nothing else is
+    written (validation; ``out`` together with ``grad=False`` raises ValueError).  ``target``: float32 / bfloat16, logical [B, heads * Dv, Ho, Wo], any strides (channels-last views are read
+    with vector loads).  ``out``: an existing [B, heads, Ho, Wo, Dv] bf16 buffer for ``dout5`` (Dv contiguous).  Two calls on the same
+    operands are bit-equal.  Raises NafHipError where ``xna_mse_supported`` says no (no fallback here)."""
+    who = "xna_mse_forward"
+    _check_mse_operands(who, q, k_lr, v_lr, target)
+    if out is not None and not grad:
+        raise ValueError(f"{who}: out is the gradient's buffer; with grad=False nothing is written")
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr"), (target, "target")):
+        _gpu(t, n)
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, Dq = q.shape
+    _, _, h, w, Dv = v_lr.shape
+    dev = q.device
+    dout = None
+    if grad:
+        dout = out if out is not None else torch.empty((B, Ho, Wo, heads, Dv), dtype=torch.bfloat16, device=dev).permute(0, 3, 1, 2, 4)
+        if tuple(dout.shape) != (B, heads, Ho, Wo, Dv) or dout.dtype != torch.bfloat16 or dout.stride(4) != 1 or dout.device != dev:
+            raise ValueError(f"{who}: out must be a bfloat16 [B, heads, Ho, Wo, Dv] buffer on q's device with Dv contiguous")
+    m = _fill_xna_mse(q, k_lr, v_lr, target, dout, ky, kx, scale)
+    ok = lib.naf_xna_mse_supported(C.byref(m))
+    if ok != 1:
+        _lib.check(-ok, "naf_xna_mse_supported")
+    iy = device_index_table(Ho, h, ky, dev)
+    ix = device_index_table(Wo, w, kx, dev)
+    m.a.idx_y, m.a.idx_x = iy.data_ptr(), ix.data_ptr()
+    ws = torch.empty(int(lib.naf_xna_mse_workspace_bytes(C.byref(m))), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    m.workspace, m.workspace_bytes, m.loss = ws.data_ptr(), ws.numel(), loss.data_ptr()
+    with torch.cuda.device(dev), _Timed("xna_union_mse"):
+        rc = lib.naf_xna_mse_fwd(C.byref(m), _stream(q))
+    _lib.check(rc, "naf_xna_mse_fwd")
+    return loss, dout
+
+
+def xna_mse_auto(B: int, heads: int, Dq: int, Dv: int, lr_size, out_size, kernel_size, out_dtype, target: torch.Tensor) -> bool:
+    """The rule of ``naf(..., regress=..., regress_path="auto")``, from shapes alone (nothing is dereferenced): True where
+    ``naf_xna_select`` runs the table-driven MFMA kernel for the plain forward of these shapes (dense channels-last operands) -- the
+    fused objective is then the same kernel with another epilogue -- and ``naf_xna_mse_supported`` takes the target."""
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    h, w = int(lr_size[0]), int(lr_size[1])
+    Ho, Wo = int(out_size[0]), int(out_size[1])
+    if out_dtype not in _DT or target.dtype not in _DT:
+        return False
+    m = _lib.XnaMSEArgs()
+    a = m.a
+    a.q = a.k_lr = a.v_lr = a.out = 4096               # shape / alignment query only
+    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
+    a.out_dtype, a.path, a.scale = _DT[out_dtype], _lib.XNA_AUTO, 0.0
+    a.q_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
+    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
+    a.v_stride = I64x4(h * w * heads * Dv, Dv, w * heads * Dv, heads * Dv)
+    a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    if lib.naf_xna_select(C.byref(a)) != _lib.XNA_UNION:
+        return False
+    a.out_dtype = _lib.NAF_BF16
+    m.target, m.target_dtype = target.data_ptr() or 4096, _DT[target.dtype]
+    m.target_stride = _strides4(target, (0, 1, 2, 3))
+    return lib.naf_xna_mse_supported(C.byref(m)) == 1
+
+
+class XnaMSEFunction(torch.autograd.Function):
+    """``loss = mse(xna(q, k_lr, v_lr), target)`` as one differentiable node: forward = naf_xna_mse_fwd (the attention launch and the
+    one-workgroup sum), which leaves the loss's gradient with respect to the attention output in bf16; backward = naf_xna_bwd on that
+    buffer as it stands, its three results scaled by the incoming scalar on the device (no host synchronisation; they are smaller than
+    dout).  The target gets no gradient."""
+
+    @staticmethod
+    def forward(ctx, q, k_lr, v_lr, target, kernel_size, scale):
+        loss, dout5 = xna_mse_forward(q, k_lr, v_lr, target, kernel_size, scale=scale, grad=True)
+        ctx.save_for_backward(q, k_lr, v_lr, dout5)
+        ctx.kernel_size, ctx.scale = kernel_size, scale
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        if not any(ctx.needs_input_grad[:3]):
+            return (None,) * 6
+        q, k_lr, v_lr, dout5 = ctx.saved_tensors
+        dq, dk, dv = xna_backward(q, k_lr, v_lr, dout5, ctx.kernel_size, scale=ctx.scale)
+        g = dloss.detach().to(torch.float32).reshape(())
+        need = ctx.needs_input_grad
+        return ((dq.mul_(g) if need[0] else None), (dk.mul_(g).to(k_lr.dtype) if need[1] else None),
+                (dv.mul_(g).to(v_lr.dtype) if need[2] else None), None, None, None)
+
+
 # ---- attention with a linear head folded in ------------------------------------------------------
 _HEAD_PATHS = ("auto", "fused", "composed")
 _BWD_DV = (32, 64, 96, 128, 192, 256)      # value widths the cell backward serves (naf_xna_bwd)
@@ -1381,6 +1525,23 @@ def xna_select(q, k_lr, v_lr, kernel_size, out_dtype=torch.bfloat16, return_logi
     if sel < 0:
         _lib.check(-sel, "naf_xna_select")
     return _PATH_NAME[sel]
+
+
+def xna_union_plan(q, k_lr, v_lr, kernel_size) -> Optional[Dict[str, int]]:
+    """The workgroup plan of the table-driven MFMA kernel for these operands (``naf_xna_union_plan``), or None where it does not serve
+    them: slots per window row ``wt``, output rows ``ry`` and pixels ``seg`` per workgroup, the staged rectangle ``hub`` x ``wub``, value
+    channels per workgroup ``dvt``, LDS bytes ``lds`` -- for tools and tests."""
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, _ = q.shape
+    Dv = v_lr.shape[-1]
+    a = _fill_xna(q, k_lr, v_lr, q, None, None, None, ky, kx, "auto", None)
+    a.out_dtype = _lib.NAF_BF16
+    a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    out = (C.c_int32 * 7)()
+    if lib.naf_xna_union_plan(C.byref(a), out) != 1:
+        return None
+    return dict(zip(("wt", "ry", "seg", "hub", "wub", "dvt", "lds"), (int(x) for x in out)))
 
 
 # ------------------------------------------------------------------------------------------------
