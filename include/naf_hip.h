@@ -85,7 +85,9 @@ extern "C" {
 
 typedef void* naf_stream_t; /* hipStream_t */
 
-enum naf_dtype { NAF_BF16 = 0, NAF_F32 = 1 };
+/* NAF_F16 (IEEE half): only where naf_dtype_supported says so -- the VALUES and the output of the attention forward.  Every other
+ * dtype field of this header keeps taking NAF_BF16 / NAF_F32 and rejects it. */
+enum naf_dtype { NAF_BF16 = 0, NAF_F32 = 1, NAF_F16 = 2 };
 
 enum naf_status {
     NAF_OK = 0,
@@ -112,6 +114,23 @@ const char* naf_last_error(void);
 /* NAF_OK when a host compiled against a header of version `header_version` (pass NAF_HIP_VERSION) may call this library:
  * same major and minor version.  NAF_ERR_INVALID (with the two versions in naf_last_error()) otherwise.  0.4.0. */
 int naf_abi_check(int header_version);
+/* Which dtypes an argument takes (new entry point; detect by symbol, version number unchanged): 1 when argument `what` accepts
+ * naf_dtype `dtype`, 0 when it does not (or `what` is unknown).  A library without this symbol knows no NAF_F16 anywhere.
+ * Half values through the attention forward (naf_xna_fwd with out_dtype NAF_F16; naf_forward with feat_dtype = out_dtype = NAF_F16):
+ * the values are read as IEEE half and never rounded to bf16, the PV product runs on v_mfma_f32_16x16x32_f16 with fp32
+ * accumulation and the output is stored as half.  Queries, keys, the stem, RoPE and the scores are bf16 / fp32 as for the other dtypes.
+ * No subnormal OPERAND is relied on: the softmax weights are multiplied by 2^8 before they are rounded to half and the fp32
+ * accumulator (or normaliser) by 2^-8 before the store, both exact, so a weight only vanishes below 2^-22.  Per element, against the
+ * exact result on the same half values: |err| <= 1.25 * 2^-11 * (sum_j p_j |v_j| + |ref|) + k*k * 2^-22 * max|v| + 2^-14 (one rounding
+ * of P plus the store; every window weight flushed; subnormal values flushed).  Half and bf16 / fp32 never mix in one call. */
+enum naf_dtype_arg {
+    NAF_DT_XNA_VALUES = 0,   /* naf_xna_args.v_lr: NAF_BF16, or NAF_F16 (then out_dtype must be NAF_F16 too) */
+    NAF_DT_XNA_OUT = 1,      /* naf_xna_args.out_dtype: NAF_BF16 / NAF_F32 (bf16 values), NAF_F16 (half values) */
+    NAF_DT_PACK_SRC = 2,     /* naf_pack_values v_dtype: NAF_BF16 / NAF_F32 -> bf16, NAF_F16 -> half (an exact copy) */
+    NAF_DT_FWD_FEAT = 3,     /* naf_forward_args.feat_dtype */
+    NAF_DT_FWD_OUT = 4       /* naf_forward_args.out_dtype (NAF_F16 exactly when feat_dtype is) */
+};
+int naf_dtype_supported(int what, int dtype);
 
 /* ---- host helper: which low-res rows/cols a hi-res query attends to (one axis) ------------------
  * Replaces, for one axis, NATTEN's neighbourhood rule composed with the reference's nearest-exact
@@ -414,7 +433,8 @@ int naf_preshrink_image_bwd(void* dimage, const float* dout, int32_t image_dtype
 /* ---- value packing --------------------------------------------------------------------------------
  * Replaces the rearrange + dtype cast of the value tensor in CrossAttention._resize
  * (attentions.py:50-51) WITHOUT the nearest-exact upsampling (values stay low-res).
- *   v  device, v_dtype, logical [B, C, h, w], strides {b, c, y, x};   vp device bf16 [B, h, w, C] dense. */
+ *   v  device, v_dtype, logical [B, C, h, w], strides {b, c, y, x};   vp device bf16 [B, h, w, C] dense.
+ *   v_dtype NAF_F16: vp is IEEE half [B, h, w, C] dense, an exact copy (what naf_xna_fwd reads with out_dtype NAF_F16). */
 int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t C, int32_t h, int32_t w,
                     const int64_t v_stride[4], naf_stream_t stream);
 
@@ -440,6 +460,9 @@ int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t
  *          rotated queries never make a round trip through HBM (pair with naf_rope_pool_fwd(q = NULL) for the
  *          keys).  Only the MFMA path with Wo/w a multiple of 16 serves this; naf_xna_select reports
  *          NAF_ERR_UNSUPPORTED otherwise and the caller falls back to materialised queries.  NULL = off.
+ * out_dtype NAF_F16 (naf_dtype_supported): v_lr holds IEEE half and `out` receives half -- the struct has no value dtype of its own,
+ *          half values with any other out_dtype cannot be expressed and hosts must reject them.  Every path serves it, and
+ *          naf_xna_select picks the kernel it picks for NAF_BF16 output of the same geometry.  q, k_lr, logits: as above.
  * scale <= 0 selects the reference default Dq^-0.5 (attentions.py:46). */
 typedef struct naf_xna_args {
     const void* q;
@@ -864,8 +887,10 @@ int naf_xna_bwd_scores(const naf_xna_bwd_args* a, const naf_xna_bwd_scores_args*
  * attention runs on a table-driven kernel the index tables are built in the workspace by
  * naf_axis_index_table_device.  The call is capturable in a hipGraph (no host-side copies, no allocation).
  *   image     device [B, 3, H, W] f32/bf16, strides {b, c, y, x}
- *   features  device [B, C, h, w] f32/bf16, strides {b, c, y, x}
- *   out       device out_dtype, dense channels-last [B, Ho, Wo, C] (logical [B, C, Ho, Wo] view for the caller)
+ *   features  device [B, C, h, w] f32/bf16/half, strides {b, c, y, x}
+ *   out       device out_dtype, dense channels-last [B, Ho, Wo, C] (logical [B, C, Ho, Wo] view for the caller);
+ *             feat_dtype NAF_F16 goes with out_dtype NAF_F16 and only with it (NAF_ERR_INVALID otherwise): the packed values in
+ *             the workspace are half (same bytes), see naf_dtype_supported
  *   branch[i] parameters of encoder / sem_encoder (naf.py:26-27): conv0 weight f32 [128][3][k0][k0] + bias, then
  *             per block layer l < nlayer: GroupNorm weight / bias f32 [128], conv weight packed bf16
  *             [k*k][128][128] (= weight.permute(2,3,0,1)) and bias f32 [128]

@@ -17,6 +17,8 @@ LIB_PATH = os.environ.get("NAF_HIP_LIB") or os.path.join(os.path.dirname(os.path
 
 HEADER_VERSION = 403          # NAF_HIP_VERSION of the include/naf_hip.h these ctypes mirrors were written against
 NAF_BF16, NAF_F32 = 0, 1
+NAF_F16 = 2     # IEEE half: values / output of the attention forward only (naf_dtype_supported)
+DT_XNA_VALUES, DT_XNA_OUT, DT_PACK_SRC, DT_FWD_FEAT, DT_FWD_OUT = range(5)     # naf_dtype_arg
 XNA_AUTO, XNA_MFMA, XNA_GENERIC, XNA_UNION, XNA_ROWS = 0, 1, 2, 3, 4
 XNA_HEAD_AUTO, XNA_HEAD_FUSED = 0, 1            # naf_xna_head_path
 
@@ -270,6 +272,7 @@ SIGNATURES = {
     "naf_version": (C.c_int, []),
     "naf_last_error": (C.c_char_p, []),
     "naf_abi_check": (C.c_int, [C.c_int]),
+    "naf_dtype_supported": (C.c_int, [C.c_int, C.c_int]),
     "naf_stem_stats_bytes": (C.c_size_t, [C.c_int32]),
     "naf_forward_aux_create": (C.c_int, [C.POINTER(ForwardAux)]),
     "naf_forward_aux_destroy": (C.c_int, [C.POINTER(ForwardAux)]),

@@ -58,6 +58,18 @@ extern "C" {
 
 int naf_version(void) { return NAF_HIP_VERSION; }
 
+int naf_dtype_supported(int what, int dtype) {
+    const bool base = dtype == NAF_BF16 || dtype == NAF_F32, half = dtype == NAF_F16;
+    switch (what) {
+        case NAF_DT_XNA_VALUES: return (dtype == NAF_BF16 || half) ? 1 : 0;
+        case NAF_DT_XNA_OUT:
+        case NAF_DT_PACK_SRC:
+        case NAF_DT_FWD_FEAT:
+        case NAF_DT_FWD_OUT: return (base || half) ? 1 : 0;
+    }
+    return 0;
+}
+
 int naf_abi_check(int header_version) {
     NAF_REQUIRE(header_version / 100 == NAF_HIP_VERSION / 100,
                 "naf_abi_check: the host was compiled against naf_hip.h %d.%d.%d, this library is %d.%d.%d: argument structs and buffer "
@@ -129,7 +141,7 @@ int naf_rope_pool_fwd(const naf_rope_pool_args* a, naf_stream_t stream) {
 int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t C, int32_t h, int32_t w,
                     const int64_t v_stride[4], naf_stream_t stream) {
     NAF_REQUIRE(vp && v && v_stride, "naf_pack_values: NULL pointer");
-    NAF_REQUIRE(v_dtype == NAF_BF16 || v_dtype == NAF_F32, "naf_pack_values: v_dtype %d", v_dtype);
+    NAF_REQUIRE(naf_dtype_supported(NAF_DT_PACK_SRC, v_dtype), "naf_pack_values: v_dtype %d", v_dtype);
     NAF_REQUIRE(B > 0 && C > 0 && h > 0 && w > 0, "naf_pack_values: non-positive size");
     return naf_launch_pack_values(vp, v, v_dtype, B, C, h, w, v_stride, static_cast<hipStream_t>(stream));
 }
@@ -315,7 +327,7 @@ static int xna_validate(const naf_xna_args* a) {
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->out, "naf_xna_fwd: NULL tensor pointer");
     const int rc = xna_geometry_validate("naf_xna_fwd", a, a->Dv);
     if (rc != NAF_OK) return rc;
-    NAF_REQUIRE(a->out_dtype == NAF_BF16 || a->out_dtype == NAF_F32, "naf_xna_fwd: out_dtype %d", a->out_dtype);
+    NAF_REQUIRE(naf_dtype_supported(NAF_DT_XNA_OUT, a->out_dtype), "naf_xna_fwd: out_dtype %d", a->out_dtype);
     NAF_REQUIRE(a->path == NAF_XNA_AUTO || a->path == NAF_XNA_MFMA || a->path == NAF_XNA_GENERIC || a->path == NAF_XNA_UNION || a->path == NAF_XNA_ROWS, "naf_xna_fwd: path %d", a->path);
     NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_fwd: rope_tab_y and rope_tab_x must be given together");
     return NAF_OK;
@@ -775,7 +787,11 @@ int naf_forward_supported(const naf_forward_args* a) {
     const int rc = fwd_validate(a);
     if (rc != NAF_OK) return -rc;
     const int hr = a->heads_rope > 0 ? a->heads_rope : a->heads;
-    if (256 % (4 * hr) != 0 || 256 % a->heads != 0 || (a->out_dtype != NAF_BF16 && a->out_dtype != NAF_F32)) return 0;
+    if ((a->feat_dtype == NAF_F16) != (a->out_dtype == NAF_F16)) {
+        naf_set_error("naf_forward: half features go with half output and only with it (feat_dtype %d, out_dtype %d)", a->feat_dtype, a->out_dtype);
+        return -NAF_ERR_INVALID;
+    }
+    if (256 % (4 * hr) != 0 || 256 % a->heads != 0 || !naf_dtype_supported(NAF_DT_FWD_OUT, a->out_dtype)) return 0;
     const int Ho = a->Ho > 0 ? a->Ho : a->H, Wo = a->Wo > 0 ? a->Wo : a->W;
     if (a->H < 2 || a->W < 2 || Ho < a->h || Wo < a->w) return 0;
     {

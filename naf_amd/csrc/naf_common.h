@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "naf_hip.h"
 
 typedef __bf16 bf16_t;
@@ -15,7 +17,40 @@ typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 
+typedef _Float16 f16_t;
+typedef f16_t f16x8_t __attribute__((ext_vector_type(8)));
+
 #define NAF_LDS __attribute__((address_space(3)))
+
+// ---- the VALUE type of the attention forward kernels, chosen by their output type ----
+// OutT = bf16_t / float: bf16 values, P rounded to bf16, v_mfma_f32_16x16x32_bf16 (what the kernels have always done).
+// OutT = f16_t (NAF_F16): the values in memory and in the LDS are IEEE half, P is rounded to half, the PV product runs on
+// v_mfma_f32_16x16x32_f16 (same lane maps, same rate) and the output is stored as half.  The kernels keep every 16-bit operand in
+// bf16-typed registers -- loads, LDS transposes and lane exchanges move bits -- so only the three places below know the type.
+// Half has 5 exponent bits: a softmax weight below 2^-14 would be a subnormal operand, and whether the matrix pipe honours those
+// is not something the kernels rely on.  P is therefore multiplied by PSCALE = 2^8 before it is rounded (P <= 1 -> at most 256; the
+// un-normalised weights of the row-streaming kernel are at most k*k * 2^8 < 65504) and the fp32 accumulator -- or the fp32
+// normaliser -- is multiplied by 2^-8 before the store.  Both are exact, and a weight only vanishes below 2^-22.
+template <typename OutT>
+struct XnaVal {
+    static constexpr bool F16 = std::is_same<OutT, f16_t>::value;
+    static constexpr float PSCALE = F16 ? 256.f : 1.f;       // applied to P (through the normaliser) before the rounding
+    static constexpr float UNSCALE = F16 ? 1.f / 256.f : 1.f;  // applied to the accumulator (or the normaliser) before the store
+    // P -> the 16-bit B / A operand (the caller has applied PSCALE)
+    __device__ static __forceinline__ bf16_t p(float x) {
+        if constexpr (F16) return __builtin_bit_cast(bf16_t, (f16_t)x);
+        else return (bf16_t)x;
+    }
+    // accumulator -> the 16-bit stored element (applies UNSCALE)
+    __device__ static __forceinline__ bf16_t o(float x) {
+        if constexpr (F16) return __builtin_bit_cast(bf16_t, (f16_t)(x * UNSCALE));
+        else return (bf16_t)x;
+    }
+    __device__ static __forceinline__ f32x4_t mfma(bf16x8_t a, bf16x8_t b, f32x4_t c) {
+        if constexpr (F16) return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
+        else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
+    }
+};
 
 // ---- error plumbing (naf_api.cpp owns the storage) ----
 void naf_set_error(const char* fmt, ...);

@@ -1,10 +1,10 @@
-// Value packing: [B, C, h, w] (any strides, f32 or bf16) -> dense channels-last bf16 [B, h, w, C].
+// Value packing: [B, C, h, w] (any strides, f32 or bf16) -> dense channels-last bf16 [B, h, w, C]; half -> half, an exact copy.
 // Replaces the rearrange + cast of CrossAttention._resize (attentions.py:50-51); the nearest-exact
 // upsampling of attentions.py:49 is NOT performed -- values stay on the low-res grid.
 #include "naf_common.h"
 
-template <typename T>
-__global__ __launch_bounds__(256) void pack_values_kernel(bf16_t* __restrict__ vp, const T* __restrict__ v, int B, int C,
+template <typename T, typename D = bf16_t>
+__global__ __launch_bounds__(256) void pack_values_kernel(D* __restrict__ vp, const T* __restrict__ v, int B, int C,
                                                           int h, int w, int64_t sb, int64_t sc, int64_t sy, int64_t sx) {
     // tile: 32 channels x 32 positions (x fastest on the read side, c fastest on the write side)
     __shared__ float tile[32][33];
@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void pack_values_kernel(bf16_t* __restrict__ v
     for (int i = 0; i < 4; ++i) {
         const int64_t pos = p0 + ty + i * 8;
         const int c = c0 + tx;
-        if (c < C && pos < npos) vp[((int64_t)b * npos + pos) * C + c] = (bf16_t)tile[tx][ty + i * 8];
+        if (c < C && pos < npos) vp[((int64_t)b * npos + pos) * C + c] = (D)tile[tx][ty + i * 8];
     }
 }
 
@@ -41,7 +41,10 @@ int naf_launch_pack_values(void* vp, const void* v, int v_dtype, int B, int C, i
         naf_set_error("naf_pack_values: grid out of range (C=%d, B=%d)", C, B);
         return NAF_ERR_INVALID;
     }
-    if (v_dtype == NAF_BF16)
+    if (v_dtype == NAF_F16)   // half -> fp32 tile -> half: both conversions are exact
+        hipLaunchKernelGGL((pack_values_kernel<f16_t, f16_t>), g, blk, 0, s, static_cast<f16_t*>(vp),
+                           static_cast<const f16_t*>(v), B, C, h, w, vs[0], vs[1], vs[2], vs[3]);
+    else if (v_dtype == NAF_BF16)
         hipLaunchKernelGGL(pack_values_kernel<bf16_t>, g, blk, 0, s, static_cast<bf16_t*>(vp),
                            static_cast<const bf16_t*>(v), B, C, h, w, vs[0], vs[1], vs[2], vs[3]);
     else

@@ -38,6 +38,8 @@ __device__ __forceinline__ float wave_max(float v) {
     return v;
 }
 
+// F16 (out_dtype NAF_F16): the values are IEEE half and so is the output; everything in between is fp32 as before
+template <bool F16>
 __global__ __launch_bounds__(256) void xna_generic_kernel(const XnaGenericParams p) {
     extern __shared__ __attribute__((aligned(16))) float lg_all[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -95,10 +97,13 @@ __global__ __launch_bounds__(256) void xna_generic_kernel(const XnaGenericParams
         for (int key = 0; key < KK; ++key) {
             const int ty = key / p.kx, tx = key - ty * p.kx;
             const bf16_t* vp = vb + (int64_t)iy[ty] * p.vs[2] + (int64_t)ix[tx] * p.vs[3];
-            acc = fmaf(lg[key], (float)vp[c], acc);
+            if constexpr (F16) acc = fmaf(lg[key], (float)reinterpret_cast<const f16_t*>(vp)[c], acc);
+            else acc = fmaf(lg[key], (float)vp[c], acc);
         }
         acc *= inv;
-        if (p.out_dtype == NAF_BF16)
+        if constexpr (F16)
+            reinterpret_cast<f16_t*>(p.out)[obase + c] = (f16_t)acc;
+        else if (p.out_dtype == NAF_BF16)
             reinterpret_cast<bf16_t*>(p.out)[obase + c] = (bf16_t)acc;
         else
             reinterpret_cast<float*>(p.out)[obase + c] = acc;
@@ -135,7 +140,8 @@ int naf_launch_xna_generic(const naf_xna_args* a, float scale, hipStream_t s) {
         naf_set_error("naf_xna_fwd: kernel %dx%d too large for the table-driven kernel", a->ky, a->kx);
         return NAF_ERR_UNSUPPORTED;
     }
-    hipLaunchKernelGGL(xna_generic_kernel, dim3((uint32_t)nb), dim3(256), lds, s, p);
+    if (a->out_dtype == NAF_F16) hipLaunchKernelGGL(xna_generic_kernel<true>, dim3((uint32_t)nb), dim3(256), lds, s, p);
+    else hipLaunchKernelGGL(xna_generic_kernel<false>, dim3((uint32_t)nb), dim3(256), lds, s, p);
     return naf_check_launch("xna_generic_kernel");
 }
 

@@ -6,6 +6,13 @@
 #define NAF_DECL(K) int naf_xna_mfma_launch_k##K(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s);
 NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
 #undef NAF_DECL
+// half values and output (NAF_F16): xna_mfma_h_k*.hip / xna_slide_h_k*.hip
+#define NAF_DECL(K) int naf_xna_mfma_launch_h_k##K(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s);
+NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
+#undef NAF_DECL
+#define NAF_DECL(K) int naf_xna_slide_launch_h_k##K(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
+NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
+#undef NAF_DECL
 int naf_xna_slide_launch_k7(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
 int naf_xna_slide_launch_k9(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
 int naf_xna_slide_launch_k11(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
@@ -117,12 +124,32 @@ int naf_launch_xna_mfma(const naf_xna_args* a, float scale, hipStream_t s) {
         sp.m.nblocks = (uint32_t)nbs;
         // (A tail hand-over -- finished workgroups claiming the last cells of other segments -- was built, bit-identical and 2-6 % slower at
         // G2-k11: profiles/r06_other_workloads.txt.  The split of a cell row into segments is static.)
+        if (a->out_dtype == NAF_F16) {
+            switch (a->ky) {
+                case 7: return naf_xna_slide_launch_h_k7(sp, dvt_u, a->out_dtype, s);
+                case 9: return naf_xna_slide_launch_h_k9(sp, dvt_u, a->out_dtype, s);
+                case 11: return naf_xna_slide_launch_h_k11(sp, dvt_u, a->out_dtype, s);
+                case 13: return naf_xna_slide_launch_h_k13(sp, dvt_u, a->out_dtype, s);
+                case 15: return naf_xna_slide_launch_h_k15(sp, dvt_u, a->out_dtype, s);
+            }
+        }
         switch (a->ky) {
             case 7: return naf_xna_slide_launch_k7(sp, dvt_u, a->out_dtype, s);
             case 9: return naf_xna_slide_launch_k9(sp, dvt_u, a->out_dtype, s);
             case 11: return naf_xna_slide_launch_k11(sp, dvt_u, a->out_dtype, s);
             case 13: return naf_xna_slide_launch_k13(sp, dvt_u, a->out_dtype, s);
             case 15: return naf_xna_slide_launch_k15(sp, dvt_u, a->out_dtype, s);
+        }
+    }
+    if (a->out_dtype == NAF_F16) {
+        switch (a->ky) {
+            case 3: return naf_xna_mfma_launch_h_k3(p, pl, a->out_dtype, s);
+            case 5: return naf_xna_mfma_launch_h_k5(p, pl, a->out_dtype, s);
+            case 7: return naf_xna_mfma_launch_h_k7(p, pl, a->out_dtype, s);
+            case 9: return naf_xna_mfma_launch_h_k9(p, pl, a->out_dtype, s);
+            case 11: return naf_xna_mfma_launch_h_k11(p, pl, a->out_dtype, s);
+            case 13: return naf_xna_mfma_launch_h_k13(p, pl, a->out_dtype, s);
+            case 15: return naf_xna_mfma_launch_h_k15(p, pl, a->out_dtype, s);
         }
     }
     switch (a->ky) {

@@ -129,6 +129,15 @@ __device__ __forceinline__ void xna_store4(bf16_t* dst, f32x4_t v) {
     *reinterpret_cast<bf16x4_t*>(dst) = o;
 }
 __device__ __forceinline__ void xna_store4(float* dst, f32x4_t v) { *reinterpret_cast<f32x4_t*>(dst) = v; }
+// half output: the accumulator still carries the 2^8 prescale of P (XnaVal in naf_common.h)
+__device__ __forceinline__ void xna_store4(f16_t* dst, f32x4_t v) {
+    bf16x4_t o;
+    o[0] = XnaVal<f16_t>::o(v[0]);
+    o[1] = XnaVal<f16_t>::o(v[1]);
+    o[2] = XnaVal<f16_t>::o(v[2]);
+    o[3] = XnaVal<f16_t>::o(v[3]);
+    *reinterpret_cast<bf16x4_t*>(dst) = o;
+}
 
 // ABL: ablation bits for tools/xna_probe.hip only (the library instantiates ABL = 0):
 //   1 no output stores, 2 no PV MFMAs / V reads, 4 no Q loads, 8 no K/V staging loads, 16 no QK MFMAs,
@@ -619,14 +628,15 @@ __global__ __launch_bounds__(NW * 64) void xna_mfma_kernel(const XnaMfmaParams p
                         sum += e;
                     }
                 sum = naf_rows_sum(sum);
-                const float inv = __builtin_amdgcn_rcpf(sum);   // sum >= 1 (the max slot contributes exp2(0))
+                float inv = __builtin_amdgcn_rcpf(sum);   // sum >= 1 (the max slot contributes exp2(0))
+                if constexpr (XnaVal<OutT>::F16) inv *= XnaVal<OutT>::PSCALE;   // half values: P leaves as 2^8 P, undone at the store
                 // pack P to bf16 B-fragments: k index (g, j) <-> slot ks*32 + (j>>2)*16 + g*4 + (j&3)
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) s[u][mt] *= inv;
 #pragma unroll
                 for (int ks = 0; ks < KST; ++ks)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[u][ks][j] = (bf16_t)s[u][2 * ks + (j >> 2)][j & 3];
+                    for (int j = 0; j < 8; ++j) pf[u][ks][j] = XnaVal<OutT>::p(s[u][2 * ks + (j >> 2)][j & 3]);
             }
 
             if constexpr ((ABL & 128) != 0) {
@@ -684,7 +694,7 @@ __global__ __launch_bounds__(NW * 64) void xna_mfma_kernel(const XnaMfmaParams p
                     a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
                     a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
 #pragma unroll
-                    for (int u = 0; u < TPW; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pf[u][ks], acc[u], 0, 0, 0);
+                    for (int u = 0; u < TPW; ++u) acc[u] = XnaVal<OutT>::mfma(a, pf[u][ks], acc[u]);
                 }
             };
             if constexpr (STG) {
@@ -758,15 +768,15 @@ __global__ __launch_bounds__(NW * 64) void xna_mfma_kernel(const XnaMfmaParams p
                         a[0] = bq[0] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
                         for (int ks = 0; ks < KST; ++ks) {
-                            a[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[cur][0][ks], pf[0][ks], a[0], 0, 0, 0);
-                            bq[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf[cur][1][ks], pf[0][ks], bq[0], 0, 0, 0);
+                            a[0] = XnaVal<OutT>::mfma(vf[cur][0][ks], pf[0][ks], a[0]);
+                            bq[0] = XnaVal<OutT>::mfma(vf[cur][1][ks], pf[0][ks], bq[0]);
                         }
                     }
                     bf16x4_t ab, bb;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        ab[i] = (bf16_t)a[0][i];
-                        bb[i] = (bf16_t)bq[0][i];
+                        ab[i] = XnaVal<OutT>::o(a[0][i]);
+                        bb[i] = XnaVal<OutT>::o(bq[0][i]);
                     }
                     const u32x2_t ua = __builtin_bit_cast(u32x2_t, ab), ub = __builtin_bit_cast(u32x2_t, bb);
                     const auto r0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -795,8 +805,8 @@ __global__ __launch_bounds__(NW * 64) void xna_mfma_kernel(const XnaMfmaParams p
                             bf16x4_t ab, bb;
 #pragma unroll
                             for (int i = 0; i < 4; ++i) {
-                                ab[i] = (bf16_t)a[u][i];
-                                bb[i] = (bf16_t)bq[u][i];
+                                ab[i] = XnaVal<OutT>::o(a[u][i]);
+                                bb[i] = XnaVal<OutT>::o(bq[u][i]);
                             }
                             const u32x2_t ua = __builtin_bit_cast(u32x2_t, ab), ub = __builtin_bit_cast(u32x2_t, bb);
                             const auto r0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -963,7 +973,7 @@ inline bool xna_mfma_plan(int ks, int Dv, int out_dtype, XnaMfmaPlan* pl) {
     for (int c : cand) {
         if (Dv % c || c > dvt_cap) continue;
         const int tpw = xna_mfma_tpw(ks);
-        const bool can_stage = (out_dtype == NAF_BF16) && (c % 32 == 0) && tpw == 1;
+        const bool can_stage = (out_dtype == NAF_BF16 || out_dtype == NAF_F16) && (c % 32 == 0) && tpw == 1;   // 16-bit output
         for (int cb = xna_mfma_cb(ks); cb >= 1; --cb) {
             for (int st = can_stage ? 1 : 0; st >= 0; --st) {
                 const size_t lds = xna_mfma_lds_for(ks, cb, c, st != 0);
@@ -987,7 +997,8 @@ inline bool xna_mfma_plan(int ks, int Dv, int out_dtype, XnaMfmaPlan* pl) {
     return false;
 }
 
-template <int KS>
+// HALF: the NAF_F16 instantiations (half values and output, XnaVal in naf_common.h) -- translation units of their own (xna_mfma_h_k*.hip)
+template <int KS, bool HALF = false>
 static int xna_mfma_launch_ks(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s) {
     constexpr int CBM = xna_mfma_cb(KS);
 #define NAF_TRY(D, ST, CBV, T)                                                              \
@@ -1000,7 +1011,14 @@ static int xna_mfma_launch_ks(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int
             return xna_mfma_launch_one<KS, D, T, ST, CBV, xna_mfma_tpw(KS), xna_mfma_nw(KS, CBV, D, ST)>(p, s); \
         }
 #define NAF_CASE(D)                                   \
-    if (out_dtype == NAF_BF16) {                      \
+    if constexpr (HALF) {                             \
+        NAF_TRY(D, true, CBM, f16_t)                  \
+        NAF_TRY(D, false, CBM, f16_t)                 \
+        if constexpr (CBM == 2) {                     \
+            NAF_TRY(D, true, 1, f16_t)                \
+            NAF_TRY(D, false, 1, f16_t)               \
+        }                                             \
+    } else if (out_dtype == NAF_BF16) {               \
         NAF_TRY(D, true, CBM, bf16_t)                 \
         NAF_TRY(D, false, CBM, bf16_t)                \
         if constexpr (CBM == 2) {                     \

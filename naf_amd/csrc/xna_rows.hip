@@ -130,7 +130,9 @@ __global__ __launch_bounds__(256) void xna_rows_kernel(const XnaRowsParams p) {
                 for (int i = 0; i < 4; ++i) {
                     const float e = wgt[hh][i] * __builtin_amdgcn_exp2f(fmaf(s[hh][i], p.scale_log2e, -mc));
                     psum += e;
-                    pa[hh * 4 + i] = (bf16_t)e;
+                    // half values (XnaVal, naf_common.h): 2^8 e <= k*k * 2^8 is rounded to half, 2^-8 rides on the normaliser below
+                    if constexpr (XnaVal<OutT>::F16) pa[hh * 4 + i] = XnaVal<OutT>::p(e * XnaVal<OutT>::PSCALE);
+                    else pa[hh * 4 + i] = (bf16_t)e;
                 }
             l = fmaf(l, alpha, psum);
             // ---- O[q][c] = alpha * O + P . V : result lane = (channel col, queries grp*4 + i) ----
@@ -149,13 +151,14 @@ __global__ __launch_bounds__(256) void xna_rows_kernel(const XnaRowsParams p) {
                 f32x4_t o = acc[ct];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] *= aq[i];
-                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vf, o, 0, 0, 0);
+                acc[ct] = XnaVal<OutT>::mfma(pa, vf, o);
             }
         }
         // ---- normalise and store ----
         l += __shfl_xor(l, 16);
         l += __shfl_xor(l, 32);
-        const float inv = __builtin_amdgcn_rcpf(l);
+        float inv = __builtin_amdgcn_rcpf(l);
+        if constexpr (XnaVal<OutT>::F16) inv *= XnaVal<OutT>::UNSCALE;
         OutT* ob = reinterpret_cast<OutT*>(p.out) + b * p.os[0] + head * p.os[1] + (int64_t)y * p.os[2];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -205,7 +208,8 @@ int naf_tile_span(int L_out, int L_in, int k) {
 namespace {
 template <int NDQ>
 int launch_ndq(const XnaRowsParams& p, int out_dtype, int grid, hipStream_t s) {
-    if (out_dtype == NAF_BF16) hipLaunchKernelGGL((xna_rows_kernel<NDQ, bf16_t>), dim3(grid), dim3(256), 0, s, p);
+    if (out_dtype == NAF_F16) hipLaunchKernelGGL((xna_rows_kernel<NDQ, f16_t>), dim3(grid), dim3(256), 0, s, p);   // half values and output
+    else if (out_dtype == NAF_BF16) hipLaunchKernelGGL((xna_rows_kernel<NDQ, bf16_t>), dim3(grid), dim3(256), 0, s, p);
     else hipLaunchKernelGGL((xna_rows_kernel<NDQ, float>), dim3(grid), dim3(256), 0, s, p);
     return naf_check_launch("xna_rows_kernel");
 }

@@ -336,13 +336,14 @@ __global__ __launch_bounds__(NW * 64) void xna_slide_kernel(const XnaSlideParams
                         sum2 += e;
                     }
                 float sum = naf_rows_sum(sum2[0] + sum2[1]);
-                const float inv = __builtin_amdgcn_rcpf(sum);
+                float inv = __builtin_amdgcn_rcpf(sum);
+                if constexpr (XnaVal<OutT>::F16) inv *= XnaVal<OutT>::PSCALE;   // half values: P leaves as 2^8 P, undone at the store
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt) s[mt] *= inv;
 #pragma unroll
                 for (int ks = 0; ks < KST; ++ks)
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) pf[u][ks][j] = (bf16_t)s[2 * ks + (j >> 2)][j & 3];
+                    for (int j = 0; j < 8; ++j) pf[u][ks][j] = XnaVal<OutT>::p(s[2 * ks + (j >> 2)][j & 3]);
                 __builtin_amdgcn_sched_barrier(0);   // keep the two tiles' score registers from overlapping
             }
 
@@ -381,7 +382,7 @@ __global__ __launch_bounds__(NW * 64) void xna_slide_kernel(const XnaSlideParams
                     a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
                     a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
 #pragma unroll
-                    for (int u = 0; u < TPW; ++u) acc[u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, pf[u][ks], acc[u], 0, 0, 0);
+                    for (int u = 0; u < TPW; ++u) acc[u] = XnaVal<OutT>::mfma(a, pf[u][ks], acc[u]);
                 }
             };
             constexpr bool kWide = sizeof(OutT) == 2;
@@ -397,8 +398,8 @@ __global__ __launch_bounds__(NW * 64) void xna_slide_kernel(const XnaSlideParams
                     bf16x4_t ab, bb;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        ab[i] = (bf16_t)a[0][i];
-                        bb[i] = (bf16_t)bq[0][i];
+                        ab[i] = XnaVal<OutT>::o(a[0][i]);
+                        bb[i] = XnaVal<OutT>::o(bq[0][i]);
                     }
                     const u32x2_t ua = __builtin_bit_cast(u32x2_t, ab), ub = __builtin_bit_cast(u32x2_t, bb);
                     const auto r0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -433,8 +434,8 @@ __global__ __launch_bounds__(NW * 64) void xna_slide_kernel(const XnaSlideParams
                         bf16x4_t ab, bb;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            ab[i] = (bf16_t)a[u][i];
-                            bb[i] = (bf16_t)bq[u][i];
+                            ab[i] = XnaVal<OutT>::o(a[u][i]);
+                            bb[i] = XnaVal<OutT>::o(bq[u][i]);
                         }
                         const u32x2_t ua = __builtin_bit_cast(u32x2_t, ab), ub = __builtin_bit_cast(u32x2_t, bb);
                         const auto r0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -470,8 +471,8 @@ __global__ __launch_bounds__(NW * 64) void xna_slide_kernel(const XnaSlideParams
                         bf16x4_t ab, bb;
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            ab[i] = (bf16_t)a[u][i];
-                            bb[i] = (bf16_t)bq[u][i];
+                            ab[i] = XnaVal<OutT>::o(a[u][i]);
+                            bb[i] = XnaVal<OutT>::o(bq[u][i]);
                         }
                         const u32x2_t ua = __builtin_bit_cast(u32x2_t, ab), ub = __builtin_bit_cast(u32x2_t, bb);
                         const auto r0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -572,18 +573,24 @@ static int xna_slide_launch_one(const XnaSlideParams& sp, hipStream_t s) {
 }
 
 // Dv tiles as the cell kernel plans them for unstaged stores (largest divisor of Dv that fits the LDS)
-template <int KS>
+// HALF: the NAF_F16 instantiations (xna_slide_h_k*.hip)
+template <int KS, bool HALF = false>
 static int xna_slide_launch_ks(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s) {
 #define NAF_SLIDE_CASE(D)                                                                              \
     if constexpr (xna_mfma_lds_for(KS, 1, D, false) <= 160 * 1024) {                                   \
         if (dvt == D) {                                                                                \
             constexpr int NWV = xna_mfma_lds_for(KS, 1, D, false) > 80 * 1024 ? 8 : 4;                 \
-            if (sp.m.tab_y != nullptr) {                                                               \
-                if (out_dtype == NAF_BF16) return xna_slide_launch_one<KS, D, bf16_t, NWV, true>(sp, s); \
-                return xna_slide_launch_one<KS, D, float, NWV, true>(sp, s);                           \
+            if constexpr (HALF) {                                                                      \
+                if (sp.m.tab_y != nullptr) return xna_slide_launch_one<KS, D, f16_t, NWV, true>(sp, s); \
+                return xna_slide_launch_one<KS, D, f16_t, NWV, false>(sp, s);                          \
+            } else {                                                                                   \
+                if (sp.m.tab_y != nullptr) {                                                           \
+                    if (out_dtype == NAF_BF16) return xna_slide_launch_one<KS, D, bf16_t, NWV, true>(sp, s); \
+                    return xna_slide_launch_one<KS, D, float, NWV, true>(sp, s);                       \
+                }                                                                                      \
+                if (out_dtype == NAF_BF16) return xna_slide_launch_one<KS, D, bf16_t, NWV, false>(sp, s); \
+                return xna_slide_launch_one<KS, D, float, NWV, false>(sp, s);                          \
             }                                                                                          \
-            if (out_dtype == NAF_BF16) return xna_slide_launch_one<KS, D, bf16_t, NWV, false>(sp, s);  \
-            return xna_slide_launch_one<KS, D, float, NWV, false>(sp, s);                              \
         }                                                                                              \
     }
     NAF_SLIDE_CASE(16)

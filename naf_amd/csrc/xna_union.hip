@@ -20,6 +20,10 @@
 #define NAF_DECL(K) int naf_xna_union_launch_k##K(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s);
 NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
 #undef NAF_DECL
+// half values and output (NAF_F16): xna_union_h_k*.hip
+#define NAF_DECL(K) int naf_xna_union_launch_h_k##K(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s);
+NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
+#undef NAF_DECL
 
 namespace {
 struct UnionPlan {
@@ -169,6 +173,17 @@ int naf_launch_xna_union(const naf_xna_args* a, float scale, hipStream_t s) {
     p.scale_log2e = scale * 1.4426950408889634f;
     for (int i = 0; i < 4; ++i) {
         p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i]; p.os[i] = a->o_stride[i];
+    }
+    if (a->out_dtype == NAF_F16) {
+        switch (a->ky) {
+            case 3: return naf_xna_union_launch_h_k3(p, pl.wt, a->out_dtype, pl.lds, s);
+            case 5: return naf_xna_union_launch_h_k5(p, pl.wt, a->out_dtype, pl.lds, s);
+            case 7: return naf_xna_union_launch_h_k7(p, pl.wt, a->out_dtype, pl.lds, s);
+            case 9: return naf_xna_union_launch_h_k9(p, pl.wt, a->out_dtype, pl.lds, s);
+            case 11: return naf_xna_union_launch_h_k11(p, pl.wt, a->out_dtype, pl.lds, s);
+            case 13: return naf_xna_union_launch_h_k13(p, pl.wt, a->out_dtype, pl.lds, s);
+            case 15: return naf_xna_union_launch_h_k15(p, pl.wt, a->out_dtype, pl.lds, s);
+        }
     }
     switch (a->ky) {
         case 3: return naf_xna_union_launch_k3(p, pl.wt, a->out_dtype, pl.lds, s);

@@ -292,14 +292,15 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const P p) {
             }
         sum += __shfl_xor(sum, 16);
         sum += __shfl_xor(sum, 32);
-        const float inv = __builtin_amdgcn_rcpf(sum);
+        float inv = __builtin_amdgcn_rcpf(sum);
+        if constexpr (XnaVal<OutT>::F16) inv *= XnaVal<OutT>::PSCALE;   // half values: P leaves as 2^8 P, undone at the store
         bf16x8_t pf[KST];
 #pragma unroll
         for (int ks = 0; ks < KST; ++ks)
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int mt = 2 * ks + (j >> 2);
-                pf[ks][j] = (mt < MT) ? (bf16_t)(s[mt < MT ? mt : 0][j & 3] * inv) : (bf16_t)0.f;
+                pf[ks][j] = (mt < MT) ? XnaVal<OutT>::p(s[mt < MT ? mt : 0][j & 3] * inv) : (bf16_t)0.f;
             }
 
         // ---- O^T = V^T . P^T and the stores ----
@@ -317,7 +318,7 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const P p) {
                 bf16x8_t av;
                 av[0] = lo[0]; av[1] = lo[1]; av[2] = lo[2]; av[3] = lo[3];
                 av[4] = hi[0]; av[5] = hi[1]; av[6] = hi[2]; av[7] = hi[3];
-                acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(av, pf[ks], acc, 0, 0, 0);
+                acc = XnaVal<OutT>::mfma(av, pf[ks], acc);
             }
             return acc;
         };
@@ -365,8 +366,8 @@ __global__ __launch_bounds__(NW * 64) void xna_union_kernel(const P p) {
                 bf16x4_t ab, bb;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    ab[i] = (bf16_t)a0[i];
-                    bb[i] = (bf16_t)a1[i];
+                    ab[i] = XnaVal<OutT>::o(a0[i]);
+                    bb[i] = XnaVal<OutT>::o(a1[i]);
                 }
                 const u32x2_t ua = __builtin_bit_cast(u32x2_t, ab), ub = __builtin_bit_cast(u32x2_t, bb);
                 const auto r0 = __builtin_amdgcn_permlane16_swap(ua[0], ub[0], false, false);
@@ -418,12 +419,18 @@ static int xna_union_launch_one(const XnaUnionParams& p, size_t lds, hipStream_t
     return naf_check_launch("xna_union_kernel");
 }
 
-template <int KS>
+// HALF: the NAF_F16 instantiations (xna_union_h_k*.hip)
+template <int KS, bool HALF = false>
 static int xna_union_launch_ks(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s) {
-    if (wt == 16) {
-        if (out_dtype == NAF_BF16) return xna_union_launch_one<KS, bf16_t, 16>(p, lds, s);
-        return xna_union_launch_one<KS, float, 16>(p, lds, s);
+    if constexpr (HALF) {
+        if (wt == 16) return xna_union_launch_one<KS, f16_t, 16>(p, lds, s);
+        return xna_union_launch_one<KS, f16_t, 32>(p, lds, s);
+    } else {
+        if (wt == 16) {
+            if (out_dtype == NAF_BF16) return xna_union_launch_one<KS, bf16_t, 16>(p, lds, s);
+            return xna_union_launch_one<KS, float, 16>(p, lds, s);
+        }
+        if (out_dtype == NAF_BF16) return xna_union_launch_one<KS, bf16_t, 32>(p, lds, s);
+        return xna_union_launch_one<KS, float, 32>(p, lds, s);
     }
-    if (out_dtype == NAF_BF16) return xna_union_launch_one<KS, bf16_t, 32>(p, lds, s);
-    return xna_union_launch_one<KS, float, 32>(p, lds, s);
 }

@@ -522,14 +522,16 @@ class CrossAttention(nn.Module):
         self.dilation = (Ho // h, Wo // w)                                     # attentions.py:56-57
         vp = ops.pack_values(values)
         v5 = vp.view(B, h, w, self.num_heads, C // self.num_heads).permute(0, 3, 1, 2, 4)
-        out_dtype = torch.bfloat16 if values.dtype == torch.bfloat16 else torch.float32
+        # bf16 / float16 features leave in their own dtype (float16: half values on the f16 matrix instruction, nothing is rounded
+        # to bf16 and no fp32 map exists); everything else is computed from bf16 values into fp32
+        out_dtype = values.dtype if values.dtype in (torch.bfloat16, torch.float16) else torch.float32
         res = ops.xna_forward(q5, k5, v5, self.kernel_size, out_dtype=out_dtype, return_logits=return_weights,
                               path=path, scale=self.scale, rope_tables=rope_tables)
         out5, logits = res if return_weights else (res, None)
         # [B, heads, Ho, Wo, Dv] view of a channels-last buffer -> logical [B, C, Ho, Wo]
         out = out5.permute(0, 2, 3, 1, 4).reshape(B, Ho, Wo, C).permute(0, 3, 1, 2)
-        if values.dtype not in (torch.bfloat16, torch.float32):
-            out = out.to(values.dtype)
+        if values.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            out = out.to(values.dtype)      # float64
         return (out, logits) if return_weights else out
 
 
@@ -716,7 +718,7 @@ class NAF(nn.Module):
             return None
         if image.shape[1] != 3 or self.xna_path != "auto":
             return None
-        if features.dtype not in (torch.bfloat16, torch.float32):
+        if features.dtype not in (torch.bfloat16, torch.float16, torch.float32):
             return None
         if image.dtype not in (torch.bfloat16, torch.float32) or features.shape[1] % self.upsampler.num_heads:
             return None
@@ -743,7 +745,7 @@ class NAF(nn.Module):
         eps = enc.encoder[1].norm1.eps
         plan = ops.ForwardPlan(branches, len(branches[0][4]), eps, enc.rope.tables(ho, wo), image, features,
                                self.upsampler.num_heads, self.upsampler.kernel_size[0],
-                               torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32, self.upsampler.scale,
+                               features.dtype if features.dtype in (torch.bfloat16, torch.float16) else torch.float32, self.upsampler.scale,
                                output_size=(ho, wo), heads_rope=enc.rope.num_heads)
         plan = plan if plan.supported else None
         self.__dict__["_plan_cache"] = (key, plan)
@@ -1021,7 +1023,8 @@ class NAF(nn.Module):
         with torch.no_grad():
             q5, k5, _ = self.guidance_qk(image, features.shape[-2:], (ho, wo))       # materialised queries: the union kernel takes no rotate-on-load
             h, w = features.shape[-2:]
-            v5 = ops.pack_values(features).view(B, h, w, heads, C // heads).permute(0, 3, 1, 2, 4)
+            # (the objective's kernel takes bf16 values: float16 features are packed to bf16 through fp32, as they always were)
+            v5 = ops.pack_values(features.float() if features.dtype == torch.float16 else features).view(B, h, w, heads, C // heads).permute(0, 3, 1, 2, 4)
             with ops._Timed("attention"):
                 loss, _ = ops.xna_mse_forward(q5, k5, v5, regress, ksz, scale=self.upsampler.scale, grad=False)
         return loss
@@ -1135,7 +1138,7 @@ class NAF(nn.Module):
         if image.shape[0] == 0:
             # an empty batch flows through the reference's torch ops as empty tensors; there is nothing to launch here
             ho, wo = int(output_size[0]), int(output_size[1])
-            odt = features.dtype if features.dtype in (torch.bfloat16, torch.float32) else torch.float32
+            odt = features.dtype if features.dtype in (torch.bfloat16, torch.float16, torch.float32) else torch.float32
             out = torch.empty((0, ho, wo, features.shape[1]), dtype=odt, device=features.device).permute(0, 3, 1, 2)
             if out.dtype != features.dtype:
                 out = out.to(features.dtype)
@@ -1180,7 +1183,7 @@ class NAF(nn.Module):
         fuse_for = None
         if features.shape[1] % self.upsampler.num_heads == 0:
             fuse_for = (features.shape[1] // self.upsampler.num_heads,
-                        torch.bfloat16 if features.dtype == torch.bfloat16 else torch.float32)
+                        features.dtype if features.dtype in (torch.bfloat16, torch.float16) else torch.float32)
         q5, k5, tabs = self.guidance_qk(image, features.shape[-2:], output_size, fuse_for=fuse_for)
         with ops._Timed("attention"):
             return self.upsampler(q5, k5, features, return_weights=return_weights, path=self.xna_path, rope_tables=tabs)

@@ -29,6 +29,9 @@ from . import _lib
 from ._lib import XnaArgs, XnaHeadArgs, XnaBwdArgs, XnaBwdScoresArgs, RopePoolArgs, StemConv0Args, StemConvArgs, KeyPoolArgs, ForwardArgs, I64x3, I64x4
 
 _DT = {torch.bfloat16: _lib.NAF_BF16, torch.float32: _lib.NAF_F32}
+# The VALUES and the output of the attention forward also come as float16 (naf_dtype_supported): a map of its own, because _DT
+# gates image dtypes, targets and every other entry, none of which takes half.
+_DT_VALUES = {**_DT, torch.float16: _lib.NAF_F16}
 
 # Optional kernel timer (bench.py): an object with start(name) / stop(name) that records HIP events on
 # the CURRENT stream tightly around one C-ABI launch.  None in normal operation.
@@ -590,16 +593,16 @@ def pool_guidance(x: torch.Tensor, output_size) -> torch.Tensor:
 
 
 def pack_values(v: torch.Tensor) -> torch.Tensor:
-    """[B, C, h, w] (bf16/fp32, any strides) -> dense channels-last bf16 [B, h, w, C]."""
+    """[B, C, h, w] (bf16/fp32, any strides) -> dense channels-last bf16 [B, h, w, C]; float16 -> float16, an exact copy."""
     _gpu(v, "lr_features")
     lib = _lib.load()
-    if v.dtype not in _DT:
+    if v.dtype not in _DT_VALUES:
         v = v.float()
     B, Cc, h, w = v.shape
-    vp = torch.empty((B, h, w, Cc), dtype=torch.bfloat16, device=v.device)
+    vp = torch.empty((B, h, w, Cc), dtype=torch.float16 if v.dtype == torch.float16 else torch.bfloat16, device=v.device)
     st = _strides4(v, (0, 1, 2, 3))
     with torch.cuda.device(v.device):
-        rc = lib.naf_pack_values(vp.data_ptr(), v.data_ptr(), _DT[v.dtype], B, Cc, h, w, st, _stream(v))
+        rc = lib.naf_pack_values(vp.data_ptr(), v.data_ptr(), _DT_VALUES[v.dtype], B, Cc, h, w, st, _stream(v))
     _lib.check(rc, "naf_pack_values")
     return vp
 
@@ -619,7 +622,7 @@ def _fill_xna(q, k, v, out, logits, idx_y, idx_x, ky, kx, path, scale, rope_tabl
             raise ValueError("xna: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
         a.rope_tab_y, a.rope_tab_x = ty.data_ptr(), tx.data_ptr()
     a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
-    a.out_dtype = _DT[out.dtype]
+    a.out_dtype = _DT_VALUES[out.dtype]
     a.path = _PATH[path]
     a.scale = float(scale) if scale else 0.0
     a.q_stride = _strides4(q, (0, 1, 2, 3))
@@ -638,24 +641,30 @@ def xna_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_
     it (see ``xna_rope_fusable``; raises NafHipError when the shapes do not allow it).
 
     q [B, heads, Ho, Wo, Dq] bf16, k_lr [B, heads, h, w, Dq] bf16, v_lr [B, heads, h, w, Dv] bf16 --
-    5-D strided views with the last dim contiguous.  Returns ``out`` as a [B, heads, Ho, Wo, Dv] view
+    5-D strided views with the last dim contiguous.  ``v_lr`` may be float16 together with ``out_dtype=torch.float16``, and only
+    together: the values are then read as half, multiplied on the f16 matrix instruction and the output is half (include/naf_hip.h,
+    naf_dtype_supported); q, k_lr and the scores stay bf16 / fp32.  Returns ``out`` as a [B, heads, Ho, Wo, Dv] view
     of a dense channels-last [B, Ho, Wo, heads*Dv] buffer (and, with ``return_logits``, the scaled
     pre-softmax scores [B, heads, Ho, Wo, ky*kx] fp32 -- what the reference's return_weights gives).
     """
+    half = v_lr.dtype == torch.float16 or out_dtype == torch.float16 or (out is not None and out.dtype == torch.float16)
     for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
         _gpu(t, n)
-        if t.dtype != torch.bfloat16:
+        if t.dtype != torch.bfloat16 and not (half and t is v_lr):
             raise TypeError(f"xna_forward: {n} must be bfloat16, got {t.dtype}")
         if t.dim() != 5 or t.stride(4) != 1:
             raise ValueError(f"xna_forward: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    if half and not (v_lr.dtype == torch.float16 and out_dtype == torch.float16 and (out is None or out.dtype == torch.float16)):
+        raise TypeError(f"xna_forward: float16 values go with out_dtype=torch.float16 and only with it "
+                        f"(v_lr {v_lr.dtype}, out_dtype {out_dtype}{'' if out is None else f', out {out.dtype}'})")
     lib = _lib.load()
     ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     _, _, h, w, Dv = v_lr.shape
     if k_lr.shape != (B, heads, h, w, Dq):
         raise ValueError(f"xna_forward: k_lr shape {tuple(k_lr.shape)} does not match q/v")
-    if out_dtype not in _DT:
-        raise TypeError(f"xna_forward: out_dtype {out_dtype} not supported (bfloat16 / float32)")
+    if out_dtype not in _DT_VALUES:
+        raise TypeError(f"xna_forward: out_dtype {out_dtype} not supported (bfloat16 / float32, float16 with float16 values)")
     dev = q.device
     if out is None:
         out = torch.empty((B, Ho, Wo, heads, Dv), dtype=out_dtype, device=dev).permute(0, 3, 1, 2, 4)
@@ -1493,7 +1502,7 @@ def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables
                      path: str = "auto") -> bool:
     """True when ``xna_forward(q, ..., rope_tables=...)`` can rotate the queries on load for these shapes (MFMA path,
     Wo/w a multiple of 16).  ``q``: the un-rotated guidance as a 5-D [B, heads, Ho, Wo, Dq] bf16 view."""
-    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or out_dtype not in _DT:
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or out_dtype not in _DT_VALUES:
         return False
     lib = _lib.load()
     ky, kx = _ksize(kernel_size)
@@ -1503,7 +1512,7 @@ def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables
     a.q = a.k_lr = a.v_lr = a.out = q.data_ptr()      # shape / alignment query only: nothing is dereferenced
     a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
     a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, int(Dv), ky, kx
-    a.out_dtype, a.path, a.scale = _DT[out_dtype], _PATH[path], 0.0
+    a.out_dtype, a.path, a.scale = _DT_VALUES[out_dtype], _PATH[path], 0.0
     a.q_stride = _strides4(q, (0, 1, 2, 3))
     a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
     a.v_stride = I64x4(h * w * heads * Dv, Dv, w * heads * Dv, heads * Dv)
@@ -1620,7 +1629,7 @@ class ForwardPlan:
         a = ForwardArgs()
         a.tab_y, a.tab_x = tabs[0].data_ptr(), tabs[1].data_ptr()
         a.nlayer = nlayer
-        a.image_dtype, a.feat_dtype, a.out_dtype = _DT[image.dtype], _DT[features.dtype], _DT[out_dtype]
+        a.image_dtype, a.feat_dtype, a.out_dtype = _DT[image.dtype], _DT_VALUES[features.dtype], _DT_VALUES[out_dtype]     # float16: both or neither
         a.B, a.H, a.W, a.h, a.w, a.C, a.heads, a.ksize = B, H, W, h, w, Cc, heads, ksize
         a.Ho, a.Wo = Ho, Wo
         a.heads_rope = int(heads_rope)
@@ -1683,7 +1692,8 @@ class ForwardPlan:
         _lib.check(self.lib.naf_forward_workspace_view(C.byref(a), code, C.byref(off), C.byref(nbytes)), "naf_forward_workspace_view")
         B, Ho, Wo, _ = self.shape_out
         shape = {"guidance": (B, Ho, Wo, 256), "keys": (B, a.h, a.w, 256), "values": (B, a.h, a.w, a.C)}[which]
-        return ws[off.value: off.value + nbytes.value].view(torch.bfloat16).view(shape)
+        dt = torch.float16 if (which == "values" and a.feat_dtype == _lib.NAF_F16) else torch.bfloat16     # half features are packed as half
+        return ws[off.value: off.value + nbytes.value].view(dt).view(shape)
 
     def release_stream(self, device_index: int, stream_handle: int) -> None:
         """Drop the scratch buffer of ONE (device, raw stream handle) -- a throw-away stream's -- once its work has been synchronised with."""
