@@ -1,7 +1,11 @@
 """Build libnaf_hip.so (gfx950) in-tree with hipcc.  ``python -m naf_amd.build [--force]``.
 
 hipcc cross-compiles for gfx950 without a GPU.  One object per translation unit, compiled in
-parallel, then one ``hipcc -shared`` link.  The library keeps a plain DT_NEEDED on libamdhip64.so.7
+parallel, then one ``hipcc -shared`` link.  The windowed attention kernels are the exception: each
+family has ONE instance source (``xna_*_inst.hip``, explicit template instantiations only) that is
+compiled once per entry of ``INSTANCES`` with ``-DNAF_KS=<window>`` (and ``-DNAF_HALF=0|1``), one
+object per instance (``xna_mfma_inst_k9_h.o``).  The link refuses undefined symbols, so an instance
+a dispatcher declares but the table lacks fails the build.  The library keeps a plain DT_NEEDED on libamdhip64.so.7
 and NO rpath: when loaded after ``import torch`` the loader reuses the HIP runtime torch already
 mapped (same SONAME), so stream handles and device pointers are shared with torch.
 """
@@ -28,6 +32,17 @@ NO_VGPR_FORM = {"stem_conv.hip"}
 # vectoriser would pack adjacent ones again.  denoise.hip: its fused multiply-adds are written out; with the compiler's own contraction
 # off, expressions that are symmetric in pred and target round symmetrically (the SSIM gradient of identical windows is exactly zero).
 EXTRA_FLAGS = {"stem_conv.hip": ["-fno-slp-vectorize"], "denoise.hip": ["-ffp-contract=off"]}
+# Instance sources -> the (window, half) instances they are compiled for (half None: the family has one value type).  The lists are
+# NAF_FOR_WINDOWS / NAF_FOR_SLIDE_WINDOWS of naf_common.h.
+_WINDOWS, _SLIDE_WINDOWS = (3, 5, 7, 9, 11, 13, 15), (7, 9, 11, 13, 15)
+INSTANCES = {
+    "xna_mfma_inst.hip": [(k, h) for h in (0, 1) for k in _WINDOWS],
+    "xna_slide_inst.hip": [(k, h) for h in (0, 1) for k in _SLIDE_WINDOWS],
+    "xna_union_inst.hip": [(k, h) for h in (0, 1) for k in _WINDOWS],
+    "xna_union_mse_inst.hip": [(k, None) for k in _WINDOWS],
+    "xna_head_inst.hip": [(k, None) for k in _WINDOWS],
+    "xna_bwd_inst.hip": [(k, None) for k in _WINDOWS],
+}
 
 
 def _hipcc() -> str:
@@ -37,8 +52,14 @@ def _hipcc() -> str:
     raise RuntimeError("hipcc not found (set HIPCC or install ROCm under /opt/rocm)")
 
 
-def _sources():
-    return sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+def _units():
+    """(source, object stem, defines) of every object: plain sources once, instance sources once per INSTANCES entry."""
+    units = [(f, os.path.splitext(f)[0], []) for f in os.listdir(CSRC) if f.endswith(".hip") and f not in INSTANCES]
+    for src, insts in INSTANCES.items():
+        for k, half in insts:
+            stem = f"{os.path.splitext(src)[0]}_k{k}" + ("_h" if half else "")
+            units.append((src, stem, [f"-DNAF_KS={k}"] + ([] if half is None else [f"-DNAF_HALF={half}"])))
+    return sorted(units, key=lambda u: u[1])
 
 
 def _deps_mtime() -> float:
@@ -48,27 +69,28 @@ def _deps_mtime() -> float:
     return max(os.path.getmtime(h) for h in hdrs)
 
 
-def _compile(src: str, force: bool, hdr_mtime: float, extra) -> str:
-    obj = os.path.join(OBJDIR, os.path.splitext(src)[0] + ".o")
+def _compile(unit, force: bool, hdr_mtime: float, extra) -> str:
+    src, stem, defines = unit
+    obj = os.path.join(OBJDIR, stem + ".o")
     spath = os.path.join(CSRC, src)
     if not force and os.path.exists(obj) and os.path.getmtime(obj) >= max(os.path.getmtime(spath), hdr_mtime):
         return obj
     cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall",
-           "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}", *([] if src in NO_VGPR_FORM else VGPR_FORM), *EXTRA_FLAGS.get(src, []), *extra, "-c", spath, "-o", obj]
+           "-Wno-unused-function", f"-I{INCLUDE}", f"-I{CSRC}", *([] if src in NO_VGPR_FORM else VGPR_FORM), *EXTRA_FLAGS.get(src, []), *defines, *extra, "-c", spath, "-o", obj]
     r = subprocess.run(cmd, capture_output=True, text=True)
     if r.returncode != 0:
-        raise RuntimeError(f"hipcc failed on {src}:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
+        raise RuntimeError(f"hipcc failed on {stem}:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")
     return obj
 
 
 def build_library(force: bool = False, verbose: bool = False, extra_flags=()) -> str:
     os.makedirs(OBJDIR, exist_ok=True)
-    srcs = _sources()
+    units = _units()
     hdr_mtime = _deps_mtime()
     with cf.ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 2)) as ex:
-        objs = list(ex.map(lambda s: _compile(s, force, hdr_mtime, list(extra_flags)), srcs))
+        objs = list(ex.map(lambda s: _compile(s, force, hdr_mtime, list(extra_flags)), units))
     if force or not os.path.exists(LIB) or os.path.getmtime(LIB) < max(os.path.getmtime(o) for o in objs):
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-fno-gpu-rdc", "-o", LIB, *objs]
+        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-shared", "-fPIC", "-fno-gpu-rdc", "-Wl,--no-undefined", "-o", LIB, *objs]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{' '.join(cmd)}\n{r.stdout}\n{r.stderr}")

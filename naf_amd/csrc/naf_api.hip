@@ -37,9 +37,6 @@ int naf_cu_count() {
     return cached[dev];
 }
 
-// The softmax scale of a call: the caller's, or 1 / sqrt(Dq) when it leaves the field at 0.
-static float xna_scale(float scale, int Dq) { return scale > 0.f ? scale : 1.0f / sqrtf((float)Dq); }
-
 // The geometry every attention entry asks for (A: naf_xna_args, naf_xna_head_args or naf_xna_bwd_args; `who` is the entry's name in the
 // messages; Dv is a parameter because the head's arguments have none).
 template <typename A>
@@ -146,8 +143,6 @@ int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t
     return naf_launch_pack_values(vp, v, v_dtype, B, C, h, w, v_stride, static_cast<hipStream_t>(stream));
 }
 
-static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 int naf_preshrink_image(float* out, const void* image, int32_t image_dtype, int32_t B, int32_t H, int32_t W, int32_t Hs, int32_t Ws,
                         const int64_t image_stride[4], naf_stream_t stream) {
     NAF_REQUIRE(out && image && image_stride, "naf_preshrink_image: NULL pointer");
@@ -159,14 +154,14 @@ int naf_preshrink_image(float* out, const void* image, int32_t image_dtype, int3
 int naf_pool_guidance(void* y, const void* x, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t C, naf_stream_t stream) {
     NAF_REQUIRE(x && y, "naf_pool_guidance: NULL pointer");
     NAF_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0, "naf_pool_guidance: non-positive size");
-    NAF_REQUIRE(C % 8 == 0 && al16(x) && al16(y), "naf_pool_guidance: needs C %% 8 == 0 and 16-byte aligned buffers (C=%d)", C);
+    NAF_REQUIRE(C % 8 == 0 && naf_aligned(x, 16) && naf_aligned(y, 16), "naf_pool_guidance: needs C %% 8 == 0 and 16-byte aligned buffers (C=%d)", C);
     return naf_launch_pool_guidance(y, x, B, H, W, Ho, Wo, C, static_cast<hipStream_t>(stream));
 }
 
 int naf_pool_guidance_bwd(void* dx, const void* dy, int32_t B, int32_t H, int32_t W, int32_t Ho, int32_t Wo, int32_t C, naf_stream_t stream) {
     NAF_REQUIRE(dx && dy, "naf_pool_guidance_bwd: NULL pointer");
     NAF_REQUIRE(B > 0 && H > 0 && W > 0 && Ho > 0 && Wo > 0 && C > 0, "naf_pool_guidance_bwd: non-positive size");
-    NAF_REQUIRE(C % 8 == 0 && al16(dx) && al16(dy), "naf_pool_guidance_bwd: needs C %% 8 == 0 and 16-byte aligned buffers (C=%d)", C);
+    NAF_REQUIRE(C % 8 == 0 && naf_aligned(dx, 16) && naf_aligned(dy, 16), "naf_pool_guidance_bwd: needs C %% 8 == 0 and 16-byte aligned buffers (C=%d)", C);
     return naf_launch_pool_guidance_bwd(dx, dy, B, H, W, Ho, Wo, C, static_cast<hipStream_t>(stream));
 }
 
@@ -190,7 +185,7 @@ int naf_stem_conv0_fwd(const naf_stem_conv0_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "naf_stem_conv0_fwd: non-positive size");
     // reflect padding needs pad < extent, like torch's ReflectionPad
     NAF_REQUIRE(a->ksize == 1 || (a->H >= 2 && a->W >= 2), "naf_stem_conv0_fwd: reflect padding needs H, W >= 2");
-    NAF_REQUIRE(a->y == nullptr || (al16(a->y) && a->y_stride[0] % 8 == 0 && a->y_stride[1] % 8 == 0 && a->y_stride[2] % 8 == 0),
+    NAF_REQUIRE(a->y == nullptr || (naf_aligned(a->y, 16) && a->y_stride[0] % 8 == 0 && a->y_stride[1] % 8 == 0 && a->y_stride[2] % 8 == 0),
                 "naf_stem_conv0_fwd: output must be 16-byte aligned with strides multiple of 8");
     if (a->channels != 0 && a->channels != 128) return naf_launch_stem_conv0_generic(a, static_cast<hipStream_t>(stream));
     return naf_launch_stem_conv0(a, static_cast<hipStream_t>(stream));
@@ -212,7 +207,7 @@ int naf_stem_conv_fwd(const naf_stem_conv_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->ksize == 1 || a->ksize == 3, "naf_stem_conv_fwd: kernel size %d (1 or 3)", a->ksize);
     NAF_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0, "naf_stem_conv_fwd: non-positive size");
     NAF_REQUIRE(a->ksize == 1 || (a->H >= 2 && a->W >= 2), "naf_stem_conv_fwd: reflect padding needs H, W >= 2");
-    NAF_REQUIRE((a->first || al16(a->x)) && al16(a->y) && al16(a->w_packed), "naf_stem_conv_fwd: tensors must be 16-byte aligned");
+    NAF_REQUIRE((a->first || naf_aligned(a->x, 16)) && naf_aligned(a->y, 16) && naf_aligned(a->w_packed, 16), "naf_stem_conv_fwd: tensors must be 16-byte aligned");
     for (int i = 0; i < 3; ++i)
         NAF_REQUIRE((a->first || a->x_stride[i] % 8 == 0) && a->y_stride[i] % 8 == 0, "naf_stem_conv_fwd: strides must be multiples of 8 elements");
     if (a->channels != 0 && a->channels != 128) return naf_launch_stem_conv_generic(a, static_cast<hipStream_t>(stream));
@@ -227,7 +222,7 @@ static int stem_conv_keys_validate(const naf_stem_conv_args* a, const naf_key_po
     NAF_REQUIRE(kp->k_lr && kp->tab_y && kp->tab_x, "naf_stem_conv_keys_fwd: NULL key / table pointer");
     NAF_REQUIRE(a->ksize == 1 || a->ksize == 3, "naf_stem_conv_keys_fwd: kernel size %d (1 or 3)", a->ksize);
     NAF_REQUIRE(a->B > 0 && a->H > 0 && a->W > 0 && kp->h > 0 && kp->w > 0, "naf_stem_conv_keys_fwd: non-positive size");
-    NAF_REQUIRE(al16(a->x) && al16(a->y) && al16(a->w_packed), "naf_stem_conv_keys_fwd: tensors must be 16-byte aligned");
+    NAF_REQUIRE(naf_aligned(a->x, 16) && naf_aligned(a->y, 16) && naf_aligned(a->w_packed, 16), "naf_stem_conv_keys_fwd: tensors must be 16-byte aligned");
     for (int i = 0; i < 3; ++i)
         NAF_REQUIRE(a->x_stride[i] % 8 == 0 && a->y_stride[i] % 8 == 0, "naf_stem_conv_keys_fwd: strides must be multiples of 8 elements");
     return NAF_OK;
@@ -257,7 +252,7 @@ int naf_rope_pool_bwd(const naf_rope_pool_bwd_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->dq && a->dk_lr && a->dx && a->tab_y && a->tab_x, "naf_rope_pool_bwd: NULL pointer");
     NAF_REQUIRE(a->B > 0 && a->heads > 0 && a->Cq > 0 && a->Cq % a->heads == 0 && a->Ho > 0 && a->Wo > 0 && a->h > 0 && a->w > 0 &&
                 a->Ho >= a->h && a->Wo >= a->w, "naf_rope_pool_bwd: sizes out of range");
-    NAF_REQUIRE(al16(a->dq) && al16(a->dk_lr) && al16(a->dx), "naf_rope_pool_bwd: tensors must be 16-byte aligned");
+    NAF_REQUIRE(naf_aligned(a->dq, 16) && naf_aligned(a->dk_lr, 16) && naf_aligned(a->dx, 16), "naf_rope_pool_bwd: tensors must be 16-byte aligned");
     for (int i = 0; i < 4; ++i)
         NAF_REQUIRE(a->dq_stride[i] % 8 == 0 && a->dk_stride[i] % 4 == 0 && (i == 1 || a->dx_stride[i] % 8 == 0), "naf_rope_pool_bwd: strides must keep 16-byte alignment");
     return naf_launch_rope_pool_bwd(a, static_cast<hipStream_t>(stream));
@@ -269,7 +264,7 @@ int naf_stem_wgrad(const naf_stem_wgrad_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->ksize == 1 || a->ksize == 3, "naf_stem_wgrad: kernel size %d (1 or 3)", a->ksize);
     NAF_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0, "naf_stem_wgrad: size out of range");
     NAF_REQUIRE(a->ksize == 1 || (a->H >= 2 && a->W >= 2), "naf_stem_wgrad: reflect padding needs H, W >= 2");
-    NAF_REQUIRE(al16(a->dy) && al16(a->x), "naf_stem_wgrad: tensors must be 16-byte aligned");
+    NAF_REQUIRE(naf_aligned(a->dy, 16) && naf_aligned(a->x, 16), "naf_stem_wgrad: tensors must be 16-byte aligned");
     for (int i = 0; i < 3; ++i) NAF_REQUIRE(a->dy_stride[i] % 8 == 0 && a->x_stride[i] % 8 == 0, "naf_stem_wgrad: strides must be multiples of 8 elements");
     if (a->channels != 0 && a->channels != 128) return naf_launch_stem_wgrad_generic(a, static_cast<hipStream_t>(stream));
     return naf_launch_stem_wgrad(a, static_cast<hipStream_t>(stream));
@@ -295,7 +290,7 @@ int naf_stem_conv0_dgrad(const naf_stem_conv0_dgrad_args* a, naf_stream_t stream
     NAF_REQUIRE(a->ksize == 1 || (a->H >= 2 && a->W >= 2), "naf_stem_conv0_dgrad: reflect padding needs H, W >= 2");
     NAF_REQUIRE(a->channels == 0 || (a->channels >= 16 && a->channels <= 256 && a->channels % 16 == 0),
                 "naf_stem_conv0_dgrad: %d channels (multiples of 16 up to 256)", a->channels);
-    NAF_REQUIRE(al16(a->dy), "naf_stem_conv0_dgrad: dy must be 16-byte aligned");
+    NAF_REQUIRE(naf_aligned(a->dy, 16), "naf_stem_conv0_dgrad: dy must be 16-byte aligned");
     for (int i = 0; i < 3; ++i) NAF_REQUIRE(a->dy_stride[i] % 8 == 0, "naf_stem_conv0_dgrad: dy strides must be multiples of 8 elements");
     return naf_launch_stem_conv0_dgrad(a, static_cast<hipStream_t>(stream));
 }
@@ -305,7 +300,7 @@ int naf_stem_act_fwd(const naf_stem_act_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->x && a->a && a->gn_weight && a->gn_bias && a->stats_in, "naf_stem_act_fwd: NULL pointer");
     NAF_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0, "naf_stem_act_fwd: size out of range");
     NAF_REQUIRE(a->pad == 0 || (a->pad == 1 && a->H >= 2 && a->W >= 2), "naf_stem_act_fwd: pad %d (0, or 1 with H, W >= 2)", a->pad);
-    NAF_REQUIRE(al16(a->x) && al16(a->a), "naf_stem_act_fwd: tensors must be 16-byte aligned");
+    NAF_REQUIRE(naf_aligned(a->x, 16) && naf_aligned(a->a, 16), "naf_stem_act_fwd: tensors must be 16-byte aligned");
     for (int i = 0; i < 3; ++i) NAF_REQUIRE(a->x_stride[i] % 8 == 0 && a->a_stride[i] % 8 == 0, "naf_stem_act_fwd: strides must be multiples of 8 elements");
     return naf_launch_stem_act_fwd(a, static_cast<hipStream_t>(stream));
 }
@@ -316,7 +311,7 @@ int naf_stem_act_bwd(const naf_stem_act_bwd_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->phase >= 0 && a->phase <= 2 && (a->phase == 1 || a->dx), "naf_stem_act_bwd: phase %d / dx", a->phase);
     NAF_REQUIRE(a->B > 0 && a->B <= 65535 && a->H > 0 && a->W > 0, "naf_stem_act_bwd: size out of range");
     NAF_REQUIRE(a->fold == 0 || (a->fold == 1 && a->H >= 2 && a->W >= 2), "naf_stem_act_bwd: fold %d (0, or 1 with H, W >= 2)", a->fold);
-    NAF_REQUIRE(al16(a->x) && al16(a->da) && (a->dx == nullptr || al16(a->dx)), "naf_stem_act_bwd: tensors must be 16-byte aligned");
+    NAF_REQUIRE(naf_aligned(a->x, 16) && naf_aligned(a->da, 16) && (a->dx == nullptr || naf_aligned(a->dx, 16)), "naf_stem_act_bwd: tensors must be 16-byte aligned");
     for (int i = 0; i < 3; ++i)
         NAF_REQUIRE(a->x_stride[i] % 8 == 0 && a->da_stride[i] % 8 == 0 && a->dx_stride[i] % 8 == 0, "naf_stem_act_bwd: strides must be multiples of 8 elements");
     return naf_launch_stem_act_bwd(a, static_cast<hipStream_t>(stream));
@@ -550,7 +545,7 @@ static int xna_bwd_dispatch(const char* who, const naf_xna_bwd_args* a, const na
     // the denoising call's shapes: matrix cores when the caller brought the tables and the statistics workspace
     // a workspace pointer that is not 16-byte aligned cannot be one this library asked for (a host built against a 0.1.0 header
     // leaves stack garbage in the field): refuse it instead of writing the per-query statistics through it
-    NAF_REQUIRE(a->workspace == nullptr || al16(a->workspace), "%s: workspace must be 16-byte aligned", who);
+    NAF_REQUIRE(a->workspace == nullptr || naf_aligned(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
     if (sel == NAF_XNA_ROWS) {
         if (a->idx_y && a->idx_x && a->workspace && (size_t)a->workspace_bytes >= naf_xna_rows_bwd_workspace(a))
             return naf_launch_xna_rows_bwd(a, scale, s, sg);

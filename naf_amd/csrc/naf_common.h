@@ -199,6 +199,58 @@ inline const char* naf_knob(const char* name) {
     return on ? getenv(name) : nullptr;
 }
 
+// ---- host helpers shared by the attention dispatchers ----
+// The windows the cell, table-driven, head and backward kernels are instantiated for (one object per window: build.py INSTANCES),
+// and the sliding kernel's.  A dispatcher declares its instances `extern template` and builds its switch from the same list.
+#define NAF_FOR_WINDOWS(X) X(3) X(5) X(7) X(9) X(11) X(13) X(15)
+#define NAF_FOR_SLIDE_WINDOWS(X) X(7) X(9) X(11) X(13) X(15)
+
+inline bool naf_aligned(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; }
+
+// The softmax scale of a call: the caller's, or 1 / sqrt(Dq) when it leaves the field at 0.  The kernels take it times log2(e) (exp2).
+inline float xna_scale(float scale, int Dq) { return scale > 0.f ? scale : 1.0f / sqrtf((float)Dq); }
+constexpr float XNA_LOG2E = 1.4426950408889634f;
+
+// The workgroup count of an attention launch: NAF_OK with *nblocks set, or NAF_ERR_INVALID with `who` (the entry's name) in the message.
+inline int xna_grid(const char* who, int64_t nb, uint32_t* nblocks) {
+    if (nb <= 0 || nb > 0x7fffffffLL) {
+        naf_set_error("%s: grid of %lld workgroups out of range", who, (long long)nb);
+        return NAF_ERR_INVALID;
+    }
+    *nblocks = (uint32_t)nb;
+    return NAF_OK;
+}
+
+// What every cell kernel asks of the geometry (A: naf_xna_args, naf_xna_head_args or naf_xna_bwd_args): a square odd window 3 .. 15,
+// Dq = 64, a grid no smaller than the window, an integer ratio.
+template <typename A>
+inline bool xna_cell_shape_ok(const A* a) {
+    const int ks = a->ky;
+    return a->ky == a->kx && ks >= 3 && ks <= 15 && (ks & 1) != 0 && a->Dq == 64 && a->h >= ks && a->w >= ks && a->Ho % a->h == 0 && a->Wo % a->w == 0;
+}
+
+// ... and of q / k / v (`v`: a->v_lr, or the head's a->pv_lr, with its strides): 16-byte pointers, strides in whole 16-byte chunks.
+template <typename A>
+inline bool xna_qkv_layout_ok(const A* a, const void* v, const int64_t* v_stride) {
+    if (!naf_aligned(a->q, 16) || !naf_aligned(a->k_lr, 16) || !naf_aligned(v, 16)) return false;
+    for (int i = 0; i < 4; ++i)
+        if (a->q_stride[i] % 8 || a->k_stride[i] % 8 || v_stride[i] % 8) return false;
+    return true;
+}
+
+// The fields every attention parameter struct shares (P: XnaMfmaParams, XnaUnionParams, XnaHeadParams, XnaBwdParams); the kernel's
+// value pointer and the rest are the caller's.
+template <typename P, typename A>
+inline void xna_fill_common(P& p, const A* a, const int64_t* v_stride, float scale) {
+    p.q = static_cast<const bf16_t*>(a->q);
+    p.k = static_cast<const bf16_t*>(a->k_lr);
+    p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w;
+    p.scale_log2e = scale * XNA_LOG2E;
+    for (int i = 0; i < 4; ++i) {
+        p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = v_stride[i];
+    }
+}
+
 // Bijective XCD-aware remap: hardware places block b on XCD b % 8; give every XCD one contiguous
 // range of logical ids so neighbouring cells (which share K/V windows) meet in the same L2.
 __device__ __forceinline__ uint32_t naf_xcd_remap(uint32_t bid, uint32_t n) {

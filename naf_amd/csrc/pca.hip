@@ -370,7 +370,6 @@ __global__ __launch_bounds__(PJ_THREADS) void pca_minmax_finish_kernel(const flo
     }
 }
 
-bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // NAF_OK, NAF_ERR_INVALID or NAF_ERR_UNSUPPORTED from the scalar fields alone
 int fm_check_scalars(const naf_feature_moments_args* a, const char* who) {
@@ -438,9 +437,9 @@ int naf_feature_moments(const naf_feature_moments_args* a, naf_stream_t stream) 
     NAF_REQUIRE(a->gram != nullptr, "%s: gram is NULL", who);
     NAF_REQUIRE(a->sum != nullptr, "%s: sum is NULL", who);
     NAF_REQUIRE(a->workspace != nullptr, "%s: workspace is NULL", who);
-    NAF_REQUIRE(aligned_to(a->x, 16), "%s: x must be 16-byte aligned", who);
-    NAF_REQUIRE(aligned_to(a->gram, 8) && aligned_to(a->sum, 8), "%s: gram and sum must be 8-byte aligned", who);
-    NAF_REQUIRE(aligned_to(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->x, 16), "%s: x must be 16-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->gram, 8) && naf_aligned(a->sum, 8), "%s: gram and sum must be 8-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
     const FmPlan pl = fm_plan(a->P, a->C);
     NAF_REQUIRE(a->workspace_bytes >= pl.bytes, "%s: workspace_bytes = %zu, %zu needed (naf_feature_moments_workspace_bytes)", who, a->workspace_bytes,
                 pl.bytes);
@@ -485,10 +484,10 @@ int naf_pca_project(const naf_pca_project_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->y != nullptr, "%s: y is NULL", who);
     NAF_REQUIRE(a->minmax != nullptr, "%s: minmax is NULL", who);
     NAF_REQUIRE(a->workspace != nullptr, "%s: workspace is NULL", who);
-    NAF_REQUIRE(aligned_to(a->x, 16), "%s: x must be 16-byte aligned", who);
-    NAF_REQUIRE(aligned_to(a->V, 4) && aligned_to(a->b, 4) && aligned_to(a->y, 4) && aligned_to(a->minmax, 4), "%s: V, b, y and minmax must be 4-byte aligned",
+    NAF_REQUIRE(naf_aligned(a->x, 16), "%s: x must be 16-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->V, 4) && naf_aligned(a->b, 4) && naf_aligned(a->y, 4) && naf_aligned(a->minmax, 4), "%s: V, b, y and minmax must be 4-byte aligned",
                 who);
-    NAF_REQUIRE(aligned_to(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
     const PjPlan pl = pj_plan(a->P);
     NAF_REQUIRE(a->workspace_bytes >= (size_t)pl.nwg * PJ_LINE, "%s: workspace_bytes = %zu, %zu needed (naf_pca_project_workspace_bytes)", who,
                 a->workspace_bytes, (size_t)pl.nwg * PJ_LINE);
@@ -517,8 +516,8 @@ int naf_pca_minmax(const naf_pca_minmax_args* a, naf_stream_t stream) {
     NAF_REQUIRE(a->y != nullptr, "%s: y is NULL", who);
     NAF_REQUIRE(a->minmax != nullptr, "%s: minmax is NULL", who);
     NAF_REQUIRE(a->workspace != nullptr, "%s: workspace is NULL", who);
-    NAF_REQUIRE(aligned_to(a->y, 4) && aligned_to(a->minmax, 4), "%s: y and minmax must be 4-byte aligned", who);
-    NAF_REQUIRE(aligned_to(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->y, 4) && naf_aligned(a->minmax, 4), "%s: y and minmax must be 4-byte aligned", who);
+    NAF_REQUIRE(naf_aligned(a->workspace, 16), "%s: workspace must be 16-byte aligned", who);
     const PjPlan pl = pj_plan(a->P);
     NAF_REQUIRE(a->workspace_bytes >= (size_t)pl.nwg * PJ_LINE, "%s: workspace_bytes = %zu, %zu needed (naf_pca_project_workspace_bytes of the same P)", who,
                 a->workspace_bytes, (size_t)pl.nwg * PJ_LINE);

@@ -1,12 +1,12 @@
 // Eligibility + dispatcher of the attention backward (mathematics: xna_bwd_params.h; the cell kernel: xna_bwd2_kernel.h).
 #include "xna_bwd2_kernel.h"
 
-#define NAF_DECL(K) int naf_xna_bwd_launch_k##K(const XnaBwdParams& p, int Dv, hipStream_t s); \
-    int naf_xna_bwd_scores_launch_k##K(const XnaBwdScoresParams& p, int Dv, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-
-static bool bwd_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
+// the instances: xna_bwd_inst.hip, one object per window (the plain backward and the one with a gradient of the scores)
+#define NAF_X(K)                                                                             \
+    extern template int xna_bwd2_launch_ks<K, false>(const XnaBwdParams&, int, hipStream_t); \
+    extern template int xna_bwd2_launch_ks<K, true>(const XnaBwdScoresParams&, int, hipStream_t);
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
 
 // Value channels per launch.  A window whose K / V tiles, round buffers or accumulators do not fit at the full Dv is served in CHANNEL CHUNKS:
 // the softmax depends on q and k only, dV splits by channel, and dQ / dK are sums over channels of V -- so the backward for a slice of V
@@ -40,31 +40,26 @@ static constexpr bool bwd_plan_served() {
         }
     return true;
 }
-static_assert(bwd_plan_served<3>() && bwd_plan_served<5>() && bwd_plan_served<7>() && bwd_plan_served<9>() && bwd_plan_served<11>() &&
-                  bwd_plan_served<13>() && bwd_plan_served<15>(),
-              "the chunk plan emits a (window, channels per launch) combination xna_bwd2_kernel does not serve");
+#define NAF_X(K) static_assert(bwd_plan_served<K>(), "the chunk plan emits a (window, channels per launch) combination xna_bwd2_kernel does not serve");
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
 
 // 1 when the cell kernel serves the request: the forward's MFMA conditions (square odd window 3..15, Dq = 64, integer
 // ratio, h, w >= window) plus row tiles (Wo/w % 16 == 0; up to 9 x 9 also 14, 15, 28, 30 ...) and Dv in {32, 64, 96, 128, 192, 256}
 // (all Dv up to k = 9 in one launch; wider heads at k = 11, 13 and 15 in channel chunks, above).
 int naf_xna_bwd_eligible(const naf_xna_bwd_args* a) {
-    if (a->ky != a->kx) return 0;
-    const int ks = a->ky;
-    if (ks < 3 || ks > 15 || (ks & 1) == 0) return 0;
-    if (a->Dq != 64) return 0;
-    if (a->h < ks || a->w < ks) return 0;
-    if (a->Ho % a->h != 0 || a->Wo % a->w != 0) return 0;
+    if (!xna_cell_shape_ok(a)) return 0;
     // cell rows of whole 16-query tiles -- or (round 6) rows whose last tile is partial, where the forward takes them too (xna_row_tiles_ok: the
     // 14-pixel cells of patch-14 backbones, 15, 28, 30 ...): windows up to 9 x 9 (the reference's training windows), whole heads
     const int dx = a->Wo / a->w;
-    if (dx % 16 != 0 && !(xna_row_tiles_ok(dx) && ks <= 9)) return 0;
+    if (dx % 16 != 0 && !(xna_row_tiles_ok(dx) && a->ky <= 9)) return 0;
     switch (a->Dv) {
         case 32: case 64: case 96: case 128: case 192: case 256: break;
         default: return 0;
     }
-    if (!bwd_aligned(a->q) || !bwd_aligned(a->k_lr) || !bwd_aligned(a->v_lr) || !bwd_aligned(a->dout) || !bwd_aligned(a->dq)) return 0;
+    if (!xna_qkv_layout_ok(a, a->v_lr, a->v_stride) || !naf_aligned(a->dout, 16) || !naf_aligned(a->dq, 16)) return 0;
     for (int i = 0; i < 4; ++i)
-        if (a->q_stride[i] % 8 || a->k_stride[i] % 8 || a->v_stride[i] % 8 || a->dout_stride[i] % 8 || a->dq_stride[i] % 8) return 0;
+        if (a->dout_stride[i] % 8 || a->dq_stride[i] % 8) return 0;
     return 1;
 }
 
@@ -89,26 +84,14 @@ int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, co
         return NAF_ERR_UNSUPPORTED;
     }
     XnaBwdParams p;
-    p.q = static_cast<const bf16_t*>(a->q);
-    p.k = static_cast<const bf16_t*>(a->k_lr);
-    p.v = static_cast<const bf16_t*>(a->v_lr);
-    p.dout = static_cast<const bf16_t*>(a->dout);
+    xna_fill_common(p, a, a->v_stride, scale);
     p.dq = static_cast<bf16_t*>(a->dq);
     p.dk = a->dk_lr;
-    p.dv = a->dv_lr;
-    p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w;
     p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
-    const int64_t nb = (int64_t)a->B * a->h * a->w * a->heads;
-    if (nb <= 0 || nb > 0x7fffffffLL) {
-        naf_set_error("naf_xna_bwd: grid of %lld workgroups out of range", (long long)nb);
-        return NAF_ERR_INVALID;
-    }
-    p.nblocks = (uint32_t)nb;
+    if (const int rc = xna_grid("naf_xna_bwd", (int64_t)a->B * a->h * a->w * a->heads, &p.nblocks)) return rc;
     p.seg_len = 1; p.nseg = a->w;
     p.scale = scale;
-    p.scale_log2e = scale * 1.4426950408889634f;
     for (int i = 0; i < 4; ++i) {
-        p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i];
         p.gs[i] = a->dout_stride[i]; p.dqs[i] = a->dq_stride[i];
     }
     p.dv_pitch = a->Dv;
@@ -129,23 +112,16 @@ int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, co
             ps.dl = sg->dlogits;
             for (int i = 0; i < 4; ++i) ps.dls[i] = sg->dlogits_stride[i];
             switch (a->ky) {
-                case 3: rc = naf_xna_bwd_scores_launch_k3(ps, dvc, s); break;
-                case 5: rc = naf_xna_bwd_scores_launch_k5(ps, dvc, s); break;
-                case 7: rc = naf_xna_bwd_scores_launch_k7(ps, dvc, s); break;
-                case 9: rc = naf_xna_bwd_scores_launch_k9(ps, dvc, s); break;
-                case 11: rc = naf_xna_bwd_scores_launch_k11(ps, dvc, s); break;
-                case 13: rc = naf_xna_bwd_scores_launch_k13(ps, dvc, s); break;
-                case 15: rc = naf_xna_bwd_scores_launch_k15(ps, dvc, s); break;
+#define NAF_X(K) case K: rc = xna_bwd2_launch_ks<K, true>(ps, dvc, s); break;
+                NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
             }
-        } else
-        switch (a->ky) {
-            case 3: rc = naf_xna_bwd_launch_k3(p, dvc, s); break;
-            case 5: rc = naf_xna_bwd_launch_k5(p, dvc, s); break;
-            case 7: rc = naf_xna_bwd_launch_k7(p, dvc, s); break;
-            case 9: rc = naf_xna_bwd_launch_k9(p, dvc, s); break;
-            case 11: rc = naf_xna_bwd_launch_k11(p, dvc, s); break;
-            case 13: rc = naf_xna_bwd_launch_k13(p, dvc, s); break;
-            case 15: rc = naf_xna_bwd_launch_k15(p, dvc, s); break;
+        } else {
+            switch (a->ky) {
+#define NAF_X(K) case K: rc = xna_bwd2_launch_ks<K, false>(p, dvc, s); break;
+                NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
+            }
         }
         if (rc != NAF_OK) return rc;
         c0 += dvc;

@@ -899,7 +899,7 @@ static int xna_bwd2_launch_one(const XnaBwdParamsT<SG>& p, hipStream_t s) {
 
 // Dv: the value channels of the launch (a whole head or a channel chunk).  Only the widths the kernel serves at the window are instantiated.
 template <int KS, bool SG = false>
-static int xna_bwd2_launch_ks(const XnaBwdParamsT<SG>& p, int Dv, hipStream_t s) {
+int xna_bwd2_launch_ks(const XnaBwdParamsT<SG>& p, int Dv, hipStream_t s) {
 #define NAF_BWD2_CASE(D)                                                            \
     if constexpr (xna_bwd2_serves<KS, D>()) {                                       \
         if (Dv == D) return xna_bwd2_launch_one<KS, D, SG>(p, s);                   \

@@ -1,28 +1,21 @@
 // Eligibility test + dispatcher for the head-summed MFMA cell kernel (see xna_head_kernel.h).
+#include <stdio.h>
+
 #include "xna_head_kernel.h"
 
-NAF_XNA_HEAD_WINDOW(extern, 3) NAF_XNA_HEAD_WINDOW(extern, 5) NAF_XNA_HEAD_WINDOW(extern, 7) NAF_XNA_HEAD_WINDOW(extern, 9)
-NAF_XNA_HEAD_WINDOW(extern, 11) NAF_XNA_HEAD_WINDOW(extern, 13) NAF_XNA_HEAD_WINDOW(extern, 15)
-
-static bool head_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
+// the instances: xna_head_inst.hip, one object per window
+#define NAF_X(K) NAF_XNA_HEAD_WINDOW(extern, K)
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
 
 // NAF_OK when the kernel serves the (validated) request; otherwise NAF_ERR_UNSUPPORTED with the reason in the error string.
 int naf_xna_head_eligible(const naf_xna_head_args* a) {
-    const int ks = a->ky;
-    if (a->ky != a->kx || ks < 3 || ks > 15) {
-        naf_set_error("naf_xna_head: the fused kernel needs a square window 3 .. 15 (got %dx%d)", a->ky, a->kx);
-        return NAF_ERR_UNSUPPORTED;
-    }
-    if (a->Dq != 64) {
-        naf_set_error("naf_xna_head: the fused kernel needs Dq = 64 (got %d)", a->Dq);
-        return NAF_ERR_UNSUPPORTED;
-    }
-    if (a->h < ks || a->w < ks) {
-        naf_set_error("naf_xna_head: the fused kernel needs h, w >= window (got %dx%d, window %d)", a->h, a->w, ks);
-        return NAF_ERR_UNSUPPORTED;
-    }
-    if (a->Ho % a->h != 0 || a->Wo % a->w != 0) {
-        naf_set_error("naf_xna_head: the fused kernel needs an integer ratio (got %dx%d -> %dx%d)", a->h, a->w, a->Ho, a->Wo);
+    if (!xna_cell_shape_ok(a)) {   // which of its conditions (an even window never gets here: the entries refuse it)
+        const int ks = a->ky;
+        if (a->ky != a->kx || ks < 3 || ks > 15) naf_set_error("naf_xna_head: the fused kernel needs a square window 3 .. 15 (got %dx%d)", a->ky, a->kx);
+        else if (a->Dq != 64) naf_set_error("naf_xna_head: the fused kernel needs Dq = 64 (got %d)", a->Dq);
+        else if (a->h < ks || a->w < ks) naf_set_error("naf_xna_head: the fused kernel needs h, w >= window (got %dx%d, window %d)", a->h, a->w, ks);
+        else naf_set_error("naf_xna_head: the fused kernel needs an integer ratio (got %dx%d -> %dx%d)", a->h, a->w, a->Ho, a->Wo);
         return NAF_ERR_UNSUPPORTED;
     }
     const int dy = a->Ho / a->h, dx = a->Wo / a->w;
@@ -31,15 +24,10 @@ int naf_xna_head_eligible(const naf_xna_head_args* a) {
                       a->h, a->w, a->Ho, a->Wo);
         return NAF_ERR_UNSUPPORTED;
     }
-    if (!head_aligned(a->q) || !head_aligned(a->k_lr) || !head_aligned(a->pv_lr)) {
-        naf_set_error("naf_xna_head: the fused kernel needs 16-byte aligned q, k_lr, pv_lr");
+    if (!xna_qkv_layout_ok(a, a->pv_lr, a->pv_stride)) {   // which half of it
+        if (!naf_aligned(a->q, 16) || !naf_aligned(a->k_lr, 16) || !naf_aligned(a->pv_lr, 16)) naf_set_error("naf_xna_head: the fused kernel needs 16-byte aligned q, k_lr, pv_lr");
+        else naf_set_error("naf_xna_head: the fused kernel needs q / k_lr / pv_lr strides that are multiples of 8 elements");
         return NAF_ERR_UNSUPPORTED;
-    }
-    for (int i = 0; i < 4; ++i) {
-        if (a->q_stride[i] % 8 || a->k_stride[i] % 8 || a->pv_stride[i] % 8) {
-            naf_set_error("naf_xna_head: the fused kernel needs q / k_lr / pv_lr strides that are multiples of 8 elements");
-            return NAF_ERR_UNSUPPORTED;
-        }
     }
     return NAF_OK;
 }
@@ -49,7 +37,7 @@ int naf_xna_head_ce_eligible(const naf_xna_head_ce_args* c) {
     const int rc = naf_xna_head_eligible(&c->head);
     if (rc != NAF_OK) return rc;
     if (c->dlogits != nullptr) {
-        if (!head_aligned(c->dlogits)) {
+        if (!naf_aligned(c->dlogits, 16)) {
             naf_set_error("naf_xna_head_ce: the fused kernel needs a 16-byte aligned dlogits");
             return NAF_ERR_UNSUPPORTED;
         }
@@ -65,28 +53,18 @@ int naf_xna_head_ce_eligible(const naf_xna_head_ce_args* c) {
 
 // `tag` names the variant in the messages: the C entry point is naf_<tag>_fwd.
 static int head_fill_params(const naf_xna_head_args* a, float scale, const char* tag, XnaHeadParams& p) {
-    p.q = static_cast<const bf16_t*>(a->q);
-    p.k = static_cast<const bf16_t*>(a->k_lr);
+    xna_fill_common(p, a, a->pv_stride, scale);
     p.pv = static_cast<const bf16_t*>(a->pv_lr);
     p.bias = a->bias;
     p.out = a->out;
     p.tab_y = a->rope_tab_y; p.tab_x = a->rope_tab_x;
-    p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w;
     p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
     p.N = a->N;
     p.npad = (a->N + 15) & ~15;
-    const int64_t nb = (int64_t)a->B * a->h * a->w;
-    if (nb <= 0 || nb > 0x7fffffffLL) {
-        naf_set_error("naf_%s_fwd: grid of %lld workgroups out of range", tag, (long long)nb);
-        return NAF_ERR_INVALID;
-    }
-    p.nblocks = (uint32_t)nb;
-    p.scale_log2e = scale * 1.4426950408889634f;
-    for (int i = 0; i < 4; ++i) {
-        p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->pv_stride[i];
-    }
     for (int i = 0; i < 3; ++i) p.os[i] = a->o_stride[i];
-    return NAF_OK;
+    char who[32];
+    snprintf(who, sizeof(who), "naf_%s_fwd", tag);
+    return xna_grid(who, (int64_t)a->B * a->h * a->w, &p.nblocks);
 }
 
 // Fills the parameters and dispatches on the window; `what` names the launch in a launch error, `x` is the variant's extra kernel argument.
@@ -96,9 +74,9 @@ static int head_launch(const naf_xna_head_args* a, float scale, hipStream_t s, c
     const int rc = head_fill_params(a, scale, tag, p);
     if (rc != NAF_OK) return rc;
     switch (a->ky) {
-#define NAF_CASE(K) case K: return xna_head_launch_ks<K>(p, a->out_dtype, s, tag, what, x...);
-        NAF_CASE(3) NAF_CASE(5) NAF_CASE(7) NAF_CASE(9) NAF_CASE(11) NAF_CASE(13) NAF_CASE(15)
-#undef NAF_CASE
+#define NAF_X(K) case K: return xna_head_launch_ks<K>(p, a->out_dtype, s, tag, what, x...);
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
     }
     naf_set_error("naf_%s_fwd: kernel size %d has no instantiation", tag, a->ky);
     return NAF_ERR_UNSUPPORTED;

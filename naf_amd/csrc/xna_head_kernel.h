@@ -481,7 +481,7 @@ static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s, const char
     return naf_check_launch(what);
 }
 
-// The window's entry point, one explicit instantiation per variant in xna_head_k<KS>.hip.  `who` names the variant in the messages
+// The window's entry point, one explicit instantiation per variant in xna_head_inst.hip.  `who` names the variant in the messages
 // ("xna_head", "xna_head_ce", "xna_head_cm"); the logits variant stores bf16 or float, the epilogues float only.
 template <int KS, typename... Extra>
 int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s, const char* who, const char* what, const Extra&... extra) {
@@ -501,7 +501,7 @@ int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s, con
     return NAF_ERR_UNSUPPORTED;
 }
 
-// xna_head_k<KS>.hip defines these three, xna_head.hip declares them (extern) and dispatches on the window.
+// xna_head_inst.hip (-DNAF_KS=<KS>) defines these three, xna_head.hip declares them (extern) and dispatches on the window.
 #define NAF_XNA_HEAD_WINDOW(LINKAGE, KS)                                                                                                        \
     LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*);                              \
     LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadCEExtra&);       \

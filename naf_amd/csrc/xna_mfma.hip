@@ -3,40 +3,27 @@
 
 #include "xna_slide_kernel.h"
 
-#define NAF_DECL(K) int naf_xna_mfma_launch_k##K(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-// half values and output (NAF_F16): xna_mfma_h_k*.hip / xna_slide_h_k*.hip
-#define NAF_DECL(K) int naf_xna_mfma_launch_h_k##K(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-#define NAF_DECL(K) int naf_xna_slide_launch_h_k##K(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
-NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-int naf_xna_slide_launch_k7(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
-int naf_xna_slide_launch_k9(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
-int naf_xna_slide_launch_k11(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
-int naf_xna_slide_launch_k13(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
-int naf_xna_slide_launch_k15(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s);
-
-static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+// the instances: xna_mfma_inst.hip / xna_slide_inst.hip, one object per (window, value type)
+#define NAF_X(K)                                                                                                   \
+    extern template int xna_mfma_launch_ks<K, false>(const XnaMfmaParams&, const XnaMfmaPlan&, int, hipStream_t);  \
+    extern template int xna_mfma_launch_ks<K, true>(const XnaMfmaParams&, const XnaMfmaPlan&, int, hipStream_t);
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
+#define NAF_X(K)                                                                                  \
+    extern template int xna_slide_launch_ks<K, false>(const XnaSlideParams&, int, int, hipStream_t); \
+    extern template int xna_slide_launch_ks<K, true>(const XnaSlideParams&, int, int, hipStream_t);
+NAF_FOR_SLIDE_WINDOWS(NAF_X)
+#undef NAF_X
 
 // Returns 1 when the MFMA cell kernel can serve the request (and the Dv tile / LDS bytes it would
 // use), 0 otherwise.  Never sets the error string: ineligibility is not an error.
 int naf_xna_mfma_eligible(const naf_xna_args* a, int* dvt_out, size_t* lds_out) {
-    if (a->ky != a->kx) return 0;
-    const int ks = a->ky;
-    if (ks < 3 || ks > 15 || (ks & 1) == 0) return 0;
-    if (a->Dq != 64) return 0;
-    if (a->h < ks || a->w < ks) return 0;
-    if (a->Ho % a->h != 0 || a->Wo % a->w != 0) return 0;
-    if (a->Dv % 16 != 0) return 0;
-    if (!aligned_to(a->q, 16) || !aligned_to(a->k_lr, 16) || !aligned_to(a->v_lr, 16) || !aligned_to(a->out, 16)) return 0;
-    for (int i = 0; i < 4; ++i) {
-        if (a->q_stride[i] % 8 || a->k_stride[i] % 8 || a->v_stride[i] % 8 || a->o_stride[i] % 4) return 0;
-    }
+    if (!xna_cell_shape_ok(a) || a->Dv % 16 != 0) return 0;
+    if (!xna_qkv_layout_ok(a, a->v_lr, a->v_stride) || !naf_aligned(a->out, 16)) return 0;
+    for (int i = 0; i < 4; ++i)
+        if (a->o_stride[i] % 4) return 0;
     XnaMfmaPlan pl;
-    if (!xna_mfma_plan(ks, a->Dv, a->out_dtype, &pl)) return 0;
+    if (!xna_mfma_plan(a->ky, a->Dv, a->out_dtype, &pl)) return 0;
     if (dvt_out) *dvt_out = pl.dvt;
     if (lds_out) *lds_out = pl.lds;
     return 1;
@@ -61,12 +48,10 @@ int naf_launch_xna_mfma(const naf_xna_args* a, float scale, hipStream_t s) {
         return NAF_ERR_UNSUPPORTED;
     }
     XnaMfmaParams p;
-    p.q = static_cast<const bf16_t*>(a->q);
-    p.k = static_cast<const bf16_t*>(a->k_lr);
+    xna_fill_common(p, a, a->v_stride, scale);
     p.v = static_cast<const bf16_t*>(a->v_lr);
     p.out = a->out;
     p.logits = a->logits;
-    p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w;
     p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
     p.tab_y = a->rope_tab_y; p.tab_x = a->rope_tab_x;
     if (a->rope_tab_y != nullptr && !naf_xna_mfma_rope_ok(a)) {
@@ -78,25 +63,19 @@ int naf_launch_xna_mfma(const naf_xna_args* a, float scale, hipStream_t s) {
     p.nchunk = a->Dv / pl.dvt;
     const int bh = (a->h + pl.cb - 1) / pl.cb, bw = (a->w + pl.cb - 1) / pl.cb;
     const int64_t nb = (int64_t)a->B * bh * bw * a->heads * p.nchunk;
-    if (nb <= 0 || nb > 0x7fffffffLL) {
-        naf_set_error("naf_xna_fwd: grid of %lld workgroups out of range", (long long)nb);
-        return NAF_ERR_INVALID;
-    }
-    p.nblocks = (uint32_t)nb;
+    if (const int rc = xna_grid("naf_xna_fwd", nb, &p.nblocks)) return rc;
     // dispatch order in groups of 16 workgroups per XCD turn (xna_block_order; profiles/r02_hbm_ceiling.txt: all XCDs
     // sweep the same cell rows, +5..9 % over one band of cell rows per XCD); NAF_XNA_ORDER=0 restores the bands (A/B knob)
     static const int order = [] { const char* e = naf_knob("NAF_XNA_ORDER"); return e ? atoi(e) : 16; }();
     p.order = order;
     static const int rope_lds = [] { const char* e = naf_knob("NAF_XNA_ROPE_LDS"); return e ? atoi(e) : 1; }();   // A/B knob
     p.rope_lds = rope_lds;
-    p.scale_log2e = scale * 1.4426950408889634f;
     p.scale = scale;
-    for (int i = 0; i < 4; ++i) {
-        p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i]; p.os[i] = a->o_stride[i];
-    }
+    for (int i = 0; i < 4; ++i) p.os[i] = a->o_stride[i];
     // Whenever the plan has no staged stores (windows of 11x11 and up, fp32 output, windows + staging tiles that would
     // leave fewer than 3 workgroups per CU) and the geometry has row tiles: persistent sliding-window kernel
     // (xna_slide_kernel.h).  return_weights needs the window's row-major slot order and stays on the cell kernel.
+    const bool half = a->out_dtype == NAF_F16;   // half values and output: the HALF instances
     static const bool no_slide = [] { const char* e = naf_knob("NAF_XNA_SLIDE"); return e && atoi(e) == 0; }();   // A/B knob
     if (a->ky >= 7 && !pl.staged && !no_slide && a->logits == nullptr && (p.dx % 16) == 0 && (int64_t)p.dy * p.dx / 16 <= 1024) {
         XnaSlideParams sp;
@@ -117,49 +96,19 @@ int naf_launch_xna_mfma(const naf_xna_args* a, float scale, hipStream_t s) {
         sp.seg_len = (int32_t)((a->w + nseg - 1) / nseg);
         sp.nseg = (int32_t)((a->w + sp.seg_len - 1) / sp.seg_len);
         const int64_t nbs = rows * sp.nseg;
-        if (nbs > 0x7fffffffLL) {
-            naf_set_error("naf_xna_fwd: grid of %lld workgroups out of range", (long long)nbs);
-            return NAF_ERR_INVALID;
-        }
-        sp.m.nblocks = (uint32_t)nbs;
+        if (const int rc = xna_grid("naf_xna_fwd", nbs, &sp.m.nblocks)) return rc;
         // (A tail hand-over -- finished workgroups claiming the last cells of other segments -- was built, bit-identical and 2-6 % slower at
         // G2-k11: profiles/r06_other_workloads.txt.  The split of a cell row into segments is static.)
-        if (a->out_dtype == NAF_F16) {
-            switch (a->ky) {
-                case 7: return naf_xna_slide_launch_h_k7(sp, dvt_u, a->out_dtype, s);
-                case 9: return naf_xna_slide_launch_h_k9(sp, dvt_u, a->out_dtype, s);
-                case 11: return naf_xna_slide_launch_h_k11(sp, dvt_u, a->out_dtype, s);
-                case 13: return naf_xna_slide_launch_h_k13(sp, dvt_u, a->out_dtype, s);
-                case 15: return naf_xna_slide_launch_h_k15(sp, dvt_u, a->out_dtype, s);
-            }
-        }
         switch (a->ky) {
-            case 7: return naf_xna_slide_launch_k7(sp, dvt_u, a->out_dtype, s);
-            case 9: return naf_xna_slide_launch_k9(sp, dvt_u, a->out_dtype, s);
-            case 11: return naf_xna_slide_launch_k11(sp, dvt_u, a->out_dtype, s);
-            case 13: return naf_xna_slide_launch_k13(sp, dvt_u, a->out_dtype, s);
-            case 15: return naf_xna_slide_launch_k15(sp, dvt_u, a->out_dtype, s);
-        }
-    }
-    if (a->out_dtype == NAF_F16) {
-        switch (a->ky) {
-            case 3: return naf_xna_mfma_launch_h_k3(p, pl, a->out_dtype, s);
-            case 5: return naf_xna_mfma_launch_h_k5(p, pl, a->out_dtype, s);
-            case 7: return naf_xna_mfma_launch_h_k7(p, pl, a->out_dtype, s);
-            case 9: return naf_xna_mfma_launch_h_k9(p, pl, a->out_dtype, s);
-            case 11: return naf_xna_mfma_launch_h_k11(p, pl, a->out_dtype, s);
-            case 13: return naf_xna_mfma_launch_h_k13(p, pl, a->out_dtype, s);
-            case 15: return naf_xna_mfma_launch_h_k15(p, pl, a->out_dtype, s);
+#define NAF_X(K) case K: return half ? xna_slide_launch_ks<K, true>(sp, dvt_u, a->out_dtype, s) : xna_slide_launch_ks<K, false>(sp, dvt_u, a->out_dtype, s);
+            NAF_FOR_SLIDE_WINDOWS(NAF_X)
+#undef NAF_X
         }
     }
     switch (a->ky) {
-        case 3: return naf_xna_mfma_launch_k3(p, pl, a->out_dtype, s);
-        case 5: return naf_xna_mfma_launch_k5(p, pl, a->out_dtype, s);
-        case 7: return naf_xna_mfma_launch_k7(p, pl, a->out_dtype, s);
-        case 9: return naf_xna_mfma_launch_k9(p, pl, a->out_dtype, s);
-        case 11: return naf_xna_mfma_launch_k11(p, pl, a->out_dtype, s);
-        case 13: return naf_xna_mfma_launch_k13(p, pl, a->out_dtype, s);
-        case 15: return naf_xna_mfma_launch_k15(p, pl, a->out_dtype, s);
+#define NAF_X(K) case K: return half ? xna_mfma_launch_ks<K, true>(p, pl, a->out_dtype, s) : xna_mfma_launch_ks<K, false>(p, pl, a->out_dtype, s);
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
     }
     naf_set_error("naf_xna_fwd: kernel size %d has no MFMA instantiation", a->ky);
     return NAF_ERR_UNSUPPORTED;

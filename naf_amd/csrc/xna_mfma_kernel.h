@@ -997,9 +997,9 @@ inline bool xna_mfma_plan(int ks, int Dv, int out_dtype, XnaMfmaPlan* pl) {
     return false;
 }
 
-// HALF: the NAF_F16 instantiations (half values and output, XnaVal in naf_common.h) -- translation units of their own (xna_mfma_h_k*.hip)
+// HALF: the NAF_F16 instantiations (half values and output, XnaVal in naf_common.h) -- objects of their own (xna_mfma_inst.hip)
 template <int KS, bool HALF = false>
-static int xna_mfma_launch_ks(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s) {
+int xna_mfma_launch_ks(const XnaMfmaParams& p, const XnaMfmaPlan& pl, int out_dtype, hipStream_t s) {
     constexpr int CBM = xna_mfma_cb(KS);
 #define NAF_TRY(D, ST, CBV, T)                                                              \
     if constexpr (xna_mfma_lds_for(KS, CBV, D, ST) <= 160 * 1024 && (!(ST) || ((D % 32 == 0) && xna_mfma_tpw(KS) == 1))) \

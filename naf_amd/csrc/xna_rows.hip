@@ -173,7 +173,6 @@ __global__ __launch_bounds__(256) void xna_rows_kernel(const XnaRowsParams p) {
 }
 
 namespace {
-bool aligned_to(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; }
 
 }  // namespace
 
@@ -224,7 +223,7 @@ int naf_xna_rows_eligible(const naf_xna_args* a) {
     if (a->logits != nullptr || a->rope_tab_y != nullptr) return 0;
     if (a->Ho < a->h || a->Wo < a->w) return 0;
     if ((int64_t)a->ky * (a->Wo / a->w) > a->Wo || (int64_t)a->ky * (a->Ho / a->h) > a->Ho) return 0;
-    if (!aligned_to(a->q, 16) || !aligned_to(a->k_lr, 16)) return 0;
+    if (!naf_aligned(a->q, 16) || !naf_aligned(a->k_lr, 16)) return 0;
     for (int i = 0; i < 4; ++i)
         if (a->q_stride[i] % 8 || a->k_stride[i] % 8) return 0;
     return naf_tile_span(a->Wo, a->w, a->kx) <= 32 ? 1 : 0;
@@ -249,7 +248,7 @@ int naf_launch_xna_rows(const naf_xna_args* a, float scale, hipStream_t s) {
     p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w; p.Dv = a->Dv; p.ks = a->ky;
     p.ntx = (a->Wo + 15) / 16;
     p.ntiles = (int64_t)a->B * a->heads * a->Ho * p.ntx;
-    p.scale_log2e = scale * 1.4426950408889634f;
+    p.scale_log2e = scale * XNA_LOG2E;
     for (int i = 0; i < 4; ++i) {
         p.qs[i] = a->q_stride[i]; p.kst[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i]; p.os[i] = a->o_stride[i];
     }

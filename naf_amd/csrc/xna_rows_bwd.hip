@@ -488,7 +488,6 @@ __global__ __launch_bounds__(256, (rb_regs_heavy(NDQ, NDV) ? 1 : 2)) void xna_ro
 }
 
 namespace {
-bool rb_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) % 16) == 0; }
 
 template <int NDQ, int NDV, bool MULT, int NH, bool SG = false>
 int launch_rows_bwd_mh(const std::conditional_t<SG, XnaRowsBwdScoresParams, XnaRowsBwdParams>& p, hipStream_t s) {
@@ -537,7 +536,7 @@ bool rb_ndq_ok(int ndq) { return ndq == 2 || ndq == 3 || ndq == 4 || ndq == 6 ||
 bool rb_ndv_ok(int ndv) { return ndv == 1 || ndv == 2 || ndv == 3 || ndv == 4 || ndv == 6 || ndv == 8; }
 // value side: 0 = few channels (Dv <= 32 through gathers, any head dim of the list), > 0 = Dv / 32 k-steps (heads of 64), -1 = not served
 int rb_value_form(const naf_xna_bwd_args* a) {
-    if (a->Dq == 64 && a->Dv % 32 == 0 && rb_ndv_ok(a->Dv / 32) && rb_aligned(a->v_lr) && rb_aligned(a->dout)) {
+    if (a->Dq == 64 && a->Dv % 32 == 0 && rb_ndv_ok(a->Dv / 32) && naf_aligned(a->v_lr, 16) && naf_aligned(a->dout, 16)) {
         bool ok = true;
         for (int i = 0; i < 4; ++i) ok = ok && a->v_stride[i] % 8 == 0 && a->dout_stride[i] % 8 == 0;
         if (ok) return a->Dv / 32;
@@ -560,7 +559,7 @@ int naf_xna_rows_bwd_eligible(const naf_xna_bwd_args* a) {
     if (integer_ratio ? (a->ky > a->h || a->kx > a->w) : (naf_tile_span(a->Wo, a->w, a->kx) > 32)) return 0;
     if (a->Dq % 32 != 0 || !rb_ndq_ok(a->Dq / 32)) return 0;
     if (rb_value_form(a) < 0) return 0;
-    if (!rb_aligned(a->q) || !rb_aligned(a->k_lr)) return 0;
+    if (!naf_aligned(a->q, 16) || !naf_aligned(a->k_lr, 16)) return 0;
     for (int i = 0; i < 4; ++i)
         if (a->q_stride[i] % 8 || a->k_stride[i] % 8) return 0;
     if ((int64_t)a->B * a->heads * a->Ho * ((a->Wo + 15) / 16) > 0x7fffffffLL) return 0;
@@ -575,7 +574,7 @@ int naf_launch_xna_rows_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t 
         return NAF_ERR_UNSUPPORTED;
     }
     if (a->idx_y == nullptr || a->idx_x == nullptr || a->workspace == nullptr || (size_t)a->workspace_bytes < naf_xna_rows_bwd_workspace(a) ||
-        !rb_aligned(a->workspace)) {
+        !naf_aligned(a->workspace, 16)) {
         naf_set_error("naf_xna_bwd: the row-streaming MFMA backward needs idx_y / idx_x and %zu bytes of 16-byte aligned workspace",
                       naf_xna_rows_bwd_workspace(a));
         return NAF_ERR_INVALID;
@@ -608,7 +607,7 @@ int naf_launch_xna_rows_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t 
     p.ntiles[0] = (int64_t)a->B * a->heads * a->Ho * p.ntx[0];
     p.ntiles[1] = (int64_t)a->B * a->heads * a->h * p.ntx[1];
     p.scale = scale;
-    p.scale_log2e = scale * 1.4426950408889634f;
+    p.scale_log2e = scale * XNA_LOG2E;
     for (int i = 0; i < 4; ++i) {
         p.qs[i] = a->q_stride[i]; p.kst[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i];
         p.gs[i] = a->dout_stride[i]; p.dqs[i] = a->dq_stride[i];

@@ -573,9 +573,9 @@ static int xna_slide_launch_one(const XnaSlideParams& sp, hipStream_t s) {
 }
 
 // Dv tiles as the cell kernel plans them for unstaged stores (largest divisor of Dv that fits the LDS)
-// HALF: the NAF_F16 instantiations (xna_slide_h_k*.hip)
+// HALF: the NAF_F16 instantiations (objects of their own: xna_slide_inst.hip)
 template <int KS, bool HALF = false>
-static int xna_slide_launch_ks(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s) {
+int xna_slide_launch_ks(const XnaSlideParams& sp, int dvt, int out_dtype, hipStream_t s) {
 #define NAF_SLIDE_CASE(D)                                                                              \
     if constexpr (xna_mfma_lds_for(KS, 1, D, false) <= 160 * 1024) {                                   \
         if (dvt == D) {                                                                                \

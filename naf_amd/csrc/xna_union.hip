@@ -17,21 +17,14 @@
 
 #include "xna_union_kernel.h"
 
-#define NAF_DECL(K) int naf_xna_union_launch_k##K(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
-// half values and output (NAF_F16): xna_union_h_k*.hip
-#define NAF_DECL(K) int naf_xna_union_launch_h_k##K(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
+// the instances: xna_union_inst.hip, one object per (window, value type)
+#define NAF_X(K)                                                                                           \
+    extern template int xna_union_launch_ks<K, false>(const XnaUnionParams&, int, int, size_t, hipStream_t); \
+    extern template int xna_union_launch_ks<K, true>(const XnaUnionParams&, int, int, size_t, hipStream_t);
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
 
 namespace {
-struct UnionPlan {
-    int ok = 0;
-    int wt = 0, ry = 0, seg = 0, hub = 0, wub = 0, dvt = 0;
-    size_t lds = 0;
-};
-
 // widest [min first tap, max last tap] over the aligned blocks of `blk` table rows
 int span_max(const std::vector<int32_t>& tab, int L, int k, int blk) {
     int worst = 0;
@@ -106,6 +99,8 @@ UnionPlan make_plan(int Ho, int h, int Wo, int w, int k, int Dv, int64_t groups)
     return best;
 }
 
+}  // namespace
+
 // (returned by value: another thread may evict the cache entry)
 UnionPlan plan_for(const naf_xna_args* a) {
     using Key = std::tuple<int, int, int, int, int, int, int64_t>;
@@ -122,9 +117,6 @@ UnionPlan plan_for(const naf_xna_args* a) {
     return it->second;
 }
 
-bool aligned_to(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; }
-}  // namespace
-
 // 1 when the table-driven MFMA kernel can serve the request (needs idx_y / idx_x at launch), 0 otherwise.
 int naf_xna_union_eligible(const naf_xna_args* a) {
     if (a->ky != a->kx) return 0;
@@ -133,10 +125,25 @@ int naf_xna_union_eligible(const naf_xna_args* a) {
     if (a->Dq != 64 || a->Dv % 16 != 0) return 0;
     if (a->logits != nullptr || a->rope_tab_y != nullptr) return 0;
     if (a->Ho < a->h || a->Wo < a->w) return 0;
-    if (!aligned_to(a->q, 16) || !aligned_to(a->k_lr, 16) || !aligned_to(a->v_lr, 16) || !aligned_to(a->out, 16)) return 0;
+    if (!xna_qkv_layout_ok(a, a->v_lr, a->v_stride) || !naf_aligned(a->out, 16)) return 0;
     for (int i = 0; i < 4; ++i)
-        if (a->q_stride[i] % 8 || a->k_stride[i] % 8 || a->v_stride[i] % 8 || a->o_stride[i] % 4) return 0;
+        if (a->o_stride[i] % 4) return 0;
     return plan_for(a).ok;
+}
+
+int xna_union_fill(const naf_xna_args* a, const UnionPlan& pl, float scale, const char* who, XnaUnionParams& p) {
+    xna_fill_common(p, a, a->v_stride, scale);
+    p.v = static_cast<const bf16_t*>(a->v_lr);
+    p.out = a->out;
+    p.idx_y = a->idx_y;
+    p.idx_x = a->idx_x;
+    p.dvt = pl.dvt; p.nchunk = a->Dv / pl.dvt;
+    p.ry = pl.ry; p.seg = pl.seg;
+    p.nyb = (a->Ho + pl.ry - 1) / pl.ry;
+    p.nxb = (a->Wo + pl.seg - 1) / pl.seg;
+    p.hub = pl.hub; p.wub = pl.wub;
+    for (int i = 0; i < 4; ++i) p.os[i] = a->o_stride[i];
+    return xna_grid(who, (int64_t)a->B * a->heads * p.nchunk * p.nyb * p.nxb, &p.nblocks);
 }
 
 int naf_launch_xna_union(const naf_xna_args* a, float scale, hipStream_t s) {
@@ -152,47 +159,12 @@ int naf_launch_xna_union(const naf_xna_args* a, float scale, hipStream_t s) {
     }
     const UnionPlan pl = plan_for(a);
     XnaUnionParams p;
-    p.q = static_cast<const bf16_t*>(a->q);
-    p.k = static_cast<const bf16_t*>(a->k_lr);
-    p.v = static_cast<const bf16_t*>(a->v_lr);
-    p.out = a->out;
-    p.idx_y = a->idx_y;
-    p.idx_x = a->idx_x;
-    p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w;
-    p.dvt = pl.dvt; p.nchunk = a->Dv / pl.dvt;
-    p.ry = pl.ry; p.seg = pl.seg;
-    p.nyb = (a->Ho + pl.ry - 1) / pl.ry;
-    p.nxb = (a->Wo + pl.seg - 1) / pl.seg;
-    p.hub = pl.hub; p.wub = pl.wub;
-    const int64_t nb = (int64_t)a->B * a->heads * p.nchunk * p.nyb * p.nxb;
-    if (nb <= 0 || nb > 0x7fffffffLL) {
-        naf_set_error("naf_xna_fwd: grid of %lld workgroups out of range", (long long)nb);
-        return NAF_ERR_INVALID;
-    }
-    p.nblocks = (uint32_t)nb;
-    p.scale_log2e = scale * 1.4426950408889634f;
-    for (int i = 0; i < 4; ++i) {
-        p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i]; p.os[i] = a->o_stride[i];
-    }
-    if (a->out_dtype == NAF_F16) {
-        switch (a->ky) {
-            case 3: return naf_xna_union_launch_h_k3(p, pl.wt, a->out_dtype, pl.lds, s);
-            case 5: return naf_xna_union_launch_h_k5(p, pl.wt, a->out_dtype, pl.lds, s);
-            case 7: return naf_xna_union_launch_h_k7(p, pl.wt, a->out_dtype, pl.lds, s);
-            case 9: return naf_xna_union_launch_h_k9(p, pl.wt, a->out_dtype, pl.lds, s);
-            case 11: return naf_xna_union_launch_h_k11(p, pl.wt, a->out_dtype, pl.lds, s);
-            case 13: return naf_xna_union_launch_h_k13(p, pl.wt, a->out_dtype, pl.lds, s);
-            case 15: return naf_xna_union_launch_h_k15(p, pl.wt, a->out_dtype, pl.lds, s);
-        }
-    }
+    if (const int rc = xna_union_fill(a, pl, scale, "naf_xna_fwd", p)) return rc;
+    const bool half = a->out_dtype == NAF_F16;   // half values and output: the HALF instances
     switch (a->ky) {
-        case 3: return naf_xna_union_launch_k3(p, pl.wt, a->out_dtype, pl.lds, s);
-        case 5: return naf_xna_union_launch_k5(p, pl.wt, a->out_dtype, pl.lds, s);
-        case 7: return naf_xna_union_launch_k7(p, pl.wt, a->out_dtype, pl.lds, s);
-        case 9: return naf_xna_union_launch_k9(p, pl.wt, a->out_dtype, pl.lds, s);
-        case 11: return naf_xna_union_launch_k11(p, pl.wt, a->out_dtype, pl.lds, s);
-        case 13: return naf_xna_union_launch_k13(p, pl.wt, a->out_dtype, pl.lds, s);
-        case 15: return naf_xna_union_launch_k15(p, pl.wt, a->out_dtype, pl.lds, s);
+#define NAF_X(K) case K: return half ? xna_union_launch_ks<K, true>(p, pl.wt, a->out_dtype, pl.lds, s) : xna_union_launch_ks<K, false>(p, pl.wt, a->out_dtype, pl.lds, s);
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
     }
     naf_set_error("naf_xna_fwd: kernel size %d has no table-driven MFMA instantiation", a->ky);
     return NAF_ERR_UNSUPPORTED;

@@ -419,9 +419,9 @@ static int xna_union_launch_one(const XnaUnionParams& p, size_t lds, hipStream_t
     return naf_check_launch("xna_union_kernel");
 }
 
-// HALF: the NAF_F16 instantiations (xna_union_h_k*.hip)
+// HALF: the NAF_F16 instantiations (objects of their own: xna_union_inst.hip)
 template <int KS, bool HALF = false>
-static int xna_union_launch_ks(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s) {
+int xna_union_launch_ks(const XnaUnionParams& p, int wt, int out_dtype, size_t lds, hipStream_t s) {
     if constexpr (HALF) {
         if (wt == 16) return xna_union_launch_one<KS, f16_t, 16>(p, lds, s);
         return xna_union_launch_one<KS, f16_t, 32>(p, lds, s);
@@ -434,3 +434,15 @@ static int xna_union_launch_ks(const XnaUnionParams& p, int wt, int out_dtype, s
         return xna_union_launch_one<KS, float, 32>(p, lds, s);
     }
 }
+
+// ---- host side (xna_union.hip), shared with the objective's entry (xna_union_mse.hip) ----
+struct UnionPlan {
+    int ok = 0;
+    int wt = 0, ry = 0, seg = 0, hub = 0, wub = 0, dvt = 0;
+    size_t lds = 0;
+};
+// The (cached) plan of a request; ok = 0 when the kernel does not serve the geometry.
+UnionPlan plan_for(const naf_xna_args* a);
+// The kernel's parameters for `a` under its plan, workgroup count included: NAF_OK, or NAF_ERR_INVALID with `who` in the message when the
+// count is out of range.
+int xna_union_fill(const naf_xna_args* a, const UnionPlan& pl, float scale, const char* who, XnaUnionParams& p);

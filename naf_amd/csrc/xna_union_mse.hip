@@ -1,13 +1,14 @@
 // naf_xna_mse_*: the table-driven MFMA attention forward with the training objective (mean squared error against a target) in its
 // epilogue.  The attention launch (xna_union_mse_kernel.h) leaves one fp32 partial sum per wave in the caller's workspace; the
-// one-workgroup kernel below adds them in fp64 in a fixed order.  The workgroup plan is the plain kernel's (naf_xna_union_plan).
+// one-workgroup kernel below adds them in fp64 in a fixed order.  The workgroup plan and the parameters are the plain kernel's (xna_union_fill).
 #include <math.h>
 
 #include "xna_union_mse_kernel.h"
 
-#define NAF_DECL(K) int naf_xna_union_mse_launch_k##K(const XnaUnionMseParams& p, int wt, size_t lds, hipStream_t s);
-NAF_DECL(3) NAF_DECL(5) NAF_DECL(7) NAF_DECL(9) NAF_DECL(11) NAF_DECL(13) NAF_DECL(15)
-#undef NAF_DECL
+// the instances: xna_union_mse_inst.hip, one object per window
+#define NAF_X(K) extern template int xna_union_mse_launch_ks<K>(const XnaUnionMseParams&, int, size_t, hipStream_t);
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
 
 namespace {
 constexpr int FIN_T = 256;
@@ -27,12 +28,10 @@ __global__ __launch_bounds__(FIN_T) void xna_mse_finish_kernel(const float* __re
 }
 
 struct MsePlan {
-    int32_t pl[7];      // naf_xna_union_plan: {wt, ry, seg, hub, wub, dvt, lds}
+    UnionPlan pl;
+    XnaUnionMseParams p;    // the plain kernel's part filled (xna_union_fill); the objective is naf_xna_mse_fwd's
     int nw;
-    int64_t nblocks;
 };
-
-bool aligned_to(const void* p, size_t n) { return (reinterpret_cast<uintptr_t>(p) % n) == 0; }
 
 // the request as the plain union kernel would see it (a stand-in for a NULL gradient buffer: nothing is dereferenced)
 naf_xna_args plain_args(const naf_xna_mse_args* m) {
@@ -55,25 +54,21 @@ int mse_plan(const naf_xna_mse_args* m, MsePlan* out) {
     NAF_REQUIRE(m->a.q && m->a.k_lr && m->a.v_lr && m->target, "naf_xna_mse: NULL tensor pointer");
     NAF_REQUIRE(m->reserved == 0, "naf_xna_mse: reserved must be 0");
     NAF_REQUIRE(m->target_dtype == NAF_BF16 || m->target_dtype == NAF_F32, "naf_xna_mse: target_dtype %d", m->target_dtype);
-    NAF_REQUIRE(aligned_to(m->target, m->target_dtype == NAF_F32 ? 4 : 2), "naf_xna_mse: target is not aligned to its element size");
+    NAF_REQUIRE(naf_aligned(m->target, m->target_dtype == NAF_F32 ? 4 : 2), "naf_xna_mse: target is not aligned to its element size");
     NAF_REQUIRE(m->a.out == nullptr || m->a.out_dtype == NAF_BF16, "naf_xna_mse: the gradient buffer (a.out) must be NAF_BF16, got out_dtype %d", m->a.out_dtype);
     NAF_REQUIRE(m->a.logits == nullptr && m->a.rope_tab_y == nullptr && m->a.rope_tab_x == nullptr,
                 "naf_xna_mse: logits and rotate-on-load (rope_tab_*) are not served by this entry");
-    const naf_xna_args a = plain_args(m);
+    const naf_xna_args a = plain_args(m);   // strides of a stand-in buffer when there is no gradient to store
     const int sel = naf_xna_select(&a);     // argument validation and union eligibility, with naf_last_error set
     if (sel < 0) return -sel;
-    if (sel != NAF_XNA_UNION || !naf_xna_union_plan(&a, out->pl)) {
+    if (sel != NAF_XNA_UNION || !(out->pl = plan_for(&a)).ok) {
         naf_set_error("naf_xna_mse: the table-driven MFMA kernel does not serve these arguments");
         return NAF_ERR_UNSUPPORTED;
     }
-    const int dvt = out->pl[5], ry = out->pl[1], seg = out->pl[2];
-    out->nw = xna_union_mse_waves_rt(a.ky, out->pl[0]);
-    out->nblocks = (int64_t)a.B * a.heads * (a.Dv / dvt) * ((a.Ho + ry - 1) / ry) * ((a.Wo + seg - 1) / seg);
-    if (out->nblocks <= 0 || out->nblocks > 0x7fffffffLL) {
-        naf_set_error("naf_xna_mse: grid of %lld workgroups out of range", (long long)out->nblocks);
-        return NAF_ERR_INVALID;
-    }
-    return NAF_OK;
+    out->nw = xna_union_mse_waves_rt(a.ky, out->pl.wt);
+    const int rc = xna_union_fill(&a, out->pl, xna_scale(a.scale, a.Dq), "naf_xna_mse", out->p);
+    out->p.out = m->a.out;
+    return rc;
 }
 }  // namespace
 
@@ -86,7 +81,7 @@ extern "C" int naf_xna_mse_supported(const naf_xna_mse_args* m) {
 extern "C" size_t naf_xna_mse_workspace_bytes(const naf_xna_mse_args* m) {
     MsePlan pl;
     if (mse_plan(m, &pl) != NAF_OK) return 0;
-    return (size_t)pl.nblocks * pl.nw * sizeof(float);
+    return (size_t)pl.p.nblocks * pl.nw * sizeof(float);
 }
 
 extern "C" int naf_xna_mse_fwd(const naf_xna_mse_args* m, naf_stream_t stream) {
@@ -95,31 +90,13 @@ extern "C" int naf_xna_mse_fwd(const naf_xna_mse_args* m, naf_stream_t stream) {
     if (rc != NAF_OK) return rc;
     const naf_xna_args* a = &m->a;
     NAF_REQUIRE(a->idx_y != nullptr && a->idx_x != nullptr, "naf_xna_mse_fwd: needs idx_y / idx_x from naf_axis_index_table");
-    NAF_REQUIRE(m->loss != nullptr && aligned_to(m->loss, 4), "naf_xna_mse_fwd: loss is NULL or misaligned");
-    const size_t need = (size_t)pl.nblocks * pl.nw * sizeof(float);
-    NAF_REQUIRE(m->workspace != nullptr && aligned_to(m->workspace, 4) && m->workspace_bytes >= need,
+    NAF_REQUIRE(m->loss != nullptr && naf_aligned(m->loss, 4), "naf_xna_mse_fwd: loss is NULL or misaligned");
+    const size_t need = (size_t)pl.p.nblocks * pl.nw * sizeof(float);
+    NAF_REQUIRE(m->workspace != nullptr && naf_aligned(m->workspace, 4) && m->workspace_bytes >= need,
                 "naf_xna_mse_fwd: workspace of %zu bytes given, %zu needed (naf_xna_mse_workspace_bytes)", m->workspace ? m->workspace_bytes : (size_t)0, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
 
-    const naf_xna_args pa = plain_args(m);      // strides of a stand-in buffer when there is no gradient to store
-    XnaUnionMseParams p;
-    p.q = static_cast<const bf16_t*>(a->q);
-    p.k = static_cast<const bf16_t*>(a->k_lr);
-    p.v = static_cast<const bf16_t*>(a->v_lr);
-    p.out = a->out;
-    p.idx_y = a->idx_y;
-    p.idx_x = a->idx_x;
-    p.B = a->B; p.heads = a->heads; p.Ho = a->Ho; p.Wo = a->Wo; p.h = a->h; p.w = a->w;
-    p.dvt = pl.pl[5]; p.nchunk = a->Dv / pl.pl[5];
-    p.ry = pl.pl[1]; p.seg = pl.pl[2];
-    p.nyb = (a->Ho + p.ry - 1) / p.ry;
-    p.nxb = (a->Wo + p.seg - 1) / p.seg;
-    p.hub = pl.pl[3]; p.wub = pl.pl[4];
-    p.nblocks = (uint32_t)pl.nblocks;
-    p.scale_log2e = (a->scale > 0.f ? a->scale : 1.0f / sqrtf((float)a->Dq)) * 1.4426950408889634f;
-    for (int i = 0; i < 4; ++i) {
-        p.qs[i] = a->q_stride[i]; p.ks[i] = a->k_stride[i]; p.vs[i] = a->v_stride[i]; p.os[i] = pa.o_stride[i];
-    }
+    XnaUnionMseParams& p = pl.p;
     const double N = (double)a->B * a->heads * a->Dv * a->Ho * a->Wo;
     XnaUnionObjective& o = p.o;
     o.target = m->target;
@@ -128,24 +105,19 @@ extern "C" int naf_xna_mse_fwd(const naf_xna_mse_args* m, naf_stream_t stream) {
     o.gscale = (float)(2.0 / N);
     o.tdtype = m->target_dtype;
     const int64_t* ts = m->target_stride;
-    o.tvec = ts[1] == 1 && ts[0] % 4 == 0 && ts[2] % 4 == 0 && ts[3] % 4 == 0 && aligned_to(m->target, m->target_dtype == NAF_F32 ? 16 : 8);
+    o.tvec = ts[1] == 1 && ts[0] % 4 == 0 && ts[2] % 4 == 0 && ts[3] % 4 == 0 && naf_aligned(m->target, m->target_dtype == NAF_F32 ? 16 : 8);
     o.grad = a->out != nullptr;
 
     int lrc;
-    const size_t lds = (size_t)pl.pl[6];
     switch (a->ky) {
-        case 3: lrc = naf_xna_union_mse_launch_k3(p, pl.pl[0], lds, s); break;
-        case 5: lrc = naf_xna_union_mse_launch_k5(p, pl.pl[0], lds, s); break;
-        case 7: lrc = naf_xna_union_mse_launch_k7(p, pl.pl[0], lds, s); break;
-        case 9: lrc = naf_xna_union_mse_launch_k9(p, pl.pl[0], lds, s); break;
-        case 11: lrc = naf_xna_union_mse_launch_k11(p, pl.pl[0], lds, s); break;
-        case 13: lrc = naf_xna_union_mse_launch_k13(p, pl.pl[0], lds, s); break;
-        case 15: lrc = naf_xna_union_mse_launch_k15(p, pl.pl[0], lds, s); break;
+#define NAF_X(K) case K: lrc = xna_union_mse_launch_ks<K>(p, pl.pl.wt, pl.pl.lds, s); break;
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
         default:
             naf_set_error("naf_xna_mse_fwd: kernel size %d has no instantiation", a->ky);
             return NAF_ERR_UNSUPPORTED;
     }
     if (lrc != NAF_OK) return lrc;
-    hipLaunchKernelGGL(xna_mse_finish_kernel, dim3(1), dim3(FIN_T), 0, s, static_cast<const float*>(m->workspace), (int64_t)pl.nblocks * pl.nw, 1.0 / N, m->loss);
+    hipLaunchKernelGGL(xna_mse_finish_kernel, dim3(1), dim3(FIN_T), 0, s, static_cast<const float*>(m->workspace), (int64_t)p.nblocks * pl.nw, 1.0 / N, m->loss);
     return naf_check_launch("xna_mse_finish_kernel");
 }

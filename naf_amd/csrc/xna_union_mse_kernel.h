@@ -28,7 +28,7 @@ static int xna_union_mse_launch_one(const XnaUnionMseParams& p, size_t lds, hipS
 }
 
 template <int KS>
-static int xna_union_mse_launch_ks(const XnaUnionMseParams& p, int wt, size_t lds, hipStream_t s) {
+int xna_union_mse_launch_ks(const XnaUnionMseParams& p, int wt, size_t lds, hipStream_t s) {
     if (wt == 16) return xna_union_mse_launch_one<KS, 16>(p, lds, s);
     return xna_union_mse_launch_one<KS, 32>(p, lds, s);
 }
