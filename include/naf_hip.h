@@ -68,7 +68,8 @@ extern "C" {
  * those naf_denoise_objective / naf_denoise_workspace_bytes -- the denoising loss with its gradient, and the PSNR / SSIM metrics (naf_denoise_args); and after
  * those naf_feature_moments (+ _workspace_bytes, _plan) / naf_pca_project (+ _workspace_bytes) / naf_pca_minmax -- feature PCA for display; and after
  * those naf_xna_mse_supported / naf_xna_mse_workspace_bytes / naf_xna_mse_fwd -- the attention forward with the training objective (mean squared error
- * against a target) in its epilogue (naf_xna_mse_args, which embeds naf_xna_args unchanged). */
+ * against a target) in its epilogue (naf_xna_mse_args, which embeds naf_xna_args unchanged); and after those naf_davis_jf_select / naf_davis_jf --
+ * the integer counts behind the DAVIS J and F measures of two label-map sequences (naf_davis_jf_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -1051,6 +1052,45 @@ typedef struct naf_xna_mse_args {
 int naf_xna_mse_supported(const naf_xna_mse_args* a);
 size_t naf_xna_mse_workspace_bytes(const naf_xna_mse_args* a);
 int naf_xna_mse_fwd(const naf_xna_mse_args* a, naf_stream_t stream);
+
+/* ---- DAVIS region similarity J and boundary measure F: the integer counts behind both (added after the objective entries; detect by symbol) ----
+ * Replaces the device-side arithmetic of davis_db_eval_iou / davis_f_measure / _seg2bmap (evaluation/eval_video_seg.py:145-248), which the
+ * reference runs on the host per (object, frame) on float64 one-hot arrays read back from PNG files.  annotation and segmentation are label
+ * maps: 0 is background, 1 .. N are objects, anything above N belongs to no object.  For object o and frame t, with g = (annotation[t] == o)
+ * and s = (segmentation[t] == o), the call ADDS into counts[o - 1][t][0 .. 5]:
+ *   [0] inters    |g and s|                  [1] union     |g or s|
+ *   [2] n_seg     |B(s)|                     [3] n_gt      |B(g)|
+ *   [4] seg_hits  pixels p of B(s) with a pixel q of B(g) at |p - q|^2 <= r2         [5] gt_hits  the converse
+ * B(m), the boundary map of a 0/1 mask, is the 3 x 3 Sobel pair on m with the border rule "reflect without repeating the edge" (row -1 is
+ * row 1, row H is row H - 2; OpenCV's BORDER_REFLECT_101): a pixel is set when either response is non-zero.  Against an empty boundary
+ * there are 0 hits.  J = inters / union and F = 2PR / (P + R), P = seg_hits / (n_seg + 1e-10), R = gt_hits / (n_gt + 1e-10), are the caller's
+ * (fp64).  Squared distances are integers, so `distance <= bound_pix` is `|p - q|^2 <= r2` with r2 = floor(bound_pix^2), exactly.
+ *   annotation, segmentation   device uint8, dense [T][H][W]
+ *   counts                     device int64 [N][T][6], ZEROED by the caller on the same stream before the call
+ *   r2, half_width             floor(bound_pix^2) and floor(bound_pix): half_width^2 <= r2 < (half_width + 1)^2 (NAF_ERR_INVALID otherwise)
+ * One launch for the sequence; a workgroup owns one NAF_DAVIS_TILE_H x NAF_DAVIS_TILE_W tile of one frame, stages both maps' tile with its halo
+ * once, and for every label present in the tile packs the two boundary maps into 64-bit words and tests each boundary pixel's disk row by
+ * row.  Counters are reduced per wave and per workgroup; a workgroup adds at most one 64-bit integer atomic per (object, counter).  Integer
+ * adds: two runs give the same bits.
+ * Served: 1 <= N <= 32, 2 <= H, W <= 16384, T >= 1, 1 <= half_width <= 32, tiles * T below 2^31; anything else that is well formed is
+ * NAF_ERR_UNSUPPORTED with the limit named in naf_last_error().  naf_davis_jf_select is a host-only query (it reads the scalar fields only
+ * and touches no device): NAF_OK, NAF_ERR_UNSUPPORTED or NAF_ERR_INVALID (NULL args, N, T, H or W < 1, half_width < 0, r2 and half_width
+ * that do not belong together, non-zero reserved).  naf_davis_jf additionally refuses NULL pointers and counts not 8-byte aligned.
+ * Caller-owned memory and stream; nothing is allocated; capturable. */
+#define NAF_DAVIS_TILE_W 64
+#define NAF_DAVIS_TILE_H 32
+#define NAF_DAVIS_MAX_OBJECTS 32
+#define NAF_DAVIS_MAX_HALF_WIDTH 32
+typedef struct naf_davis_jf_args {
+    const uint8_t* annotation;
+    const uint8_t* segmentation;
+    int64_t* counts;
+    int32_t T, H, W, N;
+    int32_t r2, half_width;
+    int32_t reserved[2]; /* must be 0 */
+} naf_davis_jf_args;
+int naf_davis_jf_select(const naf_davis_jf_args* a);
+int naf_davis_jf(const naf_davis_jf_args* a, naf_stream_t stream);
 
 #ifdef __cplusplus
 }

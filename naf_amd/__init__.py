@@ -11,9 +11,10 @@ Kernels live in naf_amd/csrc (HIP, C ABI in include/naf_hip.h); build with ``pyt
 from .model import NAF, CrossAttention, GraphedForward, ImageEncoder, RoPE  # noqa: F401
 from .ops import ConfusionMetrics, FrameFeatures, confusion_metrics, pack_frame, propagate_labels  # noqa: F401
 from .ops import DenoisingLoss, denoising_loss, denoising_metrics  # noqa: F401
+from .ops import DavisJF, davis_jf, davis_statistics  # noqa: F401
 from .feature_pca import FeaturePCA, pca  # noqa: F401
 
 __all__ = ["NAF", "CrossAttention", "GraphedForward", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics",
            "FrameFeatures", "pack_frame", "propagate_labels", "DenoisingLoss", "denoising_loss", "denoising_metrics",
-           "FeaturePCA", "pca"]
+           "FeaturePCA", "pca", "DavisJF", "davis_jf", "davis_statistics"]
 __version__ = "0.1.0"

@@ -96,6 +96,19 @@ class PropagateArgs(C.Structure):
     ]
 
 
+DAVIS_TILE_W, DAVIS_TILE_H = 64, 32             # NAF_DAVIS_TILE_W / _H: the tile one workgroup of naf_davis_jf owns
+DAVIS_MAX_OBJECTS, DAVIS_MAX_HALF_WIDTH = 32, 32
+
+
+class DavisJFArgs(C.Structure):
+    """naf_davis_jf_args (added after the objective entries, detected by symbol): the counts behind the DAVIS J and F measures."""
+    _fields_ = [
+        ("annotation", C.c_void_p), ("segmentation", C.c_void_p), ("counts", C.c_void_p),
+        ("T", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("N", C.c_int32), ("r2", C.c_int32), ("half_width", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
 DENOISE_LOSS, DENOISE_METRICS = 0, 1            # naf_denoise_mode
 
 
@@ -327,6 +340,8 @@ SIGNATURES = {
     "naf_xna_mse_supported": (C.c_int, [C.POINTER(XnaMSEArgs)]),
     "naf_xna_mse_workspace_bytes": (C.c_size_t, [C.POINTER(XnaMSEArgs)]),
     "naf_xna_mse_fwd": (C.c_int, [C.POINTER(XnaMSEArgs), C.c_void_p]),
+    "naf_davis_jf_select": (C.c_int, [C.POINTER(DavisJFArgs)]),
+    "naf_davis_jf": (C.c_int, [C.POINTER(DavisJFArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -11,6 +11,7 @@ Reference counterparts (paths relative to the reference repo):
   xna_forward        legacy_attention / na2d                            src/layers/attentions.py:16-29,72
   xna_head_forward   the same with the probe's 1x1 convolution folded in  evaluation/eval_seg_probing.py:56,104-111
   propagate_labels   label_propagation after feature extraction          evaluation/eval_video_seg.py:499-561
+  davis_jf / davis_statistics  davis_db_eval_iou, davis_db_eval_boundary, davis_db_statistics  evaluation/eval_video_seg.py:145-269
   denoising_loss     DenoisingLoss.forward and its backward               denoising.py:129-177
   denoising_metrics  MetricsCalculator.calculate_batch_metrics            denoising.py:61-126,302
   feature_moments / pca_project / pca_minmax  pca() and TorchPCA          utils/visualization.py:135-190
@@ -20,6 +21,7 @@ from __future__ import annotations
 import collections
 import contextlib
 import ctypes as C
+import math
 import threading
 from typing import Dict, Optional, Tuple
 
@@ -1893,6 +1895,145 @@ def propagate_labels(target, context, segs, radius: int = 12, topk: int = 5, tem
         rc = lib.naf_propagate_fwd(C.byref(a), _stream(out))
     _lib.check(rc, "naf_propagate_fwd")
     return out
+
+
+# ---- DAVIS J and F measures (evaluation/eval_video_seg.py:145-269) --------------------------------------------------------------------
+DavisJF = collections.namedtuple("DavisJF", ("J", "F", "counts"))
+
+
+def _davis_bound(bound_th, H: int, W: int, who: str):
+    """(r2, half_width) = (floor(bound_pix^2), floor(bound_pix)) with bound_pix as eval_video_seg.py:183 forms it; host only."""
+    try:
+        th = float(bound_th)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"naf_amd.{who}: bound_th must be a number: {e}") from e
+    if not math.isfinite(th):
+        raise ValueError(f"naf_amd.{who}: bound_th must be finite, got {th}")
+    bound_pix = th if th >= 1 else float(math.ceil(th * math.sqrt(float(H * H + W * W))))
+    half = int(math.floor(min(max(bound_pix, -1.0), 40000.0)))
+    if half < 0 or half > _lib.DAVIS_MAX_HALF_WIDTH:          # not served: the library words the refusal; r2 stays inside int32
+        return (0, -1) if half < 0 else (half * half, half)
+    return int(math.floor(bound_pix * bound_pix)), half
+
+
+def davis_jf(annotation: torch.Tensor, segmentation: torch.Tensor, num_objects: Optional[int] = None, bound_th: float = 0.008) -> "DavisJF":
+    """The DAVIS region similarity J and boundary measure F of every (object, frame) of two label-map sequences, in one kernel launch: the
+    reference's ``davis_db_eval_iou`` and ``davis_db_eval_boundary`` (evaluation/eval_video_seg.py:145-248) without PNG files, one-hot
+    float64 arrays or per-frame distance transforms on the host.
+
+    ``annotation`` and ``segmentation`` are ``[T, H, W]`` (or ``[H, W]``: one frame) label maps on one ROCm device, ``torch.uint8`` (read as
+    they are; a view that is not dense is copied once) or ``torch.int64`` (converted once on the device).  Label 0 is background, labels
+    ``1 .. N`` are objects.  Returns ``DavisJF(J, F, counts)``: ``J`` and ``F`` float64 ``[N, T]``, ``counts`` int64 ``[N, T, 6]`` holding
+    ``inters, union, n_seg, n_gt, seg_hits, gt_hits``; all on the inputs' device, detached.  With ``g = (annotation[t] == o)`` and
+    ``s = (segmentation[t] == o)``:
+
+        J = inters / union = |g & s| / |g | s|, and 1 where the union is empty
+        the boundary map of a mask is where its 3 x 3 Sobel pair is non-zero, the border reflected without repeating the edge
+        n_seg, n_gt   boundary pixels of s and of g;   seg_hits   boundary pixels of s with a boundary pixel of g within bound_pix (gt_hits: the converse)
+        P = seg_hits / (n_seg + 1e-10), R = gt_hits / (n_gt + 1e-10), F = 2 P R / (P + R), and 0 where P + R == 0
+        bound_pix = bound_th if bound_th >= 1 else ceil(bound_th * sqrt(H^2 + W^2))        (8 at 480 x 854 with the default)
+
+    Against an EMPTY boundary the hit counts are 0 here.  The reference's distance transform of a map without a boundary pixel returns
+    arbitrary small distances there and so counts spurious hits, but that count is then multiplied by the other side's ``0 / 1e-10``: ``F`` is
+    identical to the reference's in every case, only the raw ``seg_hits`` / ``gt_hits`` of those cases differ.
+
+    ``num_objects=None`` takes N = ``annotation.max()`` -- ONE host synchronisation -- and raises ``ValueError`` when ``segmentation`` holds a
+    higher label (the reference skips such a sequence: "an index higher than the number of objects", eval_video_seg.py:282-284) or when
+    ``annotation`` has no object.  With ``num_objects=N`` nothing synchronises: labels above N in either map belong to no object, and an
+    object missing from ``segmentation`` has an empty mask there (the reference's zero padding, eval_video_seg.py:285-287).  There are no
+    void pixels (the reference passes none, :322); dropping the first and last frame (:318) is the caller's slice.
+
+    Served: 1 <= N <= 32, H, W >= 2, T >= 1, 1 <= floor(bound_pix) <= 32.  Anything else raises ``ValueError``; there is no torch fallback."""
+    who = "davis_jf"
+    for name, t in (("annotation", annotation), ("segmentation", segmentation)):
+        if not torch.is_tensor(t):
+            raise ValueError(f"naf_amd.{who}: `{name}` must be a tensor, got {type(t).__name__}")
+        if t.dtype not in (torch.uint8, torch.int64):
+            raise ValueError(f"naf_amd.{who}: `{name}` must be a torch.uint8 or torch.int64 label map, got {t.dtype}")
+        if t.dim() not in (2, 3):
+            raise ValueError(f"naf_amd.{who}: `{name}` must be [T, H, W] or [H, W], got {tuple(t.shape)}")
+    if tuple(annotation.shape) != tuple(segmentation.shape):
+        raise ValueError(f"naf_amd.{who}: annotation {tuple(annotation.shape)} and segmentation {tuple(segmentation.shape)} must have one shape")
+    T, H, W = (1, *annotation.shape) if annotation.dim() == 2 else annotation.shape
+    T, H, W = int(T), int(H), int(W)
+    if num_objects is not None and (isinstance(num_objects, bool) or not isinstance(num_objects, int)):
+        raise ValueError(f"naf_amd.{who}: num_objects must be an int or None, got {num_objects!r}")
+    if num_objects is not None and not -(1 << 31) <= num_objects < (1 << 31):
+        raise ValueError(f"naf_amd.{who}: num_objects = {num_objects} is not served: 1 <= N <= {_lib.DAVIS_MAX_OBJECTS}")
+    a = _lib.DavisJFArgs()
+    a.T, a.H, a.W = T, H, W
+    a.r2, a.half_width = _davis_bound(bound_th, H, W, who)
+    a.N = 1 if num_objects is None else num_objects
+    lib = _lib.load()
+    if lib.naf_davis_jf_select(C.byref(a)) != 0:               # host only: the limits live in one place, the library
+        raise ValueError(f"naf_amd.{who}: {_lib.last_error()}")
+
+    _gpu(annotation, "annotation")
+    _gpu(segmentation, "segmentation")
+    dev = annotation.device
+    if segmentation.device != dev:
+        raise ValueError(f"naf_amd.{who}: annotation and segmentation must live on one device")
+    with torch.cuda.device(dev):
+        maps = []
+        for t in (annotation, segmentation):
+            x = t.detach()
+            x = x[None] if x.dim() == 2 else x
+            if x.dtype != torch.uint8:
+                x = x.clamp(0, 255).to(torch.uint8)            # above N (<= 32) is "no object" either way
+            maps.append(x if x.is_contiguous() else x.contiguous())
+        if num_objects is None:
+            top = torch.stack([annotation.max(), segmentation.max()]).tolist()      # the one synchronisation
+            if top[0] < 1:
+                raise ValueError(f"naf_amd.{who}: annotation holds no object (its largest label is {top[0]})")
+            if top[1] > top[0]:
+                raise ValueError(f"naf_amd.{who}: segmentation holds label {top[1]}, an index higher than the number of objects in the "
+                                 f"annotation ({top[0]}); the reference skips such a sequence (eval_video_seg.py:282-284)")
+            a.N = int(min(top[0], (1 << 31) - 1))
+            if lib.naf_davis_jf_select(C.byref(a)) != 0:
+                raise ValueError(f"naf_amd.{who}: {_lib.last_error()}")
+        N = int(a.N)
+        counts = torch.zeros((N, T, 6), dtype=torch.int64, device=dev)
+        a.annotation, a.segmentation, a.counts = maps[0].data_ptr(), maps[1].data_ptr(), counts.data_ptr()
+        with _Timed("davis_jf"):
+            rc = lib.naf_davis_jf(C.byref(a), _stream(counts))
+        _lib.check(rc, "naf_davis_jf")
+        c = counts.to(torch.float64)
+        inters, union, n_seg, n_gt, seg_hits, gt_hits = c.unbind(-1)
+        one, zero = torch.ones_like(union), torch.zeros_like(union)
+        J = torch.where(union == 0, one, inters / torch.where(union == 0, one, union))
+        P, Rc = seg_hits / (n_seg + 1e-10), gt_hits / (n_gt + 1e-10)
+        den = P + Rc
+        F = torch.where(den == 0, zero, 2 * P * Rc / torch.where(den == 0, one, den))
+    return DavisJF(J, F, counts)
+
+
+def davis_statistics(per_frame_values: torch.Tensor):
+    """Mean, recall and decay of per-frame values, the reference's ``davis_db_statistics`` (evaluation/eval_video_seg.py:251-269), for
+    every object at once: ``per_frame_values`` is ``[N, T]`` (or ``[T]``), e.g. ``davis_jf(...).J``.  Returns ``(mean, recall, decay)``, each
+    float64 ``[N]`` (0-dim for a ``[T]`` input) on the input's device -- plain torch operations, no kernel, no synchronisation:
+
+        mean = nanmean(v),   recall = mean(v > 0.5),   decay = nanmean(first bin) - nanmean(fourth bin)
+
+    with the four bins ``v[ids[i] : ids[i + 1] + 1]``, ``ids = round(linspace(1, T, 5) + 1e-10) - 1`` -- the reference's edges, overlapping
+    by one frame as they do there (T = 68: 0, 17, 34, 50, 67).  The reference casts the edges to uint8, which wraps beyond 256 frames:
+    ``T > 256`` raises ``ValueError`` instead."""
+    who = "davis_statistics"
+    v = per_frame_values
+    if not torch.is_tensor(v) or v.dim() not in (1, 2) or not v.is_floating_point():
+        raise ValueError(f"naf_amd.{who}: a floating-point [N, T] or [T] tensor is expected, got "
+                         f"{getattr(v, 'dtype', type(v).__name__)} {tuple(getattr(v, 'shape', ()))}")
+    T = int(v.shape[-1])
+    if T < 1:
+        raise ValueError(f"naf_amd.{who}: no frames (T = 0)")
+    if T > 256:
+        raise ValueError(f"naf_amd.{who}: T = {T} frames; the reference's uint8 bin edges wrap beyond 256 frames, so T <= 256 is served")
+    v = v.detach().to(torch.float64)
+    step = (T - 1) / 4
+    ids = [int(round(x + 1e-10)) - 1 for x in [1 + i * step for i in range(4)] + [float(T)]]
+    mean = torch.nanmean(v, dim=-1)
+    recall = (v > 0.5).to(torch.float64).mean(dim=-1)
+    decay = torch.nanmean(v[..., ids[0]:ids[1] + 1], dim=-1) - torch.nanmean(v[..., ids[3]:ids[4] + 1], dim=-1)
+    return mean, recall, decay
 
 
 # ---- denoising objective (denoising.py:61-177) ------------------------------------------------------------------------------------
