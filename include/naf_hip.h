@@ -69,7 +69,8 @@ extern "C" {
  * those naf_feature_moments (+ _workspace_bytes, _plan) / naf_pca_project (+ _workspace_bytes) / naf_pca_minmax -- feature PCA for display; and after
  * those naf_xna_mse_supported / naf_xna_mse_workspace_bytes / naf_xna_mse_fwd -- the attention forward with the training objective (mean squared error
  * against a target) in its epilogue (naf_xna_mse_args, which embeds naf_xna_args unchanged); and after those naf_davis_jf_select / naf_davis_jf --
- * the integer counts behind the DAVIS J and F measures of two label-map sequences (naf_davis_jf_args). */
+ * the integer counts behind the DAVIS J and F measures of two label-map sequences (naf_davis_jf_args); and after those naf_mask_labels_select /
+ * naf_mask_labels / naf_nearest_resize_table -- a propagated frame's soft masks to the label map the reference writes to disk (naf_mask_labels_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -1091,6 +1092,53 @@ typedef struct naf_davis_jf_args {
 } naf_davis_jf_args;
 int naf_davis_jf_select(const naf_davis_jf_args* a);
 int naf_davis_jf(const naf_davis_jf_args* a, naf_stream_t stream);
+
+/* ---- soft masks to a label map: upsample, norm_mask, argmax, nearest resize (added after the DAVIS entries; detect by symbol) ----
+ * Replaces what the reference does with a propagated frame before it scores it (evaluation/eval_video_seg.py:444-457): F.interpolate
+ * (bilinear, align_corners = False) of the K soft masks [h, w] to the mid grid [mid_h, mid_w], norm_mask per channel, torch.max over the
+ * channels, .cpu() and Image.resize((out_w, out_h), 0).  With u[c] the upsampled channel (ATen's fp32 arithmetic, every operation rounded on
+ * its own: scale = float(in) / float(out), src = max(scale * (dst + 0.5f) - 0.5f, 0), i0 = (int)src, i1 = i0 + (i0 < in - 1), l1 = src - i0,
+ * l0 = 1 - l1, value = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11)) and mx, mn its maximum and minimum over the mid grid:
+ *   n[c] = (u[c] - mn) / (mx - mn) where mx > 0 (subtract, then a correctly rounded divide), u[c] where not;
+ *   mx > 0 with mx == mn divides 0 by 0: the channel is NaN everywhere, as in the reference;
+ *   label = the first channel holding the maximum of n, a NaN counting above every number (torch.max on the CPU);
+ *   out[oy][ox] = label at mid pixel (tab_y[oy], tab_x[ox]).  NaN inputs are unspecified.
+ *   seg          device fp32, K channels of h x w; seg_stride = elements between channels, rows, columns (any values, 0 and negative included)
+ *   tab_y, tab_x device int32 [out_h], [out_w]: the mid row / column each output row / column reads; naf_nearest_resize_table(mid, out) for
+ *                Pillow's nearest resize.  Entries are clamped to the mid grid
+ *   out          device uint8, out_h rows of out_w bytes, out_stride (>= out_w) bytes between rows; nothing else is written
+ *   workspace    device, 4-byte aligned, at least NAF_MASK_LABELS_WORKSPACE_BYTES; need not be initialised
+ * Two launches on the caller's stream: pass 1 evaluates u at every mid pixel and leaves one (min, max) pair per workgroup and channel in the
+ * workspace; pass 2 finishes the pairs, evaluates the K values at each OUTPUT pixel's source, normalises and stores the label.  Both passes
+ * get u from one inline function, so the extreme pixels normalise to exactly 1 and 0; no atomics, no float order that depends on scheduling:
+ * two runs give the same bits.  The [K, mid_h, mid_w] map is never written.
+ * Served: 1 <= K <= NAF_MASK_LABELS_MAX_CHANNELS, every size 1 .. NAF_MASK_LABELS_MAX_SIZE; anything else that is well formed is
+ * NAF_ERR_UNSUPPORTED with the limit named in naf_last_error().  naf_mask_labels_select is a host-only query (it reads the scalar fields only
+ * and touches no device): NAF_OK, NAF_ERR_UNSUPPORTED or NAF_ERR_INVALID (NULL args, K or a size < 1, non-zero reserved).  naf_mask_labels
+ * additionally refuses NULL or misaligned pointers, a workspace that is too small and out_stride < out_w.
+ * Caller-owned memory and stream; nothing is allocated; capturable.
+ *
+ * naf_nearest_resize_table (host only) writes the n_out source indices Pillow's Image.resize(size, 0) reads along an axis of n_in pixels:
+ * with s = (double)n_in / n_out, xo = 0.5 * s; out[x] = min((int)xo, n_in - 1); xo += s.  The ACCUMULATION in doubles is the definition:
+ * floor((2x + 1) n_in / (2 n_out)) differs from it (at 64 of the 854 columns of 976 -> 854). */
+#define NAF_MASK_LABELS_MAX_CHANNELS 64
+#define NAF_MASK_LABELS_MAX_SIZE 16384
+#define NAF_MASK_LABELS_WORKSPACE_BYTES 8192
+typedef struct naf_mask_labels_args {
+    const float* seg;
+    const int32_t* tab_y;
+    const int32_t* tab_x;
+    uint8_t* out;
+    float* workspace;
+    size_t workspace_bytes;
+    int64_t seg_stride[3];
+    int64_t out_stride;
+    int32_t K, h, w, mid_h, mid_w, out_h, out_w;
+    int32_t reserved; /* must be 0 */
+} naf_mask_labels_args;
+int naf_mask_labels_select(const naf_mask_labels_args* a);
+int naf_mask_labels(const naf_mask_labels_args* a, naf_stream_t stream);
+int naf_nearest_resize_table(int32_t* out, int32_t n_in, int32_t n_out);
 
 #ifdef __cplusplus
 }

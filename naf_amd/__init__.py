@@ -12,9 +12,11 @@ from .model import NAF, CrossAttention, GraphedForward, ImageEncoder, RoPE  # no
 from .ops import ConfusionMetrics, FrameFeatures, confusion_metrics, pack_frame, propagate_labels  # noqa: F401
 from .ops import DenoisingLoss, denoising_loss, denoising_metrics  # noqa: F401
 from .ops import DavisJF, davis_jf, davis_statistics  # noqa: F401
+from .ops import VideoTracker, labels_to_masks, masks_to_labels, nearest_index_table  # noqa: F401
 from .feature_pca import FeaturePCA, pca  # noqa: F401
 
 __all__ = ["NAF", "CrossAttention", "GraphedForward", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics",
            "FrameFeatures", "pack_frame", "propagate_labels", "DenoisingLoss", "denoising_loss", "denoising_metrics",
-           "FeaturePCA", "pca", "DavisJF", "davis_jf", "davis_statistics"]
+           "FeaturePCA", "pca", "DavisJF", "davis_jf", "davis_statistics",
+           "VideoTracker", "labels_to_masks", "masks_to_labels", "nearest_index_table"]
 __version__ = "0.1.0"

@@ -109,6 +109,19 @@ class DavisJFArgs(C.Structure):
     ]
 
 
+MASK_LABELS_MAX_CHANNELS, MASK_LABELS_MAX_SIZE, MASK_LABELS_WORKSPACE_BYTES = 64, 16384, 8192     # NAF_MASK_LABELS_*
+
+
+class MaskLabelsArgs(C.Structure):
+    """naf_mask_labels_args (added after the DAVIS entries, detected by symbol): a propagated frame's soft masks to its label map."""
+    _fields_ = [
+        ("seg", C.c_void_p), ("tab_y", C.c_void_p), ("tab_x", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p),
+        ("workspace_bytes", C.c_size_t), ("seg_stride", I64x3), ("out_stride", C.c_int64),
+        ("K", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("mid_h", C.c_int32), ("mid_w", C.c_int32), ("out_h", C.c_int32),
+        ("out_w", C.c_int32), ("reserved", C.c_int32),
+    ]
+
+
 DENOISE_LOSS, DENOISE_METRICS = 0, 1            # naf_denoise_mode
 
 
@@ -342,6 +355,9 @@ SIGNATURES = {
     "naf_xna_mse_fwd": (C.c_int, [C.POINTER(XnaMSEArgs), C.c_void_p]),
     "naf_davis_jf_select": (C.c_int, [C.POINTER(DavisJFArgs)]),
     "naf_davis_jf": (C.c_int, [C.POINTER(DavisJFArgs), C.c_void_p]),
+    "naf_mask_labels_select": (C.c_int, [C.POINTER(MaskLabelsArgs)]),
+    "naf_mask_labels": (C.c_int, [C.POINTER(MaskLabelsArgs), C.c_void_p]),
+    "naf_nearest_resize_table": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

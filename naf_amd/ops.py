@@ -12,6 +12,8 @@ Reference counterparts (paths relative to the reference repo):
   xna_head_forward   the same with the probe's 1x1 convolution folded in  evaluation/eval_seg_probing.py:56,104-111
   propagate_labels   label_propagation after feature extraction          evaluation/eval_video_seg.py:499-561
   davis_jf / davis_statistics  davis_db_eval_iou, davis_db_eval_boundary, davis_db_statistics  evaluation/eval_video_seg.py:145-269
+  masks_to_labels / labels_to_masks / VideoTracker  the upsample, norm_mask, argmax and PIL resize of a propagated frame; read_seg + to_one_hot;
+                     the queue of eval_video_tracking_davis                 evaluation/eval_video_seg.py:389-457,488-496,611-643
   denoising_loss     DenoisingLoss.forward and its backward               denoising.py:129-177
   denoising_metrics  MetricsCalculator.calculate_batch_metrics            denoising.py:61-126,302
   feature_moments / pca_project / pca_minmax  pca() and TorchPCA          utils/visualization.py:135-190
@@ -2034,6 +2036,201 @@ def davis_statistics(per_frame_values: torch.Tensor):
     recall = (v > 0.5).to(torch.float64).mean(dim=-1)
     decay = torch.nanmean(v[..., ids[0]:ids[1] + 1], dim=-1) - torch.nanmean(v[..., ids[3]:ids[4] + 1], dim=-1)
     return mean, recall, decay
+
+
+# ---- a propagated frame's label map, and the tracker around it (evaluation/eval_video_seg.py:389-457, 611-643) ---------------------------
+def nearest_index_table(n_in: int, n_out: int) -> torch.Tensor:
+    """[n_out] int32 CPU tensor: the source index Pillow's ``Image.resize(size, 0)`` (nearest) reads for every output index along an axis
+    of ``n_in`` pixels resized to ``n_out`` (host function of the library, no GPU and no Pillow needed).  With ``s = n_in / n_out`` in
+    doubles: ``xo = 0.5 * s``; ``idx[x] = min(int(xo), n_in - 1)``; ``xo += s``.  The accumulation is the definition: the closed form
+    ``floor((2x + 1) n_in / (2 n_out))`` differs from it, and so does ``F.interpolate(mode="nearest")``, which reads ``floor(x * s)``."""
+    for name, v in (("n_in", n_in), ("n_out", n_out)):
+        if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v < (1 << 31):
+            raise ValueError(f"naf_amd.nearest_index_table: {name} must be an int of at least 1, got {v!r}")
+    out = torch.empty((n_out,), dtype=torch.int32)
+    rc = _lib.load().naf_nearest_resize_table(C.cast(out.data_ptr(), C.POINTER(C.c_int32)), n_in, n_out)
+    _lib.check(rc, "naf_nearest_resize_table")
+    return out
+
+
+_nearest_cache = {}
+
+
+def device_nearest_table(n_in: int, n_out: int, device) -> torch.Tensor:
+    key = (int(n_in), int(n_out), str(device))
+    t = _nearest_cache.get(key)
+    if t is None:
+        if len(_nearest_cache) > 64:
+            _nearest_cache.clear()
+        t = nearest_index_table(int(n_in), int(n_out)).to(device)
+        _nearest_cache[key] = t
+    return t
+
+
+def _size2(size, who: str, name: str) -> Tuple[int, int]:
+    try:
+        a, b = size
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"naf_amd.{who}: `{name}` must be a pair (rows, columns), got {size!r}") from e
+    for v in (a, b):
+        if isinstance(v, bool) or not isinstance(v, int) or not -(1 << 31) <= v < (1 << 31):
+            raise ValueError(f"naf_amd.{who}: `{name}` must be a pair of ints, got {size!r}")
+    return a, b
+
+
+def masks_to_labels(seg: torch.Tensor, mid_size, out_size, *, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The label map the reference writes to disk for a propagated frame (evaluation/eval_video_seg.py:444-457), from the soft masks
+    ``propagate_labels`` returns, in two kernel launches and without a host synchronisation.
+
+    ``seg`` is ``[1, K, h, w]`` or ``[K, h, w]`` fp32 on a ROCm device, any strides (it is read as it is).  Returns ``torch.uint8``
+    ``[out_h, out_w]`` on that device.  Line for line:
+
+        u = F.interpolate(seg, size=mid_size, mode="bilinear", align_corners=False)     ATen's fp32 arithmetic, never written to memory
+        norm_mask: per channel, with mx / mn over the mid grid: (u - mn) / (mx - mn) where mx > 0, unchanged where not;
+                   mx > 0 and mx == mn is 0 / 0, the channel is NaN everywhere -- as in the reference
+        label = torch.max(u, dim=0) indices: the first maximum, a NaN above every number (the CPU's rule)
+        Image.resize((out_w, out_h), 0): output pixel (y, x) reads mid pixel (ty[y], tx[x]), ty / tx = nearest_index_table(mid, out)
+
+    In the reference ``mid_size = (h * ps // ups_factor, w * ps // ups_factor)`` and ``out_size`` is the frame's own size.  ``out=`` is a
+    ``torch.uint8`` view ``[out_h, out_w]`` on the same device whose columns are adjacent (``stride(1) == 1``, any row stride of at
+    least ``out_w``), e.g. row ``t`` of a ``[T, H, W]`` sequence buffer for ``davis_jf``: it is written in place and returned, nothing outside
+    it is touched.  NaN inputs are unspecified.
+
+    Served: 1 <= K <= 64, every size 1 .. 16384.  Anything else raises ``ValueError``; there is no torch fallback."""
+    who = "masks_to_labels"
+    if not torch.is_tensor(seg):
+        raise ValueError(f"naf_amd.{who}: `seg` must be a tensor, got {type(seg).__name__}")
+    if seg.dim() == 4 and seg.shape[0] == 1:
+        s3 = seg[0]
+    elif seg.dim() == 3:
+        s3 = seg
+    else:
+        raise ValueError(f"naf_amd.{who}: `seg` must be [1, K, h, w] or [K, h, w], got {tuple(seg.shape)}")
+    if seg.dtype != torch.float32:
+        raise ValueError(f"naf_amd.{who}: `seg` must be float32 soft masks (what propagate_labels returns), got {seg.dtype}")
+    (mh, mw), (oh, ow) = _size2(mid_size, who, "mid_size"), _size2(out_size, who, "out_size")
+    a = _lib.MaskLabelsArgs()
+    a.K, a.h, a.w = (int(v) for v in s3.shape)
+    a.mid_h, a.mid_w, a.out_h, a.out_w = mh, mw, oh, ow
+    lib = _lib.load()
+    if lib.naf_mask_labels_select(C.byref(a)) != 0:            # host only: the limits live in one place, the library
+        raise ValueError(f"naf_amd.{who}: {_lib.last_error()}")
+    _gpu(seg, "seg")
+    dev = seg.device
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != (oh, ow):
+            raise ValueError(f"naf_amd.{who}: `out` must be a torch.uint8 tensor of shape {(oh, ow)}, got "
+                             f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
+        if out.device != dev:
+            raise ValueError(f"naf_amd.{who}: `out` is on {out.device}, `seg` on {dev}")
+        if (ow > 1 and out.stride(1) != 1) or (oh > 1 and out.stride(0) < ow):
+            raise ValueError(f"naf_amd.{who}: `out` must have adjacent columns and rows that do not overlap, got strides {tuple(out.stride())}")
+    with torch.cuda.device(dev):
+        s3 = s3.detach()
+        res = out if out is not None else torch.empty((oh, ow), dtype=torch.uint8, device=dev)
+        ty, tx = device_nearest_table(mh, oh, dev), device_nearest_table(mw, ow, dev)
+        ws = torch.empty((_lib.MASK_LABELS_WORKSPACE_BYTES // 4,), dtype=torch.float32, device=dev)
+        a.seg, a.tab_y, a.tab_x, a.out, a.workspace = s3.data_ptr(), ty.data_ptr(), tx.data_ptr(), res.data_ptr(), ws.data_ptr()
+        a.workspace_bytes = _lib.MASK_LABELS_WORKSPACE_BYTES
+        a.seg_stride = _strides3(s3)
+        a.out_stride = int(res.stride(0)) if oh > 1 else ow
+        with _Timed("mask_labels"):
+            rc = lib.naf_mask_labels(C.byref(a), _stream(res))
+        _lib.check(rc, "naf_mask_labels")
+    return res
+
+
+def labels_to_masks(labels: torch.Tensor, size, num_classes: Optional[int] = None) -> torch.Tensor:
+    """The first frame's one-hot masks: the reference's ``read_seg`` + ``to_one_hot`` (evaluation/eval_video_seg.py:638-643, 611-623).
+    ``labels`` is a ``[H, W]`` ``torch.uint8`` or ``torch.int64`` label map on the device; it is resized to ``size = (h, w)`` as Pillow's
+    nearest resize reads it (``nearest_index_table``) and expanded to fp32 ``[1, K, h, w]``.  ``num_classes=None`` takes
+    ``K = labels.max() + 1`` -- ONE host synchronisation, as in the reference; with ``num_classes=K`` nothing synchronises and a label outside
+    ``0 .. K - 1`` belongs to no channel.  (The reference takes the maximum AFTER the resize; an object the resize drops is an all-zero
+    channel here, which wins nowhere: ties go to a lower channel.)  Plain torch indexing on the labels' device; no kernel."""
+    who = "labels_to_masks"
+    if not torch.is_tensor(labels) or labels.dim() != 2 or labels.dtype not in (torch.uint8, torch.int64):
+        raise ValueError(f"naf_amd.{who}: `labels` must be a [H, W] torch.uint8 or torch.int64 label map, got "
+                         f"{getattr(labels, 'dtype', type(labels).__name__)} {tuple(getattr(labels, 'shape', ()))}")
+    h, w = _size2(size, who, "size")
+    H, W = (int(v) for v in labels.shape)
+    if min(h, w, H, W) < 1:
+        raise ValueError(f"naf_amd.{who}: sizes must be at least 1, got {H} x {W} -> {h} x {w}")
+    if num_classes is not None and (isinstance(num_classes, bool) or not isinstance(num_classes, int) or num_classes < 1):
+        raise ValueError(f"naf_amd.{who}: num_classes must be a positive int or None, got {num_classes!r}")
+    dev = labels.device
+    ty, tx = device_nearest_table(H, h, dev).long(), device_nearest_table(W, w, dev).long()
+    small = labels.detach()[ty][:, tx].long()
+    K = int(labels.max()) + 1 if num_classes is None else num_classes        # None: the one synchronisation (to_one_hot, :617)
+    if K < 1:
+        raise ValueError(f"naf_amd.{who}: labels.max() = {K - 1}: no class")
+    return (small[None] == torch.arange(K, device=dev)[:, None, None]).to(torch.float32)[None]
+
+
+class VideoTracker:
+    """The per-sequence loop of the reference's ``eval_video_tracking_davis`` (evaluation/eval_video_seg.py:389-441) on the device.
+
+        trk = VideoTracker(first_feats, first_labels, ps=16, ups_factor=8, n_last_frames=7, radius=12, topk=5, temperature=0.1)
+        pred[t] = trk.step(feats_t)               # or trk.step(feats_t, out=pred[t]): uint8 [H0, W0] on the device
+
+    ``first_feats`` and every ``feats_t`` are what ``naf(...)`` returns (``[C, h, w]`` / ``[1, C, h, w]``) or ``FrameFeatures``;
+    ``first_labels`` is frame 0's annotation ``[H0, W0]`` (uint8 or int64).  The first mask is ``labels_to_masks(first_labels, (h, w),
+    num_classes)``, the label maps are ``masks_to_labels(seg, (h * ps // ups_factor, w * ps // ups_factor), (H0, W0))``.  The tracker keeps the
+    packed first frame and a queue of at most ``n_last_frames`` pairs (packed features, the soft masks ``propagate_labels`` returned: BEFORE
+    the upsample and the normalisation, as :440-441 stores them); a step propagates from ``[first] + queue`` in that order, pushes its
+    result and returns its label map.  A step makes no host synchronisation (the constructor makes one when ``num_classes`` is None).  The
+    bilinear feature resize of :407 / :532 stays the caller's; a frame whose grid differs from the first frame's raises ``ValueError``."""
+
+    def __init__(self, first_feats, first_labels: torch.Tensor, ps: int = 16, ups_factor: int = 8, n_last_frames: int = 7, radius: int = 12,
+                 topk: int = 5, temperature: float = 0.1, num_classes: Optional[int] = None):
+        who = "VideoTracker"
+        for name, v, lo in (("ps", ps, 1), ("ups_factor", ups_factor, 1), ("n_last_frames", n_last_frames, 0)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+                raise ValueError(f"naf_amd.{who}: {name} must be an int of at least {lo}, got {v!r}")
+        if n_last_frames + 1 > _lib.PROPAGATE_MAX_FRAMES:
+            raise ValueError(f"naf_amd.{who}: n_last_frames = {n_last_frames}; the first frame and the queue are at most "
+                             f"{_lib.PROPAGATE_MAX_FRAMES} context frames")
+        self._first = pack_frame(first_feats, "first_feats")
+        self._grid = self._first.shape
+        _, h, w = self._grid
+        if not torch.is_tensor(first_labels) or first_labels.dim() != 2:
+            raise ValueError(f"naf_amd.{who}: `first_labels` must be a [H0, W0] label map")
+        if first_labels.device != self._first.device:
+            raise ValueError(f"naf_amd.{who}: first_labels is on {first_labels.device}, the features on {self._first.device}")
+        self.out_size = (int(first_labels.shape[0]), int(first_labels.shape[1]))
+        self.mid_size = (h * ps // ups_factor, w * ps // ups_factor)
+        self._first_seg = labels_to_masks(first_labels, (h, w), num_classes)
+        self._prop = dict(radius=radius, topk=topk, temperature=temperature)
+        self._n_last = n_last_frames
+        self._queue = collections.deque()
+        a = _lib.MaskLabelsArgs()                                # refuse a geometry no step could serve now, not at the first step
+        a.K, a.h, a.w = int(self._first_seg.shape[1]), h, w
+        (a.mid_h, a.mid_w), (a.out_h, a.out_w) = self.mid_size, self.out_size
+        if _lib.load().naf_mask_labels_select(C.byref(a)) != 0:
+            raise ValueError(f"naf_amd.{who}: {_lib.last_error()}")
+        for n_in, n_out in zip(self.mid_size, self.out_size):    # the resize tables go to the device now, so that no step uploads one
+            device_nearest_table(n_in, n_out, self._first.device)
+
+    @property
+    def context_feats(self) -> tuple:
+        """The frames the next step propagates from, first frame first (``FrameFeatures``)."""
+        return (self._first, *(f for f, _ in self._queue))
+
+    @property
+    def context_segs(self) -> tuple:
+        """Their soft masks ``[1, K, h, w]``, in the same order."""
+        return (self._first_seg, *(s for _, s in self._queue))
+
+    def step(self, feats, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        if _frame_chw(feats, "feats") != self._grid:
+            raise ValueError(f"naf_amd.VideoTracker: the frame is (C, h, w) = {_frame_chw(feats, 'feats')}, the first frame {self._grid}; "
+                             "resize the features to the first frame's grid (eval_video_seg.py:532)")
+        tgt = pack_frame(feats, "feats")
+        seg = propagate_labels(tgt, list(self.context_feats), list(self.context_segs), **self._prop)
+        if self._n_last > 0:
+            if len(self._queue) == self._n_last:
+                self._queue.popleft()
+            self._queue.append((tgt, seg))
+        return masks_to_labels(seg, self.mid_size, self.out_size, out=out)
 
 
 # ---- denoising objective (denoising.py:61-177) ------------------------------------------------------------------------------------
