@@ -440,6 +440,33 @@ int naf_preshrink_image_bwd(void* dimage, const float* dout, int32_t image_dtype
 int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t C, int32_t h, int32_t w,
                     const int64_t v_stride[4], naf_stream_t stream);
 
+/* ---- LAYOUT CONTRACT OF THE ATTENTION ENTRIES ------------------------------------------------------
+ * naf_xna_fwd, naf_xna_head_fwd, naf_xna_head_ce_fwd, naf_xna_mse_fwd, naf_xna_bwd (and naf_xna_bwd_scores) take every 5-D operand as
+ * a pointer plus four ELEMENT strides {b, head, y, x}; the last dim is contiguous.  Each stride of each operand is honoured on its own:
+ * nothing is derived from another stride, from a size or from another operand, so dense head-major and channels-last buffers, gaps
+ * between pixels, rows, heads or images, windows of a larger canvas, channel slices, a batch axis that is not the outermost, y stride <
+ * x stride and stride 0 on a READ-ONLY operand (an operand expanded over the batch or the head axis) are all the same call.  Strides
+ * are non-negative and outputs must not overlap themselves.  A call writes the elements of its outputs and nothing else -- no byte
+ * between or next to them, partial tiles included -- and never writes an input; what lies between or next to the elements of an input
+ * is never read into a result.  Dense by contract: `logits` of naf_xna_fwd, dk_lr / dv_lr and the workspace of naf_xna_bwd, `loss` and
+ * the workspace of naf_xna_mse_fwd; the call stays inside the sizes the header gives for them.
+ *
+ * The matrix-core kernels read 16-byte chunks: they are ELIGIBLE for operands whose pointer is 16-byte aligned and whose four strides
+ * are multiples of 8 elements ("vectorisable"; `out` of naf_xna_fwd: 16-byte aligned, strides multiples of 4).  What a layout outside
+ * that gets, per entry (tests/test_layout_contract_cpu.py holds this table against the *_select / *_supported queries):
+ *   naf_xna_fwd    q or k_lr not vectorisable: NAF_XNA_GENERIC under AUTO (rotate-on-load: -NAF_ERR_UNSUPPORTED, no other kernel rotates).
+ *                  v_lr or out not vectorisable: NAF_XNA_ROWS where the shape is that kernel's (it reads values and writes the output
+ *                  element by element: any alignment, any strides), else NAF_XNA_GENERIC.  An insisted NAF_XNA_MFMA / NAF_XNA_UNION (and
+ *                  NAF_XNA_ROWS for q / k_lr) answers -NAF_ERR_UNSUPPORTED; NAF_XNA_GENERIC serves every layout.
+ *   naf_xna_bwd    NAF_XNA_MFMA needs q, k_lr, v_lr, dout and dq vectorisable.  NAF_XNA_ROWS needs q and k_lr, and v_lr and dout too
+ *                  unless Dv <= 32 (the gather form reads them element by element); it stores dq element by element.  Under AUTO the
+ *                  first of NAF_XNA_MFMA, NAF_XNA_ROWS, NAF_XNA_GENERIC that admits the layout runs; an insisted kernel that does not
+ *                  answers -NAF_ERR_UNSUPPORTED.
+ *   naf_xna_head_fwd / _ce_fwd   q, k_lr, pv_lr (and dlogits) not vectorisable: -NAF_ERR_UNSUPPORTED under AUTO and FUSED alike, the
+ *                  caller composes naf_xna_fwd.  out, loss and labels are stored element by element: any alignment of their element
+ *                  size, any strides {b, y, x} (out: x stride >= N).
+ *   naf_xna_mse_fwd              the rules of NAF_XNA_UNION for q, k_lr, v_lr and out (the gradient); otherwise -NAF_ERR_UNSUPPORTED. */
+
 /* ---- cross-scale neighbourhood attention forward -------------------------------------------------
  * Replaces legacy_attention (attentions.py:16-29: na2d_qk -> *scale -> softmax -> na2d_av), the fused
  * na2d call (attentions.py:72) and the K/V nearest-exact upsampling feeding them (attentions.py:60-61),

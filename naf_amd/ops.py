@@ -650,7 +650,15 @@ def xna_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_
     naf_dtype_supported); q, k_lr and the scores stay bf16 / fp32.  Returns ``out`` as a [B, heads, Ho, Wo, Dv] view
     of a dense channels-last [B, Ho, Wo, heads*Dv] buffer (and, with ``return_logits``, the scaled
     pre-softmax scores [B, heads, Ho, Wo, ky*kx] fp32 -- what the reference's return_weights gives).
+    ``out``: a caller's buffer to write instead, any strides with Dv contiguous; checked before anything is launched -- ValueError unless
+    it is on q's device and has exactly the shape [B, heads, Ho, Wo, Dv].
     """
+    if out is not None and q.dim() == 5 and v_lr.dim() == 5:
+        # the kernel writes through `out`'s pointer and strides with q's and v_lr's sizes: anything else would be written out of bounds
+        want = (*q.shape[:4], v_lr.shape[4])
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != want or out.stride(4) != 1 or out.device != q.device:
+            raise ValueError(f"xna_forward: out must be a [B, heads, Ho, Wo, Dv] = {want} buffer on q's device ({q.device}) with Dv contiguous, got "
+                             + (f"shape {tuple(out.shape)}, strides {tuple(out.stride())} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__))
     half = v_lr.dtype == torch.float16 or out_dtype == torch.float16 or (out is not None and out.dtype == torch.float16)
     for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
         _gpu(t, n)
