@@ -70,7 +70,8 @@ extern "C" {
  * those naf_xna_mse_supported / naf_xna_mse_workspace_bytes / naf_xna_mse_fwd -- the attention forward with the training objective (mean squared error
  * against a target) in its epilogue (naf_xna_mse_args, which embeds naf_xna_args unchanged); and after those naf_davis_jf_select / naf_davis_jf --
  * the integer counts behind the DAVIS J and F measures of two label-map sequences (naf_davis_jf_args); and after those naf_mask_labels_select /
- * naf_mask_labels / naf_nearest_resize_table -- a propagated frame's soft masks to the label map the reference writes to disk (naf_mask_labels_args). */
+ * naf_mask_labels / naf_nearest_resize_table -- a propagated frame's soft masks to the label map the reference writes to disk (naf_mask_labels_args);
+ * and after those naf_xna_points -- the attention's scores, weights and features at N query pixels (naf_xna_points_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -1166,6 +1167,51 @@ typedef struct naf_mask_labels_args {
 int naf_mask_labels_select(const naf_mask_labels_args* a);
 int naf_mask_labels(const naf_mask_labels_args* a, naf_stream_t stream);
 int naf_nearest_resize_table(int32_t* out, int32_t n_in, int32_t n_out);
+
+/* ---- point queries: the attention at N pixels (added after the label-map entries; detect by symbol) ----
+ * What the reference's attention viewer reads out of model(image, feats, size, return_weights=True) (notebooks/attention_maps.ipynb, cell 11:
+ * one pixel's ky*kx scores per head out of the [B, heads, Ho, Wo, ky*kx] tensor) and what a sparse consumer (keypoints, correspondences) wants of
+ * the feature map, for N points (b, y, x) in OUTPUT coordinates, without either dense tensor.  Three optional outputs, each skipped when NULL:
+ *   logits  device float [N][heads][ky*kx] dense: the scaled pre-softmax scores, i.e. the rows of naf_xna_fwd's `logits`
+ *   probs   device float [N][heads][ky*kx] dense: their softmax
+ *   out     device float [N][heads*Dv] dense: the upsampled feature vectors; needs v_lr (v_lr NULL with out NULL: weights only)
+ * Operands:
+ *   k_lr, v_lr  as naf_xna_fwd's (layout contract above: pointer plus {b, head, y, x} element strides, last dim contiguous, stride 0 allowed);
+ *               v_dtype NAF_BF16 or NAF_F16 says what v_lr holds
+ *   idx_y, idx_x  device int32 [Ho][ky], [Wo][kx] from naf_axis_index_table (entries are clamped to the low-res grid)
+ *   points  device int32 [N][3] = (b, y, x), dense
+ *   q       device bf16 [B, heads, Ho, Wo, Dq], strides {b, head, y, x}, Dq contiguous: the rotated queries of naf_rope_pool_fwd -- or, with
+ *           rope_tab_y / rope_tab_x (device float [Ho][2][Dq/4] / [Wo][2][Dq/4] from naf_rope_tables, both or neither; Dq % 4 == 0), the
+ *           UN-rotated guidance: the kernel rotates the N * heads vectors it reads, same arithmetic and bf16 rounding as naf_rope_pool_fwd
+ *           (both forms give the same bits), so no query tensor is written for a handful of points
+ * One wave per (point, head), the loop order and the reductions of the table-driven scalar kernel (NAF_XNA_GENERIC): for a point's
+ * (b, head, y, x), logits and out are bit-identical to what naf_xna_fwd(path = NAF_XNA_GENERIC, out_dtype = NAF_F32) writes for that pixel (half
+ * values: to that kernel's accumulator before its rounding to half).  Any Dq, Dv, ky, kx with 16 * (ky*kx + Dq) bytes <= 64 KB
+ * (NAF_ERR_UNSUPPORTED beyond).
+ * A coordinate is compared with the sizes before it is used in an address: a point outside [0, B) x [0, Ho) x [0, Wo) reads nothing and gets
+ * NaN in its rows of every output; the other rows are unaffected.  Nothing is written outside the N rows.  N = 0 launches nothing.
+ * scale <= 0: Dq^-0.5.  Caller-owned memory and stream; nothing is allocated; capturable. */
+typedef struct naf_xna_points_args {
+    const void* q;
+    const void* k_lr;
+    const void* v_lr;
+    const int32_t* points;
+    const int32_t* idx_y;
+    const int32_t* idx_x;
+    const float* rope_tab_y;
+    const float* rope_tab_x;
+    float* logits;
+    float* probs;
+    float* out;
+    int32_t N, B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx;
+    int32_t v_dtype; /* naf_dtype of v_lr: NAF_BF16 or NAF_F16 */
+    float scale;
+    int32_t reserved; /* must be 0 */
+    int64_t q_stride[4];
+    int64_t k_stride[4];
+    int64_t v_stride[4];
+} naf_xna_points_args;
+int naf_xna_points(const naf_xna_points_args* a, naf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -122,6 +122,18 @@ class MaskLabelsArgs(C.Structure):
     ]
 
 
+class XnaPointsArgs(C.Structure):
+    """naf_xna_points_args (added after the label-map entries, detected by symbol): the attention's scores, weights and features at N pixels."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k_lr", C.c_void_p), ("v_lr", C.c_void_p), ("points", C.c_void_p), ("idx_y", C.c_void_p), ("idx_x", C.c_void_p),
+        ("rope_tab_y", C.c_void_p), ("rope_tab_x", C.c_void_p), ("logits", C.c_void_p), ("probs", C.c_void_p), ("out", C.c_void_p),
+        ("N", C.c_int32), ("B", C.c_int32), ("heads", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("Dq", C.c_int32), ("Dv", C.c_int32), ("ky", C.c_int32), ("kx", C.c_int32), ("v_dtype", C.c_int32), ("scale", C.c_float),
+        ("reserved", C.c_int32),
+        ("q_stride", I64x4), ("k_stride", I64x4), ("v_stride", I64x4),
+    ]
+
+
 DENOISE_LOSS, DENOISE_METRICS = 0, 1            # naf_denoise_mode
 
 
@@ -358,6 +370,7 @@ SIGNATURES = {
     "naf_mask_labels_select": (C.c_int, [C.POINTER(MaskLabelsArgs)]),
     "naf_mask_labels": (C.c_int, [C.POINTER(MaskLabelsArgs), C.c_void_p]),
     "naf_nearest_resize_table": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
+    "naf_xna_points": (C.c_int, [C.POINTER(XnaPointsArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

@@ -23,6 +23,7 @@ view of a channels-last buffer -- the same view the reference returns on its fus
 """
 from __future__ import annotations
 
+import collections
 import os
 
 from typing import Optional, Tuple
@@ -451,16 +452,34 @@ class ImageEncoder(nn.Module):
                     cur = dst
         return cat.permute(0, 3, 1, 2)
 
-    def guidance(self, image: torch.Tensor, output_size: Tuple[int, int]) -> torch.Tensor:
-        """Pre-RoPE guidance features, logical [B, dim, Ho, Wo] (naf.py:37-49 + :31-35)."""
+    # ``guidance`` in three steps, so that a ``Guidance`` can keep what each one returns: the stem's input (the image, or its pre-shrunk
+    # copy), the stem, the pooling to the output size.
+    @staticmethod
+    def stem_input_size(image_size, output_size) -> Tuple[int, int]:
+        """The size the stem runs at for this output size: the image's own, or the pre-shrunk one of naf.py:39-48."""
+        H, W = int(image_size[0]), int(image_size[1])
         ho, wo = output_size
+        if H > 4 * ho or W > 4 * wo:
+            return (min(H, 4 * ho, 4 * wo), min(W, 4 * wo, 4 * ho))
+        return (H, W)
+
+    def stem_input(self, image: torch.Tensor, size: Tuple[int, int]) -> torch.Tensor:
+        """``image`` at ``stem_input_size``: itself, or its bilinear pre-shrink."""
         x = image
-        if x.shape[-2] > 4 * ho or x.shape[-1] > 4 * wo:                       # naf.py:39-48
-            size = (min(x.shape[-2], 4 * ho, 4 * wo), min(x.shape[-1], 4 * wo, 4 * ho))
+        if tuple(x.shape[-2:]) != tuple(size):
             if x.is_cuda and x.dim() == 4 and x.shape[1] == 3 and x.dtype in (torch.float32, torch.bfloat16):
                 x = ops.preshrink_image(x, size)                               # the kernel naf_forward uses as well
             else:
                 x = F.interpolate(x.float(), size=size, mode="bilinear", align_corners=False)
+        return x
+
+    def guidance(self, image: torch.Tensor, output_size: Tuple[int, int]) -> torch.Tensor:
+        """Pre-RoPE guidance features, logical [B, dim, Ho, Wo] (naf.py:37-49 + :31-35)."""
+        x = self.stem_input(image, self.stem_input_size(image.shape[-2:], output_size))
+        return self.pool(self.stem(x), output_size)
+
+    def stem(self, x: torch.Tensor) -> torch.Tensor:
+        """Both conv branches on the stem's input (naf.py:31-33): logical [B, dim, Hs, Ws]."""
         if self.use_encoder and self.stem_impl == "hip":
             if not self._hip_stem_ok():
                 raise RuntimeError(f"naf_amd: the HIP conv stem serves hidden widths that are multiples of 16 up to 256 with "
@@ -471,6 +490,11 @@ class ImageEncoder(nn.Module):
             dt = self.stem_dtype
             x = x.to(dt).contiguous(memory_format=torch.channels_last)
             x = torch.cat([self._branch(x, self.encoder, dt), self._branch(x, self.sem_encoder, dt)], dim=1)
+        return x
+
+    def pool(self, x: torch.Tensor, output_size: Tuple[int, int]) -> torch.Tensor:
+        """The stem's output at the output size (naf.py:34), channels-last; the tensor itself when it is both already."""
+        ho, wo = output_size
         if x.shape[-2:] != (ho, wo):                                           # naf.py:34
             if (x.dtype == torch.bfloat16 and x.is_cuda and x.shape[1] % 8 == 0
                     and x.is_contiguous(memory_format=torch.channels_last)):
@@ -555,6 +579,8 @@ class GraphedForward:
 
     def __init__(self, model: "NAF", image: torch.Tensor, features: torch.Tensor, output_size, warmup: int = 2,
                  capture_error_mode: str = "global"):
+        if isinstance(image, Guidance):
+            raise TypeError("capture() takes the image, not a Guidance: the captured forward is the one-call plan, which encodes the image itself")
         if not (image.is_cuda and features.is_cuda):
             raise RuntimeError("GraphedForward needs device tensors")
         self.model, self.output_size = model, (int(output_size[0]), int(output_size[1]))
@@ -657,6 +683,120 @@ def _apply_head(head, x: torch.Tensor) -> torch.Tensor:
     return F.conv2d(x.to(weight.dtype), weight, None if bias is None else bias.to(weight.dtype))
 
 
+PointQuery = collections.namedtuple("PointQuery", ["features", "logits", "probs", "window_y", "window_x"])
+PointQuery.__doc__ = """Result of ``NAF.query``: ``features`` [N, C] fp32 or None, ``logits`` / ``probs`` [N, heads, ky*kx] fp32 or None,
+``window_y`` [N, ky] / ``window_x`` [N, kx] int32: the low-res rows / columns each point attends to (-1 for a point outside the grid)."""
+
+
+class Guidance:
+    """The image-side state of a ``NAF`` call, encoded once (``NAF.guide``) and accepted wherever ``NAF.forward`` takes an image on an
+    inference call: nothing in the guidance depends on the feature map but the size of its grid, so other backbones, other grids, other
+    dtypes and other output sizes for the same image skip the stem and -- where the keys are cached too -- the RoPE pass
+    (notebooks/inference.ipynb cells 16 and 19 of the reference upsample five backbones / five sizes for one image).
+
+    Four caches, filled on demand under ``torch.no_grad()``:
+      stem output      per stem-input size (the image's, or a pre-shrunk one)   [B, dim, Hs, Ws] channels-last bf16
+      pooled guidance  per (Ho, Wo)                                             un-rotated guidance at the output size
+      rotated queries  per (Ho, Wo)                                             only once a call could not rotate on load
+      keys             per (Ho, Wo, h, w)                                       pooled RoPE'd keys
+    (and the RoPE tables per (Ho, Wo)).  ``nbytes``: bytes the caches hold; ``clear()`` drops them.
+
+    It records (data_ptr, _version) of every parameter, of ``rope.periods`` and of the image: a call after an in-place change of any of them
+    raises RuntimeError (stale).  Towards ``NAF``'s argument checks it answers like the image it stands for (``shape``, ``dim()``,
+    ``is_cuda``, ``device``, ``dtype``, ``requires_grad``)."""
+
+    def __init__(self, model: "NAF", image: torch.Tensor):
+        if not isinstance(image, torch.Tensor) or image.dim() != 4:
+            raise ValueError(f"guide: expected an image [B, 3, H, W], got "
+                             + (f"{tuple(image.shape)}" if isinstance(image, torch.Tensor) else type(image).__name__))
+        if not image.is_cuda:
+            raise RuntimeError(f"naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got image on {image.device}")
+        self.model, self.image = model, image
+        self._stamp = self._stamp_now()
+        self._stem, self._pooled, self._queries, self._keys, self._tables = {}, {}, {}, {}, {}
+
+    # ---- what NAF's argument checks read of an image ----
+    shape = property(lambda self: self.image.shape)
+    device = property(lambda self: self.image.device)
+    dtype = property(lambda self: self.image.dtype)
+    is_cuda = property(lambda self: self.image.is_cuda)
+    requires_grad = property(lambda self: self.image.requires_grad)
+
+    def dim(self) -> int:
+        return self.image.dim()
+
+    def _stamp_now(self):
+        m, per = self.model, self.model.image_encoder.rope.periods
+        return (tuple((p.data_ptr(), p._version) for p in _walk_parameters(m)), (per.data_ptr(), per._version),
+                (self.image.data_ptr(), self.image._version))
+
+    def check(self, model: "NAF") -> None:
+        """RuntimeError unless this is ``model``'s guidance and neither its parameters nor the image changed since it was made."""
+        if model is not self.model:
+            raise RuntimeError("Guidance: made by another NAF module; call guide() on the module that uses it")
+        prm, per, img = self._stamp_now()
+        if img != self._stamp[2]:
+            raise RuntimeError("Guidance is stale: the image was modified in place after guide(); call guide() again")
+        if prm != self._stamp[0] or per != self._stamp[1]:
+            raise RuntimeError("Guidance is stale: a parameter of the module (or rope.periods) changed after guide(); call guide() again")
+
+    def _cached(self):
+        for d in (self._stem, self._pooled, self._queries, self._keys):
+            yield from d.values()
+        for ty, tx in self._tables.values():
+            yield ty
+            yield tx
+
+    @property
+    def nbytes(self) -> int:
+        """Bytes of device memory the caches hold (a stem output that is also a pooled level counts once)."""
+        seen = {}
+        for t in self._cached():
+            st = t.untyped_storage()
+            seen[st.data_ptr()] = st.nbytes()
+        return sum(seen.values())
+
+    def clear(self) -> None:
+        for d in (self._stem, self._pooled, self._queries, self._keys, self._tables):
+            d.clear()
+
+    def tables(self, ho: int, wo: int):
+        t = self._tables.get((ho, wo))
+        if t is None:
+            t = self._tables[(ho, wo)] = self.model.image_encoder.rope.tables(ho, wo)
+        return t
+
+    def pooled(self, ho: int, wo: int) -> torch.Tensor:
+        """``image_encoder.guidance(image, (ho, wo))``, from the caches."""
+        x = self._pooled.get((ho, wo))
+        if x is None:
+            enc = self.model.image_encoder
+            with torch.no_grad(), ops._Timed("stem"):
+                size = enc.stem_input_size(self.image.shape[-2:], (ho, wo))
+                s = self._stem.get(size)
+                if s is None:
+                    s = self._stem[size] = enc.stem(enc.stem_input(self.image, size))
+                x = self._pooled[(ho, wo)] = enc.pool(s, (ho, wo))
+        return x
+
+    def queries_keys(self, ho: int, wo: int, lr_size, heads_rope: int, q_layout: str, need_q: bool):
+        """(rotated queries or None, keys) of ``ops.rope_pool`` for this output size and feature grid: cached ones where there are, else
+        ONE launch -- queries and keys together when the queries are needed for the first time, keys only otherwise."""
+        h, w = int(lr_size[0]), int(lr_size[1])
+        q, k = self._queries.get((ho, wo)), self._keys.get((ho, wo, h, w))
+        if k is None or (need_q and q is None):
+            x = self.pooled(ho, wo)
+            tab_y, tab_x = self.tables(ho, wo)
+            with torch.no_grad():
+                if need_q and q is None:
+                    q, k = ops.rope_pool(x, tab_y, tab_x, heads_rope, (h, w), q_layout=q_layout)
+                    self._queries[(ho, wo)] = q
+                else:
+                    _, k = ops.rope_pool(x, tab_y, tab_x, heads_rope, (h, w), write_q=False)
+            self._keys[(ho, wo, h, w)] = k
+        return (q if need_q else None), k
+
+
 class NAF(nn.Module):
     """Drop-in for the reference's ``NAF`` (naf.py:72-116): same constructor, same ``state_dict``."""
 
@@ -678,12 +818,19 @@ class NAF(nn.Module):
         rope_tables is None when q5 is already rotated, or the (tab_y, tab_x) pair when q5 is the un-rotated
         guidance that the attention kernel rotates on load (``fuse_for`` = (Dv, out_dtype) of the attention call
         asks for that; it is granted when the shapes allow it, see ops.xna_rope_fusable).  ``fusable``: a predicate
-        ``(q5, (tab_y, tab_x)) -> bool`` that decides it instead (the head-summed attention asks its own kernel, ``ops.xna_head_select``)."""
+        ``(q5, (tab_y, tab_x)) -> bool`` that decides it instead (the head-summed attention asks its own kernel, ``ops.xna_head_select``).
+        ``image`` may be a ``Guidance``: the guidance, the tables, rotated queries and keys then come from its caches (``Guidance.queries_keys``:
+        at most one ``ops.rope_pool`` launch, none when this size and grid were seen); the choice between the two query forms is the same."""
         ho, wo = int(output_size[0]), int(output_size[1])
         enc = self.image_encoder
-        with ops._Timed("stem"):
-            x = enc.guidance(image, (ho, wo))
-        tab_y, tab_x = enc.rope.tables(ho, wo)
+        g = image if isinstance(image, Guidance) else None
+        if g is not None:
+            x = g.pooled(ho, wo)
+            tab_y, tab_x = g.tables(ho, wo)
+        else:
+            with ops._Timed("stem"):
+                x = enc.guidance(image, (ho, wo))
+            tab_y, tab_x = enc.rope.tables(ho, wo)
         heads_rope, heads_attn = enc.rope.num_heads, self.upsampler.num_heads
         same = heads_attn == heads_rope
         if (fuse_for is not None or fusable is not None) and self.fuse_rope and same and x.dtype == torch.bfloat16:
@@ -697,9 +844,16 @@ class NAF(nn.Module):
                     ok = ops.xna_rope_fusable(q5, lr_size, fuse_for[0], self.upsampler.kernel_size, (tab_y, tab_x),
                                               out_dtype=fuse_for[1], path=self.xna_path)
                 if ok:
-                    _, k5 = ops.rope_pool(x, tab_y, tab_x, heads_rope, lr_size, write_q=False)
+                    if g is not None:
+                        _, k5 = g.queries_keys(ho, wo, lr_size, heads_rope, "head_major", need_q=False)
+                    else:
+                        _, k5 = ops.rope_pool(x, tab_y, tab_x, heads_rope, lr_size, write_q=False)
                     return q5, k5, (tab_y, tab_x)
-        q5, k5 = ops.rope_pool(x, tab_y, tab_x, heads_rope, lr_size, q_layout="head_major" if same else "channels_last")
+        q_layout = "head_major" if same else "channels_last"
+        if g is not None:
+            q5, k5 = g.queries_keys(ho, wo, lr_size, heads_rope, q_layout, need_q=True)
+        else:
+            q5, k5 = ops.rope_pool(x, tab_y, tab_x, heads_rope, lr_size, q_layout=q_layout)
         if not same:        # re-split the channel axis for attention: pure views of channels-last buffers
             B, _, Ho, Wo, _ = q5.shape
             dim = enc.out_channels
@@ -910,6 +1064,13 @@ class NAF(nn.Module):
         under ``torch.no_grad()`` take the inference path; that path always uses the deterministic eval-mode RoPE
         coordinates (the reference's train-mode coordinate jitter only exists on the differentiable path here).
 
+        ``image`` may be a ``Guidance`` (``self.guide(image)``) on every inference call described here -- the plain call with bf16 / fp16 /
+        fp32 features, ``return_weights=True``, ``head=`` with or without ``target`` / ``predict``, ``confusion=``: the stem, the pooling
+        and, for a size and grid seen before, the RoPE pass are not run again, and the result is what the image call computes through the
+        same operators (``single_call = False``).  Gradients with respect to the head keep working.  Refused: ``regress=`` and
+        ``return_weights="differentiable"`` (ValueError: both train the encoder), a call that would take the training path (RuntimeError),
+        a stale ``Guidance`` (RuntimeError).  ``self.query(guidance, points, ...)`` is the attention at N pixels.
+
         ``head`` (keyword only): a linear probe on the upsampled features -- an ``nn.Conv2d`` with a 1x1 kernel, an ``nn.Linear`` or a
         ``(weight, bias_or_None)`` pair (weight [N, C] or [N, C, 1, 1]) -- what evaluation/eval_seg_probing.py:56,104-111 puts on
         ``model(image, feats, (H, W))``.  The call then returns the logits ``head(naf(image, features, size))`` as a logical
@@ -969,6 +1130,8 @@ class NAF(nn.Module):
         and materialised queries feed the loss-only launch (nothing but the loss is written).  ``regress`` together with ``head``,
         ``target``, ``predict``, ``confusion`` or ``return_weights`` raises ValueError; shape, dtype and device mismatches raise before any
         device work.  Not offered: other losses, the reference's unused ``normalize=True``, ``capture()`` of this call."""
+        if isinstance(image, Guidance):
+            self._check_guidance_call(image, features, return_weights, regress, confusion)
         if regress is not None:
             if head is not None or target is not None or predict or (confusion is not None and confusion is not False) or return_weights:
                 raise ValueError("naf(..., regress=...) is the regression objective of the features themselves: it does not combine with "
@@ -992,6 +1155,113 @@ class NAF(nn.Module):
             return self.forward_train(image, features, output_size, amp="auto", return_weights=return_weights)
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)
+
+    # ---- encode the image once ------------------------------------------------------------------------------------------------
+    def guide(self, image: torch.Tensor, output_size=None) -> Guidance:
+        """The image-side state of a call, for reuse: ``g = naf.guide(image)``, then ``naf(g, feats, size)`` for any number of feature
+        maps, grids, dtypes, sizes and modes (see ``Guidance`` and ``forward``).  ``output_size``: build that level now (stem and
+        pooling) instead of on the first call.  Always the inference encoder (bf16 stem, deterministic RoPE coordinates)."""
+        g = Guidance(self, image)
+        if output_size is not None:
+            g.pooled(int(output_size[0]), int(output_size[1]))
+        return g
+
+    def _check_guidance_call(self, g: Guidance, features, return_weights, regress, confusion) -> None:
+        """What ``forward`` refuses of a call whose image is a ``Guidance``, each with its reason."""
+        if regress is not None:
+            raise ValueError("naf(guidance, ..., regress=...): the regression objective trains the encoder, a Guidance holds the frozen "
+                             "encoder's output; pass the image")
+        if isinstance(return_weights, str) and _scores_mode(return_weights) == "differentiable":
+            raise ValueError("naf(guidance, ..., return_weights='differentiable'): the scores' gradient reaches the encoder, a Guidance holds "
+                             "the frozen encoder's output; pass the image (return_weights=True works)")
+        g.check(self)
+        evaluation = confusion is not None and confusion is not False        # never differentiable, whatever the gradient mode
+        if not evaluation and torch.is_grad_enabled() and (g.requires_grad or (isinstance(features, torch.Tensor) and features.requires_grad) or
+                                                           (self.training and any(p.requires_grad for p in self.parameters()))):
+            raise RuntimeError("naf(guidance, ...): this call wants a gradient for the upsampler, the image or the features (gradient mode with an "
+                               "input that requires grad, or .train() with trainable parameters) and would take the training path; a Guidance "
+                               "serves inference calls -- use torch.no_grad() / .eval() / requires_grad_(False), or pass the image")
+
+    def query(self, guidance, points, features=None, output_size=None, weights="logits", lr_size=None) -> PointQuery:
+        """The attention at N pixels: ``naf.query(g, points, features=feats, output_size=(Ho, Wo), weights="logits")``.
+
+        ``guidance``: a ``Guidance`` (or an image, encoded for this call).  ``points``: an integer tensor [N, 3] of (b, y, x) in output
+        coordinates -- [N, 2] of (y, x) when the batch is 1 -- on any device.  ``weights``: "logits" (the scaled pre-softmax scores: the
+        rows of what ``return_weights=True`` returns), "softmax", "both" or None.  ``features`` [B, C, h, w]: also the upsampled feature
+        vectors of the points; without them pass ``lr_size=(h, w)``, the grid the keys are pooled to.  Returns ``PointQuery(features [N, C]
+        fp32 or None, logits, probs [N, heads, k*k] fp32 or None, window_y [N, k], window_x [N, k] int32)``: the windows are the low-res
+        rows / columns each point attends to (duplicates included), taken from the index tables on the device.  A point outside the grid
+        gets NaN rows and -1 windows.  No dense score tensor or feature map is formed (``ops.xna_points``); where the RoPE heads are the
+        attention heads and no rotated queries are cached the kernel rotates the N vectors it reads, so no query tensor is written either.
+        Keys come from the ``Guidance``'s cache; values go through ``ops.pack_values`` (fp32 features are read as bf16, as everywhere).
+        Nothing synchronises with the host."""
+        if weights not in ("logits", "softmax", "both", None):
+            raise ValueError(f"query: weights must be 'logits', 'softmax', 'both' or None, got {weights!r}")
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] not in (2, 3):
+            raise ValueError("query: points must be an integer tensor [N, 3] of (b, y, x), or [N, 2] of (y, x) for a batch of 1; got "
+                             + (f"{tuple(points.shape)}" if isinstance(points, torch.Tensor) else type(points).__name__))
+        if points.dtype not in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8):
+            raise TypeError(f"query: points must be an integer tensor, got {points.dtype}")
+        if output_size is None:
+            raise ValueError("query: output_size=(Ho, Wo) is required: the points are in its coordinates")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        if features is not None:
+            if not isinstance(features, torch.Tensor) or features.dim() != 4:
+                raise ValueError("query: features must be [B, C, h, w]")
+            if lr_size is not None and (int(lr_size[0]), int(lr_size[1])) != tuple(features.shape[-2:]):
+                raise ValueError(f"query: lr_size {tuple(lr_size)} contradicts the features' grid {tuple(features.shape[-2:])}")
+            if features.shape[1] % self.upsampler.num_heads:
+                raise ValueError(f"feature channels {features.shape[1]} not divisible by {self.upsampler.num_heads} heads")
+            h, w = int(features.shape[-2]), int(features.shape[-1])
+        elif lr_size is None:
+            raise ValueError("query: without features pass lr_size=(h, w), the grid the keys are pooled to")
+        else:
+            h, w = int(lr_size[0]), int(lr_size[1])
+        if features is None and weights is None:
+            raise ValueError("query: nothing asked for: no features and weights=None")
+        g = guidance if isinstance(guidance, Guidance) else self.guide(guidance)
+        g.check(self)
+        B = g.shape[0]
+        if features is not None and (features.shape[0] != B or not features.is_cuda):
+            if features.shape[0] != B:
+                raise ValueError(f"query: features of batch {features.shape[0]}, image of batch {B}")
+            raise RuntimeError(f"naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got features on {features.device}")
+        if points.shape[1] == 2 and B != 1:
+            raise ValueError(f"query: [N, 2] points name no image; the batch is {B}, pass [N, 3] of (b, y, x)")
+        dev = g.device
+        with torch.no_grad():
+            pts = points.to(device=dev, dtype=torch.int32)
+            if pts.shape[1] == 2:
+                pts = torch.cat([torch.zeros_like(pts[:, :1]), pts], dim=1)
+            pts = pts.contiguous()
+            enc, heads, ksz = self.image_encoder, self.upsampler.num_heads, self.upsampler.kernel_size
+            heads_rope = enc.rope.num_heads
+            same = heads == heads_rope
+            tabs = None
+            q5 = None
+            if same and self.fuse_rope and (ho, wo) not in g._queries:
+                x = g.pooled(ho, wo)
+                xq = x.permute(0, 2, 3, 1)
+                if x.dtype == torch.bfloat16 and xq.stride(3) == 1:     # the un-rotated guidance: the kernel rotates the vectors it reads
+                    q5 = xq.unflatten(3, (heads_rope, x.shape[1] // heads_rope)).permute(0, 3, 1, 2, 4)
+                    tabs = g.tables(ho, wo)
+                    _, k5 = g.queries_keys(ho, wo, (h, w), heads_rope, "head_major", need_q=False)
+            if q5 is None:
+                q5, k5, _ = self.guidance_qk(g, (h, w), (ho, wo))
+            v5 = None
+            if features is not None:
+                C_ = features.shape[1]
+                v5 = ops.pack_values(features).view(B, h, w, heads, C_ // heads).permute(0, 3, 1, 2, 4)
+            with ops._Timed("attention"):
+                out, logits, probs = ops.xna_points(q5, k5, v5, pts, ksz, want_logits=weights in ("logits", "both"),
+                                                    want_probs=weights in ("softmax", "both"), scale=self.upsampler.scale, rope_tables=tabs)
+            iy = ops.device_index_table(ho, h, ksz[0], dev)
+            ix = ops.device_index_table(wo, w, ksz[1], dev)
+            py, px = pts[:, 1].long(), pts[:, 2].long()
+            ok = ((pts[:, 0] >= 0) & (pts[:, 0] < B) & (py >= 0) & (py < ho) & (px >= 0) & (px < wo))[:, None]
+            win_y = torch.where(ok, iy[py.clamp(0, ho - 1)], -1)
+            win_x = torch.where(ok, ix[px.clamp(0, wo - 1)], -1)
+        return PointQuery(out, logits, probs, win_y, win_x)
 
     def _forward_regress(self, image, features, output_size, regress, regress_path):
         """``forward(..., regress=regress)``: see ``forward``."""
@@ -1146,7 +1416,7 @@ class NAF(nn.Module):
                 k = self.upsampler.kernel_size
                 return out, torch.empty((0, self.upsampler.num_heads, ho, wo, k[0] * k[1]), dtype=torch.float32, device=features.device)
             return out
-        if self.single_call:
+        if self.single_call and not isinstance(image, Guidance):       # (the one-call plan runs the whole forward: nothing of it is reusable)
             plan = self._forward_plan(image, features, output_size)
             if plan is not None:
                 timer = ops.KERNEL_TIMER

@@ -9,6 +9,7 @@ Reference counterparts (paths relative to the reference repo):
   rope_pool          RoPE.forward rotation + KeyEncoder pooling         src/layers/rope.py:147-174, src/model/naf.py:63-69
   pack_values        CrossAttention._resize layout/dtype part           src/layers/attentions.py:50-51
   xna_forward        legacy_attention / na2d                            src/layers/attentions.py:16-29,72
+  xna_points         the same at N query pixels (the attention viewer's read)    notebooks/attention_maps.ipynb cell 11
   xna_head_forward   the same with the probe's 1x1 convolution folded in  evaluation/eval_seg_probing.py:56,104-111
   propagate_labels   label_propagation after feature extraction          evaluation/eval_video_seg.py:499-561
   davis_jf / davis_statistics  davis_db_eval_iou, davis_db_eval_boundary, davis_db_statistics  evaluation/eval_video_seg.py:145-269
@@ -693,6 +694,97 @@ def xna_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_
         rc = lib.naf_xna_fwd(C.byref(a), _stream(q))
     _lib.check(rc, "naf_xna_fwd")
     return (out, logits) if return_logits else out
+
+
+def xna_points(q: torch.Tensor, k_lr: torch.Tensor, v_lr: Optional[torch.Tensor], points: torch.Tensor, kernel_size, *,
+               want_logits: bool = True, want_probs: bool = False, scale: Optional[float] = None, rope_tables=None,
+               logits: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """The attention of ``xna_forward`` at N query pixels (naf_xna_points): ``points`` int32 [N, 3] of (b, y, x) in output coordinates on q's
+    device.  Returns ``(out, logits, probs)``: ``out`` [N, heads * Dv] fp32 feature vectors (None when ``v_lr`` is None: weights only),
+    ``logits`` [N, heads, ky*kx] fp32 scaled pre-softmax scores (the rows of ``xna_forward(..., return_logits=True)``'s second result; None
+    unless ``want_logits``), ``probs`` their softmax (None unless ``want_probs``).  No dense [B, heads, Ho, Wo, .] tensor is formed.
+
+    q / k_lr / v_lr as ``xna_forward``'s (5-D strided views, last dim contiguous, any strides incl. 0); v_lr bf16 or float16.
+    ``rope_tables=(tab_y, tab_x)``: q is the UN-rotated guidance and the kernel rotates the N * heads vectors it reads -- the same bits as
+    rotated queries, for every geometry (unlike ``xna_forward``'s rotate-on-load).  Scores and features are bit-identical to the pixel of
+    ``xna_forward(..., path="generic", out_dtype=torch.float32, return_logits=True)``.  A point outside [0, B) x [0, Ho) x [0, Wo) gets NaN
+    rows; nothing is read for it.  ``logits`` / ``probs`` / ``out``: a caller's dense fp32 buffers of exactly those shapes to write instead
+    (giving one asks for that output).  N = 0 launches nothing."""
+    who = "xna_points"
+    for t, n in ((q, "q"), (k_lr, "k_lr")) + (((v_lr, "v_lr"),) if v_lr is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.dim() != 5 or t.stride(4) != 1:
+            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+        if t is v_lr:
+            if t.dtype not in (torch.bfloat16, torch.float16):
+                raise TypeError(f"{who}: v_lr must be bfloat16 or float16, got {t.dtype}")
+        elif t.dtype != torch.bfloat16:
+            raise TypeError(f"{who}: {n} must be bfloat16, got {t.dtype}")
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w = int(k_lr.shape[2]), int(k_lr.shape[3])
+    if tuple(k_lr.shape) != (B, heads, h, w, Dq):
+        raise ValueError(f"{who}: k_lr shape {tuple(k_lr.shape)} does not match q {tuple(q.shape)}")
+    Dv = 0
+    if v_lr is not None:
+        Dv = int(v_lr.shape[4])
+        if tuple(v_lr.shape) != (B, heads, h, w, Dv):
+            raise ValueError(f"{who}: v_lr shape {tuple(v_lr.shape)} does not match k_lr {tuple(k_lr.shape)}")
+    elif out is not None:
+        raise ValueError(f"{who}: `out` needs the values v_lr")
+    if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError(f"{who}: points must be [N, 3] of (b, y, x), got "
+                         + (f"{tuple(points.shape)}" if isinstance(points, torch.Tensor) else type(points).__name__))
+    if points.dtype != torch.int32:
+        raise TypeError(f"{who}: points must be int32, got {points.dtype}")
+    N = int(points.shape[0])
+    want_logits, want_probs = bool(want_logits) or logits is not None, bool(want_probs) or probs is not None
+    if not (want_logits or want_probs or v_lr is not None):
+        raise ValueError(f"{who}: nothing to compute: no values and neither logits nor probs asked for")
+    for buf, n, shape in ((logits, "logits", (N, heads, ky * kx)), (probs, "probs", (N, heads, ky * kx)), (out, "out", (N, heads * Dv))):
+        if buf is not None and (not isinstance(buf, torch.Tensor) or buf.dtype != torch.float32 or tuple(buf.shape) != shape
+                                or not buf.is_contiguous() or buf.device != q.device):
+            raise ValueError(f"{who}: {n} must be a dense float32 {shape} buffer on q's device")
+    if rope_tables is not None:
+        ty, tx = rope_tables
+        if Dq % 4 or ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
+                or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
+            raise ValueError(f"{who}: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (points, "points")) + (((v_lr, "v_lr"),) if v_lr is not None else ()):
+        _gpu(t, n)
+        if t.device != q.device:
+            raise ValueError(f"{who}: {n} is on {t.device}, q on {q.device}")
+    lib = _lib.load()
+    dev = q.device
+    points = points.contiguous()
+    if logits is None and want_logits:
+        logits = torch.empty((N, heads, ky * kx), dtype=torch.float32, device=dev)
+    if probs is None and want_probs:
+        probs = torch.empty((N, heads, ky * kx), dtype=torch.float32, device=dev)
+    if out is None and v_lr is not None:
+        out = torch.empty((N, heads * Dv), dtype=torch.float32, device=dev)
+    if N == 0:
+        return out, logits, probs
+    iy = device_index_table(Ho, h, ky, dev)
+    ix = device_index_table(Wo, w, kx, dev)
+    a = _lib.XnaPointsArgs()
+    a.q, a.k_lr, a.v_lr, a.points = q.data_ptr(), k_lr.data_ptr(), (v_lr.data_ptr() if v_lr is not None else None), points.data_ptr()
+    a.idx_y, a.idx_x = iy.data_ptr(), ix.data_ptr()
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    a.logits = logits.data_ptr() if logits is not None else None
+    a.probs = probs.data_ptr() if probs is not None else None
+    a.out = out.data_ptr() if out is not None else None
+    a.N, a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = N, B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
+    a.v_dtype = _DT_VALUES[v_lr.dtype] if v_lr is not None else _lib.NAF_BF16
+    a.scale = float(scale) if scale else 0.0
+    a.q_stride = _strides4(q, (0, 1, 2, 3))
+    a.k_stride = _strides4(k_lr, (0, 1, 2, 3))
+    if v_lr is not None:
+        a.v_stride = _strides4(v_lr, (0, 1, 2, 3))
+    with torch.cuda.device(dev), _Timed("xna_points"):
+        rc = lib.naf_xna_points(C.byref(a), _stream(q))
+    _lib.check(rc, "naf_xna_points")
+    return out, logits, probs
 
 
 def _fill_xna_bwd(q, k, v, dout, dq, dk, dv, ky, kx, scale) -> XnaBwdArgs:
