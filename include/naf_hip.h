@@ -71,7 +71,8 @@ extern "C" {
  * against a target) in its epilogue (naf_xna_mse_args, which embeds naf_xna_args unchanged); and after those naf_davis_jf_select / naf_davis_jf --
  * the integer counts behind the DAVIS J and F measures of two label-map sequences (naf_davis_jf_args); and after those naf_mask_labels_select /
  * naf_mask_labels / naf_nearest_resize_table -- a propagated frame's soft masks to the label map the reference writes to disk (naf_mask_labels_args);
- * and after those naf_xna_points -- the attention's scores, weights and features at N query pixels (naf_xna_points_args). */
+ * and after those naf_xna_points -- the attention's scores, weights and features at N query pixels (naf_xna_points_args); and after that
+ * naf_propagate_plan -- the kernel instance, key blocks, buffering and LDS naf_propagate_fwd chooses (host-only, naf_propagate_args unchanged). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -666,6 +667,10 @@ int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream);
  * Served: C % 32 == 0 and 32 <= C <= 1024, 1 <= K <= 64, 1 <= topk <= 16, 1 <= radius <= 15, 1 <= n <= 16, any h, w >= 1 (h * w * max(C, K)
  * below 2^31 elements per frame); anything else that is well formed is NAF_ERR_UNSUPPORTED with the limit named in naf_last_error().
  * radius = 0 is the reference's "no mask", the dense case: not served.  No atomics: the output is bit-reproducible from run to run.
+ * Every point of that range launches: the key rows stream through LDS double-buffered where two halo rows fit in 160 KiB beside the
+ * (K + 1) * 512 bytes of sums, single-buffered where they do not (which therefore depends on C, radius AND K: C = 768, radius = 15 is
+ * double-buffered at K <= 27 and single-buffered above; C = 1024 is single-buffered from radius = 1 at K = 64), and the largest request
+ * (C = 1024, radius = 15, K = 64) takes 132 544 bytes.  naf_propagate_plan names the choice.
  * naf_propagate_select is a host-only query (it reads the scalar fields only and touches no device): NAF_OK, NAF_ERR_UNSUPPORTED or
  * NAF_ERR_INVALID (NULL args, non-positive sizes, negative radius, temperature not > 0, non-zero reserved).  naf_propagate_fwd additionally
  * refuses NULL or misaligned pointers.  Caller-owned memory and stream; capturable; no workspace. */
@@ -683,6 +688,12 @@ typedef struct naf_propagate_args {
 } naf_propagate_args;
 int naf_propagate_select(const naf_propagate_args* a);
 int naf_propagate_fwd(const naf_propagate_args* a, naf_stream_t stream);
+/* What naf_propagate_fwd would launch for these scalar fields (added after naf_xna_points; detect by symbol).  Host-only like
+ * naf_propagate_select, whose status it returns (NAF_ERR_INVALID also for a NULL `out`); on NAF_OK out = {KSMAX, nkb, nbuf, LDS bytes}:
+ * the kernel instantiation's query fragments (4, 8, 12, 16, 24 or 32: the smallest that holds C / 32), the 16-key blocks per halo row
+ * (ceil((16 + 2 radius) / 16)), 2 where two halo rows fit in 160 KiB of LDS beside the sums (double-buffered) and 1 where they do not, and
+ * the dynamic LDS of the launch.  The launch takes its choices from the same function. */
+int naf_propagate_plan(const naf_propagate_args* a, int32_t out[4]);
 /* inv[p] = 1 / max(sqrt(sum_c x[p][c]^2), 1e-12) from an fp32 sum of squares.  x: bf16 dense channels-last [h, w, C], 16-byte aligned,
  * C % 8 == 0; inv: fp32 [h, w].  NAF_ERR_INVALID on NULL / misaligned pointers or non-positive sizes. */
 int naf_feature_inv_norm(const void* x, float* inv, int32_t h, int32_t w, int32_t C, naf_stream_t stream);

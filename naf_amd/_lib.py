@@ -353,6 +353,7 @@ SIGNATURES = {
     "naf_xna_head_cm_fwd": (C.c_int, [C.POINTER(XnaHeadCMArgs), C.c_void_p]),
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
+    "naf_propagate_plan": (C.c_int, [C.POINTER(PropagateArgs), C.POINTER(C.c_int32)]),
     "naf_feature_inv_norm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]),
     "naf_denoise_workspace_bytes": (C.c_size_t, [C.POINTER(DenoiseArgs)]),
     "naf_denoise_objective": (C.c_int, [C.POINTER(DenoiseArgs), C.c_void_p]),

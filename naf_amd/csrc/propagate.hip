@@ -254,27 +254,46 @@ int launch_ks(const PropParams& p, size_t lds, int grid, hipStream_t s) {
 
 }  // namespace
 
-static int naf_launch_propagate(const naf_propagate_args* a, hipStream_t s) {
-    PropParams p;
-    p.a = *a;
-    p.nkb = (PT_W + 2 * a->radius + 15) / 16;
-    p.kstride = 2 * a->C + 16;
-    p.nbuf = prop_lds(a, p.nkb, p.kstride, 2) <= (size_t)PROP_LDS_MAX ? 2 : 1;
-    p.tiles_x = (a->w + PT_W - 1) / PT_W;
-    p.inv_t = 1.f / a->temperature;
-    const size_t lds = prop_lds(a, p.nkb, p.kstride, p.nbuf);
-    if (lds > (size_t)PROP_LDS_MAX) {
-        naf_set_error("naf_propagate_fwd: %zu bytes of LDS needed, %d available", lds, PROP_LDS_MAX);
+// The launch's choices from the scalar fields alone (host only): naf_propagate_plan reports them, naf_launch_propagate takes them from here.
+struct PropPlan {
+    int ksmax, nkb, kstride, nbuf;
+    size_t lds;
+};
+
+static int prop_plan(const naf_propagate_args* a, PropPlan* pl) {
+    pl->nkb = (PT_W + 2 * a->radius + 15) / 16;
+    pl->kstride = 2 * a->C + 16;
+    pl->nbuf = prop_lds(a, pl->nkb, pl->kstride, 2) <= (size_t)PROP_LDS_MAX ? 2 : 1;
+    pl->lds = prop_lds(a, pl->nkb, pl->kstride, pl->nbuf);
+    if (pl->lds > (size_t)PROP_LDS_MAX) {
+        naf_set_error("naf_propagate_fwd: %zu bytes of LDS needed, %d available", pl->lds, PROP_LDS_MAX);
         return NAF_ERR_UNSUPPORTED;
     }
-    const int64_t grid = (int64_t)p.tiles_x * ((a->h + PT_H - 1) / PT_H);
     const int nks = a->C / 32;
-    if (nks <= 4) return launch_ks<4>(p, lds, (int)grid, s);
-    if (nks <= 8) return launch_ks<8>(p, lds, (int)grid, s);
-    if (nks <= 12) return launch_ks<12>(p, lds, (int)grid, s);
-    if (nks <= 16) return launch_ks<16>(p, lds, (int)grid, s);
-    if (nks <= 24) return launch_ks<24>(p, lds, (int)grid, s);
-    return launch_ks<32>(p, lds, (int)grid, s);
+    pl->ksmax = nks <= 4 ? 4 : nks <= 8 ? 8 : nks <= 12 ? 12 : nks <= 16 ? 16 : nks <= 24 ? 24 : 32;
+    return NAF_OK;
+}
+
+static int naf_launch_propagate(const naf_propagate_args* a, hipStream_t s) {
+    PropPlan pl;
+    const int rc = prop_plan(a, &pl);
+    if (rc != NAF_OK) return rc;
+    PropParams p;
+    p.a = *a;
+    p.nkb = pl.nkb;
+    p.kstride = pl.kstride;
+    p.nbuf = pl.nbuf;
+    p.tiles_x = (a->w + PT_W - 1) / PT_W;
+    p.inv_t = 1.f / a->temperature;
+    const int64_t grid = (int64_t)p.tiles_x * ((a->h + PT_H - 1) / PT_H);
+    switch (pl.ksmax) {
+        case 4: return launch_ks<4>(p, pl.lds, (int)grid, s);
+        case 8: return launch_ks<8>(p, pl.lds, (int)grid, s);
+        case 12: return launch_ks<12>(p, pl.lds, (int)grid, s);
+        case 16: return launch_ks<16>(p, pl.lds, (int)grid, s);
+        case 24: return launch_ks<24>(p, pl.lds, (int)grid, s);
+        default: return launch_ks<32>(p, pl.lds, (int)grid, s);
+    }
 }
 
 static int naf_launch_inv_norm(const void* x, float* inv, int h, int w, int C, hipStream_t s) {
@@ -316,6 +335,17 @@ int naf_propagate_select(const naf_propagate_args* a) {
     const int64_t per = (int64_t)a->h * a->w * (a->C > a->K ? a->C : a->K);
     PROP_SERVED(per < ((int64_t)1 << 31) && (int64_t)((a->w + PT_W - 1) / PT_W) * ((a->h + PT_H - 1) / PT_H) < ((int64_t)1 << 31),
                 "naf_propagate: h * w * max(C, K) = %lld is not served: below 2^31 elements per frame", (long long)per);
+    return NAF_OK;
+}
+
+int naf_propagate_plan(const naf_propagate_args* a, int32_t out[4]) {
+    const int rc = naf_propagate_select(a);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(out != nullptr, "naf_propagate_plan: out is NULL");
+    PropPlan pl;
+    const int prc = prop_plan(a, &pl);
+    if (prc != NAF_OK) return prc;
+    out[0] = pl.ksmax; out[1] = pl.nkb; out[2] = pl.nbuf; out[3] = (int32_t)pl.lds;
     return NAF_OK;
 }
 

@@ -1999,6 +1999,18 @@ def propagate_labels(target, context, segs, radius: int = 12, topk: int = 5, tem
     return out
 
 
+def propagate_plan(n: int, C_: int, h: int, w: int, K: int, radius: int = 12, topk: int = 5, temperature: float = 0.1) -> Dict[str, int]:
+    """What ``propagate_labels`` launches for these sizes (``naf_propagate_plan``, host only): ``ksmax`` the kernel instantiation's query
+    fragments, ``nkb`` the 16-key blocks per halo row, ``nbuf`` 2 for the double-buffered key stream and 1 for the single buffer, ``lds``
+    the launch's LDS bytes.  ``ValueError`` outside the served range, as ``propagate_labels`` raises it."""
+    a = _lib.PropagateArgs()
+    a.n, a.C, a.h, a.w, a.K, a.radius, a.topk, a.temperature = int(n), int(C_), int(h), int(w), int(K), int(radius), int(topk), float(temperature)
+    out = (C.c_int32 * 4)()
+    if _lib.load().naf_propagate_plan(C.byref(a), out) != 0:
+        raise ValueError(f"naf_amd.propagate_plan: {_lib.last_error()}")
+    return dict(zip(("ksmax", "nkb", "nbuf", "lds"), (int(v) for v in out)))
+
+
 # ---- DAVIS J and F measures (evaluation/eval_video_seg.py:145-269) --------------------------------------------------------------------
 DavisJF = collections.namedtuple("DavisJF", ("J", "F", "counts"))
 

@@ -56,7 +56,107 @@ def test_matches_the_reference_on_unambiguous_pixels(dev, ci):
     assert float(err[ok].max()) <= bound
 
 
+@pytest.mark.parametrize("li", [pytest.param(i, id=R.LIMIT_IDS[i]) for i in range(len(R.LIMIT_CASES))])
+def test_matches_the_reference_at_the_limits_of_the_served_range(dev, li):
+    """LIMIT_CASES: every propagate_kernel<KSMAX>, the single-buffered key stream, topk = 16, K = 64, n = 16, kept sets above the 16 list
+    slots, grids of exactly one tile and thinner than one (tests/test_propagate_cpu.py reads from naf_propagate_plan what each launches).
+    The bound is the one above with one more term, propagate_reference.gpu_bound:
+        |out - ref| <= 2 * (delta_s / T + 2^-20 + kept_max * 2^-24) * max|segs|
+    on every non-ambiguous pixel, kept_max the reference's own largest kept set: the fp32 additions of kept_max terms, which the "handful"
+    of the 2^-20 does not cover where ties keep dozens.  The lattice cases have no ambiguous pixel, so every pixel is compared."""
+    import naf_amd
+    n, C, h, w, r, topk, K, features = R.LIMIT_CASES[li]
+    (target, context, segs), (ref, ambiguous, kept) = R.limit_reference(li)
+    out = naf_amd.propagate_labels(target.to(dev), [f.to(dev) for f in context], segs.to(dev), radius=r, topk=topk, temperature=R.TEMPERATURE)
+    assert out.shape == (1, K, h, w) and out.dtype == torch.float32
+    share = float(ambiguous.double().mean())
+    assert share <= R.MAX_AMBIGUOUS_SHARE and (features != "lattice" or share == 0.0)
+    bound = R.gpu_bound(C, int(kept.max()), float(segs.abs().max()))
+    err = (out.double().cpu() - ref).abs().amax(1)[0]
+    ok = ~ambiguous
+    worst = float(err[ok].max())
+    print(f"{R.LIMIT_IDS[li]}: max err {worst:.3e} / bound {bound:.3e} = {worst / bound:.1e} on {int(ok.sum())} pixels; "
+          f"kept sets up to {int(kept.max())}; excluded {100 * share:.2f} %")
+    assert bool(torch.isfinite(out).all())
+    assert worst <= bound
+
+
 # ---- B. exact checks that need no reference -----------------------------------------------------------------------------
+EMBED_BASE = (2, 64, 19, 27, 3, 5, 4)                 # n, C, h, w, radius, topk, K: lattice features with all 64 channels live (m = 64)
+
+
+def _embed_inputs():
+    n, C, h, w, _, _, K = EMBED_BASE
+    g = torch.Generator().manual_seed(9)
+    target = R.lattice_features(C, h, w, g)
+    context = [R.lattice_features(C, h, w, g) for _ in range(n)]
+    return target, context, R.make_labels(n, K, h, w, g)
+
+
+def _embedded(x, C, seed):
+    """The 64 channels of x at 64 random (sorted or not: a dot product does not care) positions among C, zeros elsewhere; one placement per
+    (C, seed), shared by the target and every context frame."""
+    pos = torch.randperm(C, generator=torch.Generator().manual_seed(seed))[: x.shape[0]]
+    y = torch.zeros(C, *x.shape[1:], dtype=x.dtype)
+    y[pos] = x
+    return y
+
+
+@pytest.fixture(scope="module")
+def embed_base(dev):
+    import naf_amd
+    target, context, segs = _embed_inputs()
+    _, _, _, _, r, topk, _ = EMBED_BASE
+    out = naf_amd.propagate_labels(target.to(dev), [f.to(dev) for f in context], segs.to(dev), radius=r, topk=topk)
+    ref, ambiguous, kept = R.windowed(target, context, segs, radius=r, topk=topk)
+    assert int(ambiguous.sum()) == 0 and int(kept.max()) > topk                  # exact ties: the kept sets matter
+    assert float((out.double().cpu() - ref).abs().max()) <= R.gpu_bound(64, int(kept.max()), float(segs.max()))
+    return target, context, segs, out
+
+
+@pytest.mark.parametrize("C", [160, 256, 416, 512, 544, 768, 800, 1024])
+def test_channel_embedding_leaves_every_bit_unchanged(dev, embed_base, C):
+    """The base's 64 live channels placed at random positions among C, the same for the target and every context frame, zeros elsewhere:
+    the sums of squares, the integer dot products and therefore every score are exactly the base's, whichever instantiation runs and
+    whichever registers hold the query fragments, so the output must be the base's bit for bit.  No reference, no tolerance."""
+    import naf_amd
+    from naf_amd import ops
+    target, context, segs, base = embed_base
+    n, _, h, w, r, topk, K = EMBED_BASE
+    assert ops.propagate_plan(n, C, h, w, K, radius=r, topk=topk)["ksmax"] == {160: 8, 256: 8, 416: 16, 512: 16, 544: 24, 768: 24, 800: 32, 1024: 32}[C]
+    out = naf_amd.propagate_labels(_embedded(target, C, C).to(dev), [_embedded(f, C, C).to(dev) for f in context], segs.to(dev), radius=r, topk=topk)
+    assert torch.equal(out, base), f"C = {C}: {int((out != base).sum())} of {out.numel()} values differ, max |diff| {float((out - base).abs().max()):.3e}"
+
+
+def test_channel_embedding_through_the_single_buffer(dev, embed_base):
+    """The same at C = 1024 with K = 64 -- the four label maps followed by 60 zero channels -- which the plan runs single-buffered: the
+    first four output channels are the base's bit for bit and the rest exactly 0."""
+    import naf_amd
+    from naf_amd import ops
+    target, context, segs, base = embed_base
+    n, _, h, w, r, topk, K = EMBED_BASE
+    assert ops.propagate_plan(n, 1024, h, w, 64, radius=r, topk=topk)["nbuf"] == 1
+    wide = torch.cat([segs, torch.zeros(n, 64 - K, h, w)], 1)
+    out = naf_amd.propagate_labels(_embedded(target, 1024, 1).to(dev), [_embedded(f, 1024, 1).to(dev) for f in context], wide.to(dev), radius=r, topk=topk)
+    assert out.shape == (1, 64, h, w)
+    assert torch.equal(out[:, :K], base), f"{int((out[:, :K] != base).sum())} values differ, max |diff| {float((out[:, :K] - base).abs().max()):.3e}"
+    assert torch.equal(out[:, K:], torch.zeros_like(out[:, K:]))
+
+
+def test_a_frame_propagated_from_itself_returns_its_labels_at_every_limit(dev):
+    """As below at C = 1024, K = 64, radius 15 on 17 x 33 (KSMAX 32, single-buffered, three key blocks): the only kept candidate is the pixel
+    itself, and 1 * seg / 1 is exact for soft label maps too."""
+    import naf_amd
+    from naf_amd import ops
+    g = torch.Generator().manual_seed(10)
+    C, h, w, K = 1024, 17, 33, 64
+    assert ops.propagate_plan(1, C, h, w, K, radius=15, topk=1) == dict(ksmax=32, nkb=3, nbuf=1, lds=132544)
+    feats = torch.randn(C, h, w, generator=g).to(torch.bfloat16).to(dev)
+    segs = torch.rand(1, K, h, w, generator=g).to(dev)
+    out = naf_amd.propagate_labels(feats, [feats], segs, radius=15, topk=1)
+    assert torch.equal(out, segs)
+
+
 def test_a_frame_propagated_from_itself_returns_its_labels(dev):
     """Context = the target frame, n = 1, topk = 1: the only kept candidate is the pixel itself (cosine 1 against random neighbours), its
     weight is exp(0) = 1, and 1 * seg / 1 is exact."""
@@ -69,14 +169,10 @@ def test_a_frame_propagated_from_itself_returns_its_labels(dev):
     assert torch.equal(out[0], segs)
 
 
-@pytest.mark.parametrize("r", [1, 12, 15])
-def test_window_reaches_exactly_its_corner(dev, r):
-    """Context = the target rolled by (+r, -r): the source of target pixel (i, j) is context pixel (i + r, j - r), the corner of its
-    window.  Where that lies inside the image the output is the rolled label map bit for bit (topk = 1); with radius r - 1 the corner is
-    out of reach and some such pixel must differ."""
+def _window_reaches_exactly_its_corner(dev, r, C):
     import naf_amd
     g = torch.Generator().manual_seed(4)
-    C, h, w, K = 32, 35, 41, 4
+    h, w, K = 35, 41, 4
     feats = torch.randn(C, h, w, generator=g).to(torch.bfloat16)
     labels = torch.randint(0, K, (h, w), generator=g)
     ctx = torch.roll(feats, shifts=(r, -r), dims=(1, 2)).to(dev)
@@ -90,6 +186,20 @@ def test_window_reaches_exactly_its_corner(dev, r):
     if r > 1:
         short = naf_amd.propagate_labels(feats.to(dev), [ctx], segs[None], radius=r - 1, topk=1)
         assert not torch.equal(short[0][:, inside], expect[:, inside])
+
+
+@pytest.mark.parametrize("r", [1, 12, 15])
+def test_window_reaches_exactly_its_corner(dev, r):
+    """Context = the target rolled by (+r, -r): the source of target pixel (i, j) is context pixel (i + r, j - r), the corner of its
+    window.  Where that lies inside the image the output is the rolled label map bit for bit (topk = 1); with radius r - 1 the corner is
+    out of reach and some such pixel must differ."""
+    _window_reaches_exactly_its_corner(dev, r, 32)
+
+
+@pytest.mark.parametrize("r", [1, 12, 15])
+def test_window_reaches_exactly_its_corner_at_1024_channels(dev, r):
+    """The same through propagate_kernel<32> (double-buffered at r = 1, single-buffered at r = 11, 12, 14 and 15)."""
+    _window_reaches_exactly_its_corner(dev, r, 1024)
 
 
 def test_outputs_are_convex_combinations_and_reproducible(dev):

@@ -14,8 +14,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import propagate_reference as R  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SYMBOLS = ("naf_propagate_select", "naf_propagate_fwd", "naf_feature_inv_norm")
+SYMBOLS = ("naf_propagate_select", "naf_propagate_fwd", "naf_propagate_plan", "naf_feature_inv_norm")
 CASE_PARAMS = [pytest.param(i, id=R.CASE_IDS[i]) for i in range(len(R.CASES))]
+LIMIT_PARAMS = [pytest.param(i, id=R.LIMIT_IDS[i]) for i in range(len(R.LIMIT_CASES))]
 
 
 # ---- the yardstick ------------------------------------------------------------------------------------------------
@@ -48,6 +49,108 @@ def test_ambiguous_share_of_every_gpu_case_is_within_the_cap(ci):
     share = float(ambiguous.double().mean())
     print(f"{R.CASE_IDS[ci]}: ambiguous share {100 * share:.2f} % ({int(ambiguous.sum())} of {ambiguous.numel()} pixels)")
     assert share <= R.MAX_AMBIGUOUS_SHARE
+
+
+# ---- the limits of the served range -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("li", LIMIT_PARAMS)
+def test_limit_case_forms_agree_and_ambiguous_share_is_within_the_cap(li):
+    """Every LIMIT_CASES entry: the dense form equals the windowed form to 1e-12, and the ambiguous share is within the same 3 % cap --
+    exactly 0 on the lattice cases, whose scores are multiples of 1 / m >= 1 / 1024 (propagate_reference.lattice_features)."""
+    case = R.LIMIT_CASES[li]
+    n, C_, h, w, r, topk, K, features = case
+    (target, context, segs), (out, ambiguous, kept) = R.limit_reference(li)
+    ref = R.dense(target, context, segs, radius=r, topk=topk)
+    assert out.shape == ref.shape == (1, K, h, w)
+    err = float((out - ref).abs().max())
+    share = float(ambiguous.double().mean())
+    print(f"{R.LIMIT_IDS[li]}: max |dense - windowed| = {err:.3e}; kept set sizes {int(kept.min())} .. {int(kept.max())}; "
+          f"ambiguous share {100 * share:.2f} %")
+    assert err <= 1e-12
+    assert share <= R.MAX_AMBIGUOUS_SHARE
+    if n * min(h, r + 1) * min(w, r + 1) < topk:
+        assert int(kept[0, 0]) == n * min(h, r + 1) * min(w, r + 1)      # a corner: fewer candidates than topk, every one of them kept
+    if features == "lattice":
+        assert int(ambiguous.sum()) == 0
+        m = R.lattice_m(C_)
+        for x in [target, *context]:
+            assert x.dtype == torch.bfloat16 and set(x.float().unique().tolist()) <= {-1.0, 0.0, 1.0}
+            assert bool((x.float().abs().sum(0) == m).all())                                    # exactly m live channels per pixel
+            assert bool((x.float().abs().reshape(C_ // 32, 32, h, w).sum(1) > 0).all())         # every 32-channel chunk of every pixel is live
+        s = torch.einsum("chw,nchw->nhw", target.double(), torch.stack(context).double())       # same-position scores times m: integers
+        assert bool((s == s.round()).all()) and float(s.abs().max()) <= m <= 1024
+    if K == 1:
+        assert float(segs.max() - segs.min()) > 0.5                      # not the constant 1 a normalisation over K = 1 would give
+
+
+def test_lattice_m_is_the_largest_power_of_four():
+    assert [R.lattice_m(c) for c in (32, 63, 64, 160, 255, 256, 416, 512, 768, 800, 1023, 1024)] == [16, 16, 64, 64, 64, 256, 256, 256, 256, 256, 256, 1024]
+    assert {R.lattice_m(c[1]) for c in R.LIMIT_CASES if c[7] == "lattice"} == {16, 64, 256, 1024}
+
+
+def _case_args(case):
+    from naf_amd import _lib
+    a = _lib.PropagateArgs()
+    a.n, a.C, a.h, a.w, a.radius, a.topk, a.K = case[:7]
+    a.temperature = R.TEMPERATURE
+    return a
+
+
+def test_the_cases_reach_every_kernel_instance_and_both_key_streams(built_lib):
+    """Coverage read from the library (naf_propagate_plan, which the launch takes its choices from), not from a copied formula: CASES and
+    LIMIT_CASES together launch every propagate_kernel<KSMAX>, the single-buffered key stream at KSMAX 24 and 32 with 2 and with 3 key
+    blocks, and the double-buffered one at KSMAX 32.  A change of the LDS budget or of the dispatch that moves a case fails here."""
+    from naf_amd import _lib, ops
+    lib = _lib.load()
+    plans = []
+    for case in list(R.CASES) + list(R.LIMIT_CASES):
+        out = (C.c_int32 * 4)()
+        assert lib.naf_propagate_plan(C.byref(_case_args(case)), out) == 0, (case, _lib.last_error())
+        ksmax, nkb, nbuf, lds = (int(v) for v in out)
+        n, C_, h, w, r, topk, K = case[:7]
+        assert ops.propagate_plan(n, C_, h, w, K, radius=r, topk=topk) == dict(ksmax=ksmax, nkb=nkb, nbuf=nbuf, lds=lds)
+        assert C_ // 32 <= ksmax and nkb * 16 >= 16 + 2 * r > (nkb - 1) * 16 and nbuf in (1, 2) and 0 < lds <= 160 * 1024
+        print(f"{case}: KSMAX {ksmax}, nkb {nkb}, nbuf {nbuf}, LDS {lds}")
+        plans.append((ksmax, nkb, nbuf))
+    assert {p[0] for p in plans} == {4, 8, 12, 16, 24, 32}
+    assert (24, 3, 1) in plans                                            # single buffer at KSMAX 24
+    assert {(32, 2, 1), (32, 3, 1)} <= set(plans)                         # single buffer at KSMAX 32, with 2 and with 3 key blocks
+    assert any(p[0] == 32 and p[2] == 2 for p in plans)                   # double buffer at KSMAX 32
+    assert {p[1] for p in plans if p[2] == 1} >= {2, 3}
+
+
+GPU_BOUND_DEFECTS = ("exactly_topk", "drop_last_chunk", "stale_row0")
+WIDE_LATTICE = [i for i, c in enumerate(R.LIMIT_CASES) if c[7] == "lattice" and c[1] >= 416]
+
+
+def _defect_error(li, defect):
+    case = R.LIMIT_CASES[li]
+    (target, context, segs), (ref, ambiguous, kept) = R.limit_reference(li)
+    bad = R.windowed_with_defect(defect, target, context, segs, radius=case[4], topk=case[5])
+    err = float((bad - ref).abs().amax(1)[0][~ambiguous].max())
+    bound = R.gpu_bound(case[1], int(kept.max()), float(segs.abs().max()))
+    print(f"{R.LIMIT_IDS[li]}: {defect} moves the output by {err:.3e}; GPU bound {bound:.3e}; largest kept set {int(kept.max())}")
+    return err, bound
+
+
+@pytest.mark.parametrize("defect", GPU_BOUND_DEFECTS)
+@pytest.mark.parametrize("li", [pytest.param(i, id=R.LIMIT_IDS[i]) for i in WIDE_LATTICE])
+def test_wide_lattice_cases_tell_a_planted_defect_from_the_reference(li, defect):
+    """Sensitivity of the yardstick: a kernel that kept exactly topk instead of all ties, lost the target's last 32-channel fragment, or
+    multiplied image row 0 of a frame against the previous frame's keys would miss the GPU test's bound on EVERY lattice case with
+    C >= 416 (the instantiations and the single-buffered stream no other case launches)."""
+    assert len(WIDE_LATTICE) == 7
+    err, bound = _defect_error(li, defect)
+    assert err > bound
+
+
+def test_cases_with_large_kept_sets_tell_a_kept_set_cut_at_the_list_size():
+    """Pass 2 keeps every tie, however many: on each limit case whose largest kept set exceeds the 16 list slots, cutting the kept set at
+    16 misses the GPU bound.  There are at least three such cases (n = 16, topk = 16 at C = 512, and the all-limits case)."""
+    large = [i for i in range(len(R.LIMIT_CASES)) if int(R.limit_reference(i)[1][2].max()) > 16]
+    assert {R.LIMIT_CASES[i][:2] for i in large} >= {(16, 32), (2, 512), (3, 1024)}
+    for li in large:
+        err, bound = _defect_error(li, "cut_at_16")
+        assert err > bound
 
 
 # ---- validation -----------------------------------------------------------------------------------------------------
@@ -181,3 +284,39 @@ def test_select_is_a_host_only_policy(built_lib):
     assert lib.naf_propagate_select(C.byref(a)) == 1 and "reserved" in _lib.last_error()
     # a served geometry with NULL pointers: refused by the launch entry before anything touches a device
     assert lib.naf_propagate_fwd(C.byref(_args()), None) == 1 and "NULL" in _lib.last_error()
+
+
+def test_plan_is_a_host_only_query_with_selects_status(built_lib):
+    """naf_propagate_plan reads the scalar fields only (every pointer here is NULL) and returns what naf_propagate_select returns; on NAF_OK
+    it fills {KSMAX, nkb, nbuf, LDS bytes}, otherwise it leaves `out` alone."""
+    from naf_amd import _lib, ops
+    lib = _lib.load()
+    untouched = (C.c_int32 * 4)(-7, -7, -7, -7)
+    assert lib.naf_propagate_plan(None, None) == 1 and "NULL" in _lib.last_error()
+    assert lib.naf_propagate_plan(None, untouched) == 1 and "NULL" in _lib.last_error()
+    assert lib.naf_propagate_plan(C.byref(_args()), None) == 1 and "out is NULL" in _lib.last_error()
+    for kw, rc, text in ((dict(C=40), 2, "C % 32 == 0"), (dict(C=1056), 2, "C <= 1024"), (dict(K=65), 2, "K <= 64"), (dict(topk=17), 2, "topk <= 16"),
+                         (dict(radius=16), 2, "radius <= 15"), (dict(radius=0), 2, "dense"), (dict(n=17), 2, "n <= 16"),
+                         (dict(h=1 << 15, w=1 << 15), 2, "2^31"), (dict(n=0), 1, "n"), (dict(K=0), 1, "K"), (dict(radius=-1), 1, "radius"),
+                         (dict(temperature=0.0), 1, "temperature")):
+        a = _args(**kw)
+        assert lib.naf_propagate_plan(C.byref(a), untouched) == rc == lib.naf_propagate_select(C.byref(a)), kw
+        assert text in _lib.last_error(), (kw, _lib.last_error())
+    a = _args()
+    a.reserved[0] = 1
+    assert lib.naf_propagate_plan(C.byref(a), untouched) == 1 and "reserved" in _lib.last_error()
+    assert list(untouched) == [-7, -7, -7, -7]
+    # the benchmarked setting, worked out by hand: 384 / 32 = 12 fragments; 16 + 24 = 40 keys -> 3 blocks; sums 128 * (8 + 1) * 4 = 4608 bytes,
+    # per buffer 48 inverse norms (192 bytes) and 48 keys of 2 * 384 + 16 = 784 bytes (37632): two buffers fit, 4608 + 2 * 37824 = 80256
+    out = (C.c_int32 * 4)()
+    assert lib.naf_propagate_plan(C.byref(_args()), out) == 0 and list(out) == [12, 3, 2, 80256]
+    # the largest request of the served range, single-buffered: 128 * 65 * 4 + 192 + 48 * 2064
+    assert lib.naf_propagate_plan(C.byref(_args(C=1024, K=64, radius=15, topk=16, n=16)), out) == 0 and list(out) == [32, 3, 1, 132544]
+    # every corner of the served range launches (the plan never exceeds the 160 KiB it sizes the buffers for)
+    for C_ in (32, 1024):
+        for K in (1, 64):
+            for r in (1, 15):
+                assert lib.naf_propagate_plan(C.byref(_args(C=C_, K=K, radius=r)), out) == 0 and 0 < out[3] <= 160 * 1024
+    assert ops.propagate_plan(8, 384, 34, 61, 8, radius=12, topk=5) == dict(ksmax=12, nkb=3, nbuf=2, lds=80256)
+    with pytest.raises(ValueError, match="radius <= 15"):
+        ops.propagate_plan(8, 384, 34, 61, 8, radius=16)
