@@ -72,7 +72,8 @@ extern "C" {
  * the integer counts behind the DAVIS J and F measures of two label-map sequences (naf_davis_jf_args); and after those naf_mask_labels_select /
  * naf_mask_labels / naf_nearest_resize_table -- a propagated frame's soft masks to the label map the reference writes to disk (naf_mask_labels_args);
  * and after those naf_xna_points -- the attention's scores, weights and features at N query pixels (naf_xna_points_args); and after that
- * naf_propagate_plan -- the kernel instance, key blocks, buffering and LDS naf_propagate_fwd chooses (host-only, naf_propagate_args unchanged). */
+ * naf_propagate_plan -- the kernel instance, key blocks, buffering and LDS naf_propagate_fwd chooses (host-only, naf_propagate_args unchanged); and
+ * after that naf_image_prep_select / naf_image_prep -- resized, normalised views of one decoded frame from one launch (naf_image_prep_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -1223,6 +1224,73 @@ typedef struct naf_xna_points_args {
     int64_t v_stride[4];
 } naf_xna_points_args;
 int naf_xna_points(const naf_xna_points_args* a, naf_stream_t stream);
+
+/* ---- frame preparation: resized, normalised views of one image from one launch (added after the point queries; detect by symbol) ----
+ * Replaces the torch-eager work the reference's callers do before anything reaches the model: evaluation/eval_video_seg.py:577-597 (ToTensor,
+ * bilinear resize to a multiple of the patch size, two normalisations, bicubic resize of the upsampler's image), train.py:115-126 with
+ * utils/training.py:47 (bilinear resize, two normalisations, two bilinear resizes of the results), evaluation/eval_seg_probing.py:97-98 (two
+ * normalisations, a horizontal flip in training).  One call writes up to NAF_IMAGE_PREP_MAX_VIEWS derived images ("views") of ONE source; no
+ * intermediate image is written.
+ *
+ * A view is: first resize -> normalise -> second resize -> store.  Every step is optional.  All arithmetic is fp32 and every operation is
+ * rounded on its own (no fused multiply-add); fl() below is that rounding.
+ *   source value   NAF_IMAGE_PREP_U8: fl(float(u) / 255), a correctly rounded divide (ToTensor on the host); NAF_F32: the value as it is;
+ *                  NAF_BF16: widened.  With hflip, source column x reads column W - 1 - x.
+ *   resize n_in -> n_out, per axis (align_corners = False, no antialiasing): scale = fl(float(n_in) / float(n_out)),
+ *                  real = fl(fl(scale * fl(dst + 0.5)) - 0.5) -- ATen's DEVICE arithmetic, as for naf_preshrink_image.
+ *     NAF_PREP_BILINEAR  src = max(real, 0), i0 = (int)src, i1 = min(i0 + 1, n_in - 1), l1 = fl(src - i0), l0 = fl(1 - l1);
+ *                  value = h0 * (w0 * v00 + w1 * v01) + h1 * (w0 * v10 + w1 * v11), each product and sum rounded, in this order.
+ *     NAF_PREP_BICUBIC   (ATen's, A = -0.75) i = floor(real), t = fl(real - i), u = fl(1 - t);
+ *                  c1(x) = (((A + 2) x - (A + 3)) x) x + 1, c2(x) = ((A x - 5A) x + 8A) x - 4A, each operation rounded (1.25, 2.25, -3.75, -6,
+ *                  -3 are exact); the weights [c2(fl(t + 1)), c1(t), c1(u), c2(fl(u + 1))] go on taps i - 1 .. i + 2, every tap index clamped
+ *                  into [0, n_in - 1] (2 - t is taken as (1 - t) + 1, as ATen does).  Row pass first: ((v0 cx0 + v1 cx1) + v2 cx2) + v3 cx3,
+ *                  left to right; then the same form with the y weights over the four row results.
+ *     NAF_PREP_NONE      the sizes must be equal and the value passes through.
+ *                  An equal-size bilinear or bicubic resize returns the value exactly for finite inputs.
+ *   normalise      fl(fl(v - mean[c]) / std[c]), the divide correctly rounded (no reciprocal); mean and std are the caller's fp32 values.
+ *                  normalise = 0 skips the step (it is not "subtract 0").  std[c] == 0 is NAF_ERR_INVALID.
+ *   second resize  reads the normalised first-stage image exactly as if that fp32 image had been written to memory; it is not written.
+ *   store          NAF_F32 as it is; NAF_BF16 rounded to nearest even.
+ * Operands:
+ *   src          device; 3 channels of B images of H x W; src_stride = ELEMENTS between images, channels, rows, columns (any values: an HWC
+ *                uint8 frame is {H*W*3, 1, W*3, 3}, a CHW tensor {3*H*W, H*W, W, 1}, a crop of either keeps the parent's strides)
+ *   view[i].out  device; [B][3][h2][w2] through out_stride = elements between images, channels, rows, columns; nothing outside the
+ *                B x 3 x h2 x w2 elements those strides address is written.  Views must not overlap each other or the source.
+ *   (h1, w1, mode1) the first resize H x W -> h1 x w1; (h2, w2, mode2) the second h1 x w1 -> h2 x w2, which is the view's size
+ * One launch on the caller's stream: a flat list of 256-pixel workgroups over the views' output pixels, a thread per output pixel and its
+ * three channels; pure gather -- no workspace, no atomics, no host synchronisation -- so two runs give the same bits.
+ * Served: 1 <= n_views <= NAF_IMAGE_PREP_MAX_VIEWS, every size 1 .. NAF_IMAGE_PREP_MAX_SIZE, B >= 1 with B * h2 * w2 < 2^31 per view and fewer
+ * than 2^31 workgroups in all; anything else that is well formed is NAF_ERR_UNSUPPORTED with the limit named in naf_last_error().
+ * naf_image_prep_select is a host-only query (it reads the scalar fields only and touches no device): NAF_OK, NAF_ERR_UNSUPPORTED or
+ * NAF_ERR_INVALID (NULL args, n_views, B or a size < 1, an unknown dtype or mode, NAF_PREP_NONE between different sizes, std == 0 or NaN
+ * statistics on a normalised view, non-zero reserved).  naf_image_prep additionally refuses NULL pointers and pointers not aligned to their
+ * element (4 bytes for fp32, 2 for bf16).  Caller-owned memory and stream; nothing is allocated; capturable. */
+#define NAF_IMAGE_PREP_MAX_VIEWS 4
+#define NAF_IMAGE_PREP_MAX_SIZE 16384
+#define NAF_IMAGE_PREP_U8 3 /* src_dtype only: uint8, value u / 255 */
+enum naf_prep_mode { NAF_PREP_NONE = 0, NAF_PREP_BILINEAR = 1, NAF_PREP_BICUBIC = 2 };
+typedef struct naf_image_prep_view {
+    void* out;
+    int64_t out_stride[4]; /* elements between images, channels, rows, columns */
+    int32_t out_dtype;     /* NAF_F32 or NAF_BF16 */
+    int32_t h1, w1, mode1;
+    int32_t normalise;
+    int32_t h2, w2, mode2;
+    float mean[3];
+    float std[3];
+    int32_t reserved[2]; /* must be 0 */
+} naf_image_prep_view;
+typedef struct naf_image_prep_args {
+    const void* src;
+    int64_t src_stride[4]; /* elements between images, channels, rows, columns */
+    int32_t src_dtype;     /* NAF_IMAGE_PREP_U8, NAF_F32 or NAF_BF16 */
+    int32_t B, H, W;
+    int32_t hflip, n_views;
+    int32_t reserved[2]; /* must be 0 */
+    naf_image_prep_view view[NAF_IMAGE_PREP_MAX_VIEWS];
+} naf_image_prep_args;
+int naf_image_prep_select(const naf_image_prep_args* a);
+int naf_image_prep(const naf_image_prep_args* a, naf_stream_t stream);
 
 #ifdef __cplusplus
 }

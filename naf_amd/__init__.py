@@ -15,10 +15,12 @@ from .ops import ConfusionMetrics, FrameFeatures, confusion_metrics, pack_frame,
 from .ops import DenoisingLoss, denoising_loss, denoising_metrics  # noqa: F401
 from .ops import DavisJF, davis_jf, davis_statistics  # noqa: F401
 from .ops import VideoTracker, labels_to_masks, masks_to_labels, nearest_index_table  # noqa: F401
+from .ops import PrepView, davis_frame_views, lr_image_size, prepare_views, probing_views, training_views  # noqa: F401
 from .feature_pca import FeaturePCA, pca  # noqa: F401
 
 __all__ = ["NAF", "CrossAttention", "GraphedForward", "Guidance", "PointQuery", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics",
            "FrameFeatures", "pack_frame", "propagate_labels", "DenoisingLoss", "denoising_loss", "denoising_metrics",
            "FeaturePCA", "pca", "DavisJF", "davis_jf", "davis_statistics",
-           "VideoTracker", "labels_to_masks", "masks_to_labels", "nearest_index_table"]
+           "VideoTracker", "labels_to_masks", "masks_to_labels", "nearest_index_table",
+           "PrepView", "prepare_views", "davis_frame_views", "training_views", "probing_views", "lr_image_size"]
 __version__ = "0.1.0"

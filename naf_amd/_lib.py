@@ -134,6 +134,27 @@ class XnaPointsArgs(C.Structure):
     ]
 
 
+IMAGE_PREP_MAX_VIEWS, IMAGE_PREP_MAX_SIZE, IMAGE_PREP_U8 = 4, 16384, 3      # NAF_IMAGE_PREP_*
+PREP_NONE, PREP_BILINEAR, PREP_BICUBIC = 0, 1, 2                          # naf_prep_mode
+
+
+class ImagePrepView(C.Structure):
+    """naf_image_prep_view: one derived image of naf_image_prep -- first resize, normalise, second resize, store."""
+    _fields_ = [
+        ("out", C.c_void_p), ("out_stride", I64x4), ("out_dtype", C.c_int32), ("h1", C.c_int32), ("w1", C.c_int32), ("mode1", C.c_int32),
+        ("normalise", C.c_int32), ("h2", C.c_int32), ("w2", C.c_int32), ("mode2", C.c_int32),
+        ("mean", C.c_float * 3), ("std", C.c_float * 3), ("reserved", C.c_int32 * 2),
+    ]
+
+
+class ImagePrepArgs(C.Structure):
+    """naf_image_prep_args (added after the point queries, detected by symbol): up to four views of one source image from one launch."""
+    _fields_ = [
+        ("src", C.c_void_p), ("src_stride", I64x4), ("src_dtype", C.c_int32), ("B", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+        ("hflip", C.c_int32), ("n_views", C.c_int32), ("reserved", C.c_int32 * 2), ("view", ImagePrepView * IMAGE_PREP_MAX_VIEWS),
+    ]
+
+
 DENOISE_LOSS, DENOISE_METRICS = 0, 1            # naf_denoise_mode
 
 
@@ -372,6 +393,8 @@ SIGNATURES = {
     "naf_mask_labels": (C.c_int, [C.POINTER(MaskLabelsArgs), C.c_void_p]),
     "naf_nearest_resize_table": (C.c_int, [C.POINTER(C.c_int32), C.c_int32, C.c_int32]),
     "naf_xna_points": (C.c_int, [C.POINTER(XnaPointsArgs), C.c_void_p]),
+    "naf_image_prep_select": (C.c_int, [C.POINTER(ImagePrepArgs)]),
+    "naf_image_prep": (C.c_int, [C.POINTER(ImagePrepArgs), C.c_void_p]),
     "naf_xna_bwd_supported": (C.c_int, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_workspace_bytes": (C.c_size_t, [C.POINTER(XnaBwdArgs)]),
     "naf_xna_bwd_chunk_plan": (C.c_int, [C.POINTER(XnaBwdArgs), C.POINTER(C.c_int32), C.c_int]),

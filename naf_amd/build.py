@@ -32,7 +32,9 @@ NO_VGPR_FORM = {"stem_conv.hip"}
 # vectoriser would pack adjacent ones again.  denoise.hip: its fused multiply-adds are written out; with the compiler's own contraction
 # off, expressions that are symmetric in pred and target round symmetrically (the SSIM gradient of identical windows is exactly zero).
 # mask_labels.hip: its two passes must round the upsampled value identically, so the compiler contracts nothing there either.
-EXTRA_FLAGS = {"stem_conv.hip": ["-fno-slp-vectorize"], "denoise.hip": ["-ffp-contract=off"], "mask_labels.hip": ["-ffp-contract=off"]}
+# image_prep.hip: its values are defined operation by operation (include/naf_hip.h), and the tests ask for those bits.
+EXTRA_FLAGS = {"stem_conv.hip": ["-fno-slp-vectorize"], "denoise.hip": ["-ffp-contract=off"], "mask_labels.hip": ["-ffp-contract=off"],
+               "image_prep.hip": ["-ffp-contract=off"]}
 # Instance sources -> the (window, half) instances they are compiled for (half None: the family has one value type).  The lists are
 # NAF_FOR_WINDOWS / NAF_FOR_SLIDE_WINDOWS of naf_common.h.
 _WINDOWS, _SLIDE_WINDOWS = (3, 5, 7, 9, 11, 13, 15), (7, 9, 11, 13, 15)

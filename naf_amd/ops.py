@@ -15,6 +15,8 @@ Reference counterparts (paths relative to the reference repo):
   davis_jf / davis_statistics  davis_db_eval_iou, davis_db_eval_boundary, davis_db_statistics  evaluation/eval_video_seg.py:145-269
   masks_to_labels / labels_to_masks / VideoTracker  the upsample, norm_mask, argmax and PIL resize of a propagated frame; read_seg + to_one_hot;
                      the queue of eval_video_tracking_davis                 evaluation/eval_video_seg.py:389-457,488-496,611-643
+  prepare_views / PrepView / davis_frame_views / training_views / probing_views  the resizes and normalisations in front of the model
+                     evaluation/eval_video_seg.py:577-597, train.py:115-126, utils/training.py:24-47, evaluation/eval_seg_probing.py:97-98
   denoising_loss     DenoisingLoss.forward and its backward               denoising.py:129-177
   denoising_metrics  MetricsCalculator.calculate_batch_metrics            denoising.py:61-126,302
   feature_moments / pca_project / pca_minmax  pca() and TorchPCA          utils/visualization.py:135-190
@@ -2343,6 +2345,178 @@ class VideoTracker:
                 self._queue.popleft()
             self._queue.append((tgt, seg))
         return masks_to_labels(seg, self.mid_size, self.out_size, out=out)
+
+
+# ---- frame preparation: the resizes and normalisations in front of the model (eval_video_seg.py:577-597, train.py:115-126) ---------------
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)       # the upsampler's statistics everywhere in the reference
+_PREP_MODE = {None: _lib.PREP_NONE, "bilinear": _lib.PREP_BILINEAR, "bicubic": _lib.PREP_BICUBIC}
+
+
+class PrepView:
+    """One derived image of ``prepare_views``: first resize, normalise, second resize, store -- every step optional.
+
+        size, mode   the first resize, to ``size = (h, w)`` with ``mode`` ``"bilinear"`` / ``"bicubic"`` (``align_corners=False``, no
+                     antialiasing); ``size=None`` keeps the source's size, ``mode=None`` is no resize (the sizes must then be equal)
+        mean, std    three values each: ``(v - mean) / std`` per channel; both ``None``: the step is skipped
+        then         ``((h, w), mode)``: the second resize, of the normalised image; ``None``: none
+        dtype        ``torch.float32`` or ``torch.bfloat16`` of the result
+        out          an existing ``[B, 3, h, w]`` tensor of that dtype (any strides) to write instead of a new one
+    """
+    __slots__ = ("size", "mode", "mean", "std", "then", "dtype", "out")
+
+    def __init__(self, size=None, mode=None, mean=None, std=None, then=None, dtype=torch.float32, out=None):
+        self.size, self.mode, self.mean, self.std, self.then, self.dtype, self.out = size, mode, mean, std, then, dtype, out
+
+    def __repr__(self):
+        return (f"PrepView(size={self.size!r}, mode={self.mode!r}, mean={self.mean!r}, std={self.std!r}, then={self.then!r}, "
+                f"dtype={self.dtype}, out={'given' if self.out is not None else None})")
+
+
+def _prep_mode(mode, who: str) -> int:
+    if not (mode is None or isinstance(mode, str)) or mode not in _PREP_MODE:
+        raise ValueError(f"naf_amd.{who}: a resize mode is 'bilinear', 'bicubic' or None, got {mode!r}")
+    return _PREP_MODE[mode]
+
+
+def _prep_stats(v, who: str, name: str):
+    try:
+        vals = [float(x) for x in (v.tolist() if torch.is_tensor(v) else v)]
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"naf_amd.{who}: `{name}` must be three numbers, got {v!r}") from e
+    if len(vals) != 3:
+        raise ValueError(f"naf_amd.{who}: `{name}` must be three numbers (one per channel), got {len(vals)}")
+    return vals
+
+
+def prepare_views(src: torch.Tensor, views, hflip: bool = False):
+    """Every resized, normalised image the reference's callers derive from one decoded frame or batch, in ONE kernel launch: no
+    intermediate image, no host synchronisation, and the frame may stay the uint8 it was decoded as.
+
+    ``src`` is ``torch.uint8`` ``[H, W, 3]`` / ``[B, H, W, 3]`` (its value is ``u / 255``, ``ToTensor``), or ``torch.float32`` /
+    ``torch.bfloat16`` ``[3, H, W]`` / ``[B, 3, H, W]``, with any strides (a crop, a channels-last tensor), on a ROCm device.  ``views`` is a
+    sequence of 1 .. 4 ``PrepView``; ``hflip=True`` mirrors the source's columns first.  Returns a list with one ``[B, 3, h, w]`` tensor per view
+    (dense unless the view names ``out=``).  The arithmetic is ATen's device arithmetic in fp32, every operation rounded on its own, stated
+    in include/naf_hip.h (naf_image_prep): the second resize reads the normalised first-stage image as if it had been stored in fp32.
+
+    Served: every size 1 .. 16384, fewer than 2^31 output pixels per view.  A CPU tensor raises ``RuntimeError``; anything else not served
+    raises ``ValueError`` with the library's message.  There is no torch fallback."""
+    who = "prepare_views"
+    if not torch.is_tensor(src):
+        raise ValueError(f"naf_amd.{who}: `src` must be a tensor, got {type(src).__name__}")
+    if src.dtype == torch.uint8:
+        if src.dim() not in (3, 4) or src.shape[-1] != 3:
+            raise ValueError(f"naf_amd.{who}: a uint8 `src` must be [H, W, 3] or [B, H, W, 3] (3 channels last), got {tuple(src.shape)}")
+        s4 = src if src.dim() == 4 else src[None]
+        s4 = s4.permute(0, 3, 1, 2)
+        dt = _lib.IMAGE_PREP_U8
+    elif src.dtype in _DT:
+        if src.dim() not in (3, 4) or src.shape[-3] != 3:
+            raise ValueError(f"naf_amd.{who}: a {src.dtype} `src` must be [3, H, W] or [B, 3, H, W] (3 channels), got {tuple(src.shape)}")
+        s4 = src if src.dim() == 4 else src[None]
+        dt = _DT[src.dtype]
+    else:
+        raise ValueError(f"naf_amd.{who}: `src` must be uint8, float32 or bfloat16, got {src.dtype}")
+    try:
+        views = list(views)
+    except TypeError as e:
+        raise ValueError(f"naf_amd.{who}: `views` must be a sequence of PrepView") from e
+    if any(not isinstance(v, PrepView) for v in views):
+        raise ValueError(f"naf_amd.{who}: `views` must be a sequence of PrepView")
+    a = _lib.ImagePrepArgs()
+    a.src_dtype, a.hflip, a.n_views = dt, int(bool(hflip)), len(views)
+    a.B, a.H, a.W = int(s4.shape[0]), int(s4.shape[2]), int(s4.shape[3])
+    shapes = []
+    for i, v in enumerate(views[:_lib.IMAGE_PREP_MAX_VIEWS]):
+        q = a.view[i]
+        if v.dtype not in _DT:
+            raise ValueError(f"naf_amd.{who}: view {i}: dtype must be torch.float32 or torch.bfloat16, got {v.dtype}")
+        q.out_dtype = _DT[v.dtype]
+        q.mode1 = _prep_mode(v.mode, who)
+        q.h1, q.w1 = (a.H, a.W) if v.size is None else _size2(v.size, who, "size")
+        if v.then is None:
+            q.h2, q.w2, q.mode2 = q.h1, q.w1, _lib.PREP_NONE
+        else:
+            try:
+                size2, mode2 = v.then
+            except (TypeError, ValueError) as e:
+                raise ValueError(f"naf_amd.{who}: view {i}: `then` must be ((h, w), mode), got {v.then!r}") from e
+            (q.h2, q.w2), q.mode2 = _size2(size2, who, "then"), _prep_mode(mode2, who)
+        if (v.mean is None) != (v.std is None):
+            raise ValueError(f"naf_amd.{who}: view {i}: give both `mean` and `std`, or neither")
+        if v.mean is not None:
+            q.normalise = 1
+            q.mean = (C.c_float * 3)(*_prep_stats(v.mean, who, "mean"))       # rounded to fp32 here, once
+            q.std = (C.c_float * 3)(*_prep_stats(v.std, who, "std"))
+        shapes.append((a.B, 3, int(q.h2), int(q.w2)))
+    lib = _lib.load()
+    if lib.naf_image_prep_select(C.byref(a)) != 0:              # host only: the limits live in one place, the library
+        raise ValueError(f"naf_amd.{who}: {_lib.last_error()}")
+    _gpu(src, "src")
+    dev = src.device
+    for i, (v, shape) in enumerate(zip(views, shapes)):
+        if v.out is None:
+            continue
+        if not torch.is_tensor(v.out) or v.out.dtype != v.dtype or tuple(v.out.shape) != shape:
+            raise ValueError(f"naf_amd.{who}: view {i}: `out` must be a {v.dtype} tensor of shape {shape}, got "
+                             f"{getattr(v.out, 'dtype', type(v.out).__name__)} {tuple(getattr(v.out, 'shape', ()))}")
+        if v.out.device != dev:
+            raise ValueError(f"naf_amd.{who}: view {i}: `out` is on {v.out.device}, `src` on {dev}")
+    with torch.cuda.device(dev):
+        s4 = s4.detach()
+        a.src = s4.data_ptr()
+        a.src_stride = _strides4(s4, (0, 1, 2, 3))
+        res = []
+        for i, (v, shape) in enumerate(zip(views, shapes)):
+            t = v.out.detach() if v.out is not None else torch.empty(shape, dtype=v.dtype, device=dev)
+            a.view[i].out = t.data_ptr()
+            a.view[i].out_stride = _strides4(t, (0, 1, 2, 3))
+            res.append(v.out if v.out is not None else t)
+        with _Timed("image_prep"):
+            rc = lib.naf_image_prep(C.byref(a), _stream(s4))
+        _lib.check(rc, "naf_image_prep")
+    return res
+
+
+def lr_image_size(H: int, W: int, factor: float, ps: int) -> Tuple[int, int]:
+    """The size of the training step's low-res pass: the reference's ``round_to_nearest_multiple(v * factor, ps)`` per axis
+    (utils/training.py:24-25, 44-46), with Python's ``round`` (halves go to the even multiple)."""
+    return ps * round(H * factor / ps), ps * round(W * factor / ps)
+
+
+def davis_frame_views(frame_hw, ps: int, ups_factor: int, backbone_mean, backbone_std):
+    """The two images ``extract_feature`` derives from a decoded DAVIS frame (evaluation/eval_video_seg.py:579-595), as views for
+    ``prepare_views``.  Returns ``(views, lr_grid, hr_size)``: the frame goes bilinearly to ``(H // ps * ps, W // ps * ps)``; ``views[0]`` is that
+    image with the backbone's statistics; ``views[1]`` is it with the upsampler's (ImageNet) statistics, then bicubically at
+    ``hr_size = lr_grid * ups_factor``, ``lr_grid = (H // ps, W // ps)`` being the backbone's feature grid."""
+    H, W = _size2(frame_hw, "davis_frame_views", "frame_hw")
+    lr_grid = (H // ps, W // ps)
+    first = (lr_grid[0] * ps, lr_grid[1] * ps)
+    hr_size = (lr_grid[0] * ups_factor, lr_grid[1] * ups_factor)
+    views = [PrepView(first, "bilinear", backbone_mean, backbone_std),
+             PrepView(first, "bilinear", IMAGENET_MEAN, IMAGENET_STD, then=(hr_size, "bicubic"))]
+    return views, lr_grid, hr_size
+
+
+def training_views(img_size, hr_grid, lr_image_size, backbone_mean, backbone_std):
+    """The three images a training step derives from a batch (train.py:115-126, utils/training.py:47), as views for ``prepare_views``: the
+    batch bilinearly at ``img_size`` with the backbone's statistics; that image's bilinear shrink to ``lr_image_size`` (``lr_image_size()`` of
+    this module, or the configured ``lr_img_size``) for the low-res pass; the batch at ``img_size`` with the upsampler's (ImageNet) statistics,
+    then bilinearly at ``[min(224, 4 * v) for v in hr_grid]``, ``hr_grid`` being the backbone's feature grid at ``img_size``."""
+    who = "training_views"
+    size = (img_size, img_size) if isinstance(img_size, int) and not isinstance(img_size, bool) else _size2(img_size, who, "img_size")
+    lr = (lr_image_size, lr_image_size) if isinstance(lr_image_size, int) and not isinstance(lr_image_size, bool) else \
+        _size2(lr_image_size, who, "lr_image_size")
+    gh, gw = _size2(hr_grid, who, "hr_grid")
+    ups = (min(224, 4 * gh), min(224, 4 * gw))
+    return [PrepView(size, "bilinear", backbone_mean, backbone_std),
+            PrepView(size, "bilinear", backbone_mean, backbone_std, then=(lr, "bilinear")),
+            PrepView(size, "bilinear", IMAGENET_MEAN, IMAGENET_STD, then=(ups, "bilinear"))]
+
+
+def probing_views(backbone_mean, backbone_std):
+    """The two normalisations of the probing loops (evaluation/eval_seg_probing.py:97-98, 162-165), no resize: the backbone's image and the
+    upsampler's.  The horizontal flip of the training loop is ``prepare_views(..., hflip=True)``."""
+    return [PrepView(mean=backbone_mean, std=backbone_std), PrepView(mean=IMAGENET_MEAN, std=IMAGENET_STD)]
 
 
 # ---- denoising objective (denoising.py:61-177) ------------------------------------------------------------------------------------
