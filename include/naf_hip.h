@@ -73,7 +73,9 @@ extern "C" {
  * naf_mask_labels / naf_nearest_resize_table -- a propagated frame's soft masks to the label map the reference writes to disk (naf_mask_labels_args);
  * and after those naf_xna_points -- the attention's scores, weights and features at N query pixels (naf_xna_points_args); and after that
  * naf_propagate_plan -- the kernel instance, key blocks, buffering and LDS naf_propagate_fwd chooses (host-only, naf_propagate_args unchanged); and
- * after that naf_image_prep_select / naf_image_prep -- resized, normalised views of one decoded frame from one launch (naf_image_prep_args). */
+ * after that naf_image_prep_select / naf_image_prep -- resized, normalised views of one decoded frame from one launch (naf_image_prep_args); and
+ * after those naf_xna_cos_select / naf_xna_cos_fwd -- the attention with a cosine head folded in: scaled cosines between the upsampled feature
+ * and N embeddings, and the feature's norm (naf_xna_cos_args). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -444,7 +446,7 @@ int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t
                     const int64_t v_stride[4], naf_stream_t stream);
 
 /* ---- LAYOUT CONTRACT OF THE ATTENTION ENTRIES ------------------------------------------------------
- * naf_xna_fwd, naf_xna_head_fwd, naf_xna_head_ce_fwd, naf_xna_mse_fwd, naf_xna_bwd (and naf_xna_bwd_scores) take every 5-D operand as
+ * naf_xna_fwd, naf_xna_head_fwd, naf_xna_head_ce_fwd, naf_xna_cos_fwd, naf_xna_mse_fwd, naf_xna_bwd (and naf_xna_bwd_scores) take every 5-D operand as
  * a pointer plus four ELEMENT strides {b, head, y, x}; the last dim is contiguous.  Each stride of each operand is honoured on its own:
  * nothing is derived from another stride, from a size or from another operand, so dense head-major and channels-last buffers, gaps
  * between pixels, rows, heads or images, windows of a larger canvas, channel slices, a batch axis that is not the outermost, y stride <
@@ -468,7 +470,9 @@ int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t
  *   naf_xna_head_fwd / _ce_fwd   q, k_lr, pv_lr (and dlogits) not vectorisable: -NAF_ERR_UNSUPPORTED under AUTO and FUSED alike, the
  *                  caller composes naf_xna_fwd.  out, loss and labels are stored element by element: any alignment of their element
  *                  size, any strides {b, y, x} (out: x stride >= N).
- *   naf_xna_mse_fwd              the rules of NAF_XNA_UNION for q, k_lr, v_lr and out (the gradient); otherwise -NAF_ERR_UNSUPPORTED. */
+ *   naf_xna_mse_fwd              the rules of NAF_XNA_UNION for q, k_lr, v_lr and out (the gradient); otherwise -NAF_ERR_UNSUPPORTED.
+ *   naf_xna_cos_fwd              as naf_xna_head_fwd, with v_lr held to the rule of q, k_lr and pv_lr; out and norms are stored element by
+ *                  element: 4-byte aligned, any strides {b, y, x} (out: x stride >= N). */
 
 /* ---- cross-scale neighbourhood attention forward -------------------------------------------------
  * Replaces legacy_attention (attentions.py:16-29: na2d_qk -> *scale -> softmax -> na2d_av), the fused
@@ -1291,6 +1295,61 @@ typedef struct naf_image_prep_args {
 } naf_image_prep_args;
 int naf_image_prep_select(const naf_image_prep_args* a);
 int naf_image_prep(const naf_image_prep_args* a, naf_stream_t stream);
+
+/* ---- attention with a COSINE head folded in (added after the image-preparation entries; detect by symbol) ------------
+ * Open-vocabulary segmentation and "click a pixel, see what looks like it" heat maps compare the upsampled feature of every pixel with N
+ * embeddings by their cosine (the reference normalises its upsampled maps the same way before comparing, evaluation/eval_video_seg.py:539-540).
+ * With E [N, C], E^ = its rows divided by max(||row||, 1e-12), f[px] the C channels of naf(V) at the pixel, head g owning channels
+ * [g*Dv, (g+1)*Dv):
+ *     out[n, px]  = logit_scale * (E^[n] . f[px]) / max(||f[px]||_2, 1e-12)
+ *     norms[px]   = ||f[px]||_2                                                       (fp32, unclamped)
+ * A linear head cannot give this: the norm is quadratic in the attention's output.  The numerator is the head identity of
+ * naf_xna_head_fwd on pv_lr = E^[:, g*Dv:(g+1)*Dv] @ V_g (no bias); for the denominator the kernel forms f_g = P_g . V_g on the matrix
+ * cores from the SAME bf16 weights P_g, adds the squares of its fp32 results per pixel and drops them.  The [B, C, Ho, Wo] tensor is never
+ * written.  A pixel whose feature is zero gets exactly 0 for every n (never NaN) and norm 0.
+ *   q, k_lr   as in naf_xna_args (bf16, strides {b, head, y, x}, last dim contiguous, Dq = 64)
+ *   pv_lr     device bf16 [B, heads, h, w, Npad] as for naf_xna_head_fwd, formed from the NORMALISED rows E^ (the caller normalises)
+ *   v_lr      device bf16 [B, heads, h, w, Dv], strides v_stride {b, head, y, x}, last dim contiguous: the values pv_lr was formed from
+ *   out       device float [B, Ho, Wo, N], element strides o_stride {b, y, x}, channel axis contiguous
+ *   norms     device float [B, Ho, Wo], element strides norms_stride {b, y, x}, or NULL
+ *   rope_tab_y / rope_tab_x   rotate-on-load exactly as in naf_xna_args (q is then the un-rotated channels-last guidance)
+ *   logit_scale   multiplies the cosine, used as given (a zero-initialised struct yields zeros: set it, 1 for plain cosines); finite
+ *   scale     the softmax scale; <= 0 selects Dq^-0.5
+ * Kernel (xna_cos_kernel.h): naf_xna_head_fwd's -- one workgroup per (batch, low-res cell) loops over the heads, each head's softmax is
+ * normalised in fp32 before its weights are rounded to bf16, the heads add up in fp32 -- with the head's value window staged next to
+ * the K and PV windows in chunks of 64 channels.  No atomics: every output is deterministic, bit for bit.  A power-of-two factor on
+ * the values changes no bit of out and scales norms exactly.
+ * Served: the geometries of naf_xna_head_fwd (square odd window 3 .. 15, Dq = 64, integer ratio whose cell rows are row tiles, h, w >=
+ * window, any head count, 1 <= N <= 256), Dv a multiple of 16, 16-byte aligned q / k_lr / pv_lr / v_lr with strides that are multiples
+ * of 8 elements -- EXCEPT windows 13 and 15 with N > 64 (those instantiations would spill registers or exceed the LDS).
+ * naf_xna_cos_select: NAF_XNA_HEAD_FUSED when naf_xna_cos_fwd serves the arguments, else a negative naf_status (with naf_last_error):
+ * -NAF_ERR_INVALID for arguments no kernel could serve (NULL, N outside 1 .. 256, even window, non-finite logit_scale, non-zero reserved
+ * ...), -NAF_ERR_UNSUPPORTED for a valid request outside the list above -- the caller then normalises the output of naf_xna_fwd.  A pure
+ * host-side query: pointers are checked, never read.  path: naf_xna_head_path (the same answer for both today).  The struct must be
+ * zero-initialised.  Caller-owned memory and stream; capturable; no workspace. */
+typedef struct naf_xna_cos_args {
+    const void* q;
+    const void* k_lr;
+    const void* pv_lr;
+    const void* v_lr;
+    float* out;
+    float* norms; /* or NULL */
+    const float* rope_tab_y;
+    const float* rope_tab_x;
+    int32_t B, heads, Ho, Wo, h, w, Dq, Dv, N, ky, kx;
+    int32_t path; /* naf_xna_head_path */
+    float scale;
+    float logit_scale;
+    int32_t reserved[2]; /* must be 0 */
+    int64_t q_stride[4];
+    int64_t k_stride[4];
+    int64_t pv_stride[4];
+    int64_t v_stride[4];
+    int64_t o_stride[3];
+    int64_t norms_stride[3];
+} naf_xna_cos_args;
+int naf_xna_cos_select(const naf_xna_cos_args* a);
+int naf_xna_cos_fwd(const naf_xna_cos_args* a, naf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -74,6 +74,18 @@ class XnaHeadCMArgs(C.Structure):
     _fields_ = [("ce", XnaHeadCEArgs), ("confusion", C.c_void_p), ("cm_stride", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
+class XnaCosArgs(C.Structure):
+    """naf_xna_cos_args (added after the image-preparation entries, detected by symbol): the attention with a cosine head folded in."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k_lr", C.c_void_p), ("pv_lr", C.c_void_p), ("v_lr", C.c_void_p), ("out", C.c_void_p), ("norms", C.c_void_p),
+        ("rope_tab_y", C.c_void_p), ("rope_tab_x", C.c_void_p),
+        ("B", C.c_int32), ("heads", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("Dq", C.c_int32), ("Dv", C.c_int32), ("N", C.c_int32), ("ky", C.c_int32), ("kx", C.c_int32),
+        ("path", C.c_int32), ("scale", C.c_float), ("logit_scale", C.c_float), ("reserved", C.c_int32 * 2),
+        ("q_stride", I64x4), ("k_stride", I64x4), ("pv_stride", I64x4), ("v_stride", I64x4), ("o_stride", I64x3), ("norms_stride", I64x3),
+    ]
+
+
 class XnaMSEArgs(C.Structure):
     """naf_xna_mse_args (added after the PCA entries, detected by symbol): naf_xna_args plus the regression target of the training objective."""
     _fields_ = [
@@ -372,6 +384,8 @@ SIGNATURES = {
     "naf_xna_head_ce_fwd": (C.c_int, [C.POINTER(XnaHeadCEArgs), C.c_void_p]),
     "naf_xna_head_cm_select": (C.c_int, [C.POINTER(XnaHeadCMArgs)]),
     "naf_xna_head_cm_fwd": (C.c_int, [C.POINTER(XnaHeadCMArgs), C.c_void_p]),
+    "naf_xna_cos_select": (C.c_int, [C.POINTER(XnaCosArgs)]),
+    "naf_xna_cos_fwd": (C.c_int, [C.POINTER(XnaCosArgs), C.c_void_p]),
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
     "naf_propagate_plan": (C.c_int, [C.POINTER(PropagateArgs), C.POINTER(C.c_int32)]),

@@ -44,6 +44,7 @@ INSTANCES = {
     "xna_union_inst.hip": [(k, h) for h in (0, 1) for k in _WINDOWS],
     "xna_union_mse_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_head_inst.hip": [(k, None) for k in _WINDOWS],
+    "xna_cos_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_bwd_inst.hip": [(k, None) for k in _WINDOWS],
 }
 

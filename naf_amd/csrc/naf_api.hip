@@ -481,6 +481,37 @@ int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream) {
     return naf_launch_xna_head_cm(a, xna_scale(a->ce.head.scale, a->ce.head.Dq), static_cast<hipStream_t>(stream));
 }
 
+// ---- the cosine head: scaled cosines between the upsampled feature and N embeddings (after the image-preparation entries) ----
+static int xna_cos_validate(const naf_xna_cos_args* a) {
+    NAF_REQUIRE(a != nullptr, "naf_xna_cos_fwd: args is NULL");
+    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && a->v_lr && a->out, "naf_xna_cos_fwd: NULL tensor pointer");
+    const int rc = xna_geometry_validate("naf_xna_cos_fwd", a, a->Dv);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(a->N >= 1 && a->N <= 256, "naf_xna_cos_fwd: N must be in 1 .. 256, got %d", a->N);
+    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "naf_xna_cos_fwd: path %d", a->path);
+    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_cos_fwd: rope_tab_y and rope_tab_x must be given together");
+    NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "naf_xna_cos_fwd: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)",
+                (long long)a->pv_stride[3], a->N);
+    NAF_REQUIRE(a->v_stride[3] >= a->Dv, "naf_xna_cos_fwd: v_lr x stride %lld smaller than Dv %d", (long long)a->v_stride[3], a->Dv);
+    NAF_REQUIRE(a->o_stride[2] >= a->N, "naf_xna_cos_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
+    NAF_REQUIRE(reinterpret_cast<uintptr_t>(a->out) % 4 == 0 && reinterpret_cast<uintptr_t>(a->norms) % 4 == 0, "naf_xna_cos_fwd: out / norms not 4-byte aligned");
+    NAF_REQUIRE(a->logit_scale == a->logit_scale && a->logit_scale - a->logit_scale == 0.f, "naf_xna_cos_fwd: logit_scale must be finite");
+    NAF_REQUIRE(a->reserved[0] == 0 && a->reserved[1] == 0, "naf_xna_cos_fwd: reserved fields must be 0");
+    return NAF_OK;
+}
+
+int naf_xna_cos_select(const naf_xna_cos_args* a) {
+    int rc = xna_cos_validate(a);
+    if (rc == NAF_OK) rc = naf_xna_cos_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
+}
+
+int naf_xna_cos_fwd(const naf_xna_cos_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_cos_select(a);
+    if (sel < 0) return -sel;
+    return naf_launch_xna_cos(a, xna_scale(a->scale, a->Dq), static_cast<hipStream_t>(stream));
+}
+
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_bwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->dout && a->dq && a->dk_lr && a->dv_lr, "naf_xna_bwd: NULL tensor pointer");

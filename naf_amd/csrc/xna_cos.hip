@@ -1,0 +1,70 @@
+// Eligibility test + dispatcher for the cosine-head MFMA cell kernel (see xna_cos_kernel.h).
+#include "xna_cos_kernel.h"
+
+// the instances: xna_cos_inst.hip, one object per window
+#define NAF_X(K) NAF_XNA_COS_WINDOW(extern, K)
+NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
+
+// NAF_OK when the kernel serves the (validated) request; otherwise NAF_ERR_UNSUPPORTED with the reason in the error string.  The geometry
+// and layout rules are the head family's (naf_common.h): what naf_xna_head_select grants, this kernel is asked to serve.
+int naf_xna_cos_eligible(const naf_xna_cos_args* a) {
+    if (!xna_cell_shape_ok(a)) {   // which of its conditions (an even window never gets here: the entries refuse it)
+        const int ks = a->ky;
+        if (a->ky != a->kx || ks < 3 || ks > 15) naf_set_error("naf_xna_cos: the fused kernel needs a square window 3 .. 15 (got %dx%d)", a->ky, a->kx);
+        else if (a->Dq != 64) naf_set_error("naf_xna_cos: the fused kernel needs Dq = 64 (got %d)", a->Dq);
+        else if (a->h < ks || a->w < ks) naf_set_error("naf_xna_cos: the fused kernel needs h, w >= window (got %dx%d, window %d)", a->h, a->w, ks);
+        else naf_set_error("naf_xna_cos: the fused kernel needs an integer ratio (got %dx%d -> %dx%d)", a->h, a->w, a->Ho, a->Wo);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    const int dy = a->Ho / a->h, dx = a->Wo / a->w;
+    if (!xna_row_tiles_ok(dx) || (int64_t)dy * ((dx + 15) / 16) > 1024) {
+        naf_set_error("naf_xna_cos: the fused kernel needs row tiles (Wo/w a multiple of 16, or 14, 15, 28, 30 ...; at most 1024 tiles per cell; got %dx%d -> %dx%d)",
+                      a->h, a->w, a->Ho, a->Wo);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    if (a->Dv % 16 != 0) {
+        naf_set_error("naf_xna_cos: the fused kernel needs Dv a multiple of 16 (got %d)", a->Dv);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    if (!xna_cos_served(a->ky, xna_head_nct((a->N + 15) & ~15))) {
+        naf_set_error("naf_xna_cos: no fused kernel for window %d with N = %d (registers / LDS: the instantiation would spill)", a->ky, a->N);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    if (!xna_qkv_layout_ok(a, a->pv_lr, a->pv_stride) || !naf_aligned(a->v_lr, 16) ||
+        a->v_stride[0] % 8 || a->v_stride[1] % 8 || a->v_stride[2] % 8 || a->v_stride[3] % 8) {
+        if (!naf_aligned(a->q, 16) || !naf_aligned(a->k_lr, 16) || !naf_aligned(a->pv_lr, 16) || !naf_aligned(a->v_lr, 16))
+            naf_set_error("naf_xna_cos: the fused kernel needs 16-byte aligned q, k_lr, pv_lr, v_lr");
+        else naf_set_error("naf_xna_cos: the fused kernel needs q / k_lr / pv_lr / v_lr strides that are multiples of 8 elements");
+        return NAF_ERR_UNSUPPORTED;
+    }
+    return NAF_OK;
+}
+
+int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s) {
+    XnaCosParams p;
+    xna_fill_common(p, a, a->pv_stride, scale);
+    p.pv = static_cast<const bf16_t*>(a->pv_lr);
+    p.v = static_cast<const bf16_t*>(a->v_lr);
+    p.out = a->out;
+    p.tab_y = a->rope_tab_y; p.tab_x = a->rope_tab_x;
+    p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
+    p.N = a->N;
+    p.npad = (a->N + 15) & ~15;
+    p.dv = a->Dv;
+    for (int i = 0; i < 4; ++i) p.ws[i] = a->v_stride[i];
+    for (int i = 0; i < 3; ++i) p.os[i] = a->o_stride[i];
+    XnaCosEpilogue e;
+    e.norms = a->norms;
+    for (int i = 0; i < 3; ++i) e.ns[i] = a->norms != nullptr ? a->norms_stride[i] : 0;
+    e.logit_scale = a->logit_scale;
+    const int rc = xna_grid("naf_xna_cos_fwd", (int64_t)a->B * a->h * a->w, &p.nblocks);
+    if (rc != NAF_OK) return rc;
+    switch (a->ky) {
+#define NAF_X(K) case K: return xna_cos_launch_ks<K>(p, e, s);
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
+    }
+    naf_set_error("naf_xna_cos_fwd: kernel size %d has no instantiation", a->ky);
+    return NAF_ERR_UNSUPPORTED;
+}

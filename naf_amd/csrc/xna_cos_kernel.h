@@ -1,0 +1,381 @@
+// Cross-scale neighbourhood attention with a COSINE head folded in, head-summed MFMA cell kernel (gfx950 / CDNA4).
+//
+// out[b, y, x, n] = logit_scale * (sum_g sum_slot P_g[px, slot] * PV_g[cell(slot), n]) / max(||f[px]||, 1e-12)   (include/naf_hip.h: naf_xna_cos_args)
+// f[px] = the upsampled feature of the pixel, all heads' channels: f_g = sum_slot P_g[px, slot] * V_g[cell(slot), :].  PV_g = E^[:, g*Dv:(g+1)*Dv] @ V_g
+// is formed by the host on the low-res grid from the NORMALISED rows E^ of the embedding matrix; f is never written.
+//
+// The numerator is xna_head_kernel.h's logits kernel (read its header comment first): one workgroup (8 waves) = one (batch, low-res
+// cell), it loops over the heads, stages the head's K and PV windows in LDS, S^T = K . Q on v_mfma_f32_16x16x32_bf16, fp32 softmax over
+// the key slots, P normalised in fp32 BEFORE it is packed to bf16, O^T += PV^T . P^T with the accumulators kept across the heads;
+// rotate-on-load with naf_rope_rotate.  What the cosine adds is the DENOMINATOR:
+//   * the head's VALUE window is staged in LDS as well, in channel chunks of XNA_COS_DVC = 64 ([slots][64 (+16)] bf16; a chunk past Dv is
+//     zero-filled, its channel tiles are skipped).  Per chunk and 16-channel tile the wave forms F^T = V^T . P^T on the same MFMA with the
+//     SAME packed P as the numerator, adds the squares of the four fp32 results of the lane into ONE fp32 sum per tile of the wave (fmaf,
+//     fixed order) and drops them: P . V is never stored.  Chunks of a head and the heads themselves simply add.
+//   * a head of more than 64 value channels takes several chunks: chunk 0 is staged with the K and PV windows, every further chunk
+//     between two more barriers; the packed P of the wave's tiles is kept in registers across them.
+//   * after the head loop the lane's partial sum holds the channels grp*4 + r of every tile; the four lanes col + 16 * grp of a pixel are
+//     added with naf_rows_sum (the reduction the softmax over the key slots and the class softmax use; fixed order).
+//   * epilogue: nrm = sqrt(sum), inv = 1 / max(nrm, 1e-12), out = logit_scale * (acc * inv), channels >= N masked; norms (optional, NULL:
+//     a wave-uniform branch) receives nrm, fp32 and unclamped, from the pixel's grp = 0 lane.  A pixel whose window holds only zero
+//     features has acc = 0 and sum = 0: out = 0 * 1e12 = 0, never NaN.  sqrt and the divide are the correctly rounded ones.
+//   * no atomics, nothing crosses a workgroup: two launches give the same bits.
+//   * the epilogue's own arguments (XnaCosEpilogue) are the kernel's second argument and are read from the kernel-argument segment in the
+//     epilogue, behind an opaque address, as the classification epilogue of xna_head_kernel.h does: held across the head loop they cost
+//     scalar registers the loop does not have.
+// Which (window, channel tiles) instantiations exist and which of them the dispatcher serves is decided by the compiler's figures
+// (profiles/cosine_head.txt): xna_cos_served below.
+#pragma once
+#include "xna_head_kernel.h"
+
+struct XnaCosParams {
+    const bf16_t* q;
+    const bf16_t* k;
+    const bf16_t* pv;
+    const bf16_t* v;
+    float* out;
+    const float* tab_y;  // rotate-on-load: RoPE tables [Ho][2][16] / [Wo][2][16], or nullptr
+    const float* tab_x;
+    int32_t B, heads, Ho, Wo, h, w, dy, dx;
+    int32_t N;           // stored channels
+    int32_t npad;        // channels a pv row holds (N rounded up to 16)
+    int32_t dv;          // value channels of a head (a multiple of 16)
+    uint32_t nblocks;
+    float scale_log2e;
+    int64_t qs[4], ks[4], vs[4], ws[4];  // {b, head, y, x} element strides of q, k, pv, v
+    int64_t os[3];                       // {b, y, x}
+};
+// read in the epilogue only (see the header comment)
+struct XnaCosEpilogue {
+    float* norms;        // [B, Ho, Wo] by ns, or nullptr
+    int64_t ns[3];       // {b, y, x}
+    float logit_scale;
+};
+constexpr size_t XNA_COS_ARG_OFFSET = (sizeof(XnaCosParams) + alignof(XnaCosEpilogue) - 1) / alignof(XnaCosEpilogue) * alignof(XnaCosEpilogue);
+
+constexpr int XNA_COS_DVC = 64;   // value channels staged at a time
+constexpr size_t xna_cos_lds_for(int ks, int nct) { return (size_t)(ks * ks) * (72 + nct * 16 + 16 + XNA_COS_DVC + 16) * 2; }
+// 16-query tiles a wave carries through the head loop: the head kernel's two, and one where two tiles' accumulators, their packed P
+// (kept across the value chunks) and the window's scores spill (the compiler's figures: profiles/cosine_head.txt)
+constexpr int xna_cos_tpw(int ks, int nct) { return (xna_head_tpw(ks, nct) == 1 || ks >= 15 || (nct >= 10 && ks >= 9) || (nct >= 16 && ks >= 7)) ? 1 : 2; }
+// instantiated: the windows fit the 160 KB of LDS (15 x 15 with 16 channel tiles does not)
+constexpr bool xna_cos_fits(int ks, int nct) { return xna_cos_lds_for(ks, nct) <= 160 * 1024; }
+// served: instantiated and free of scratch.  13 x 13 and 15 x 15 with 10 or 16 channel tiles (N > 64) spill even with one tile per wave
+// (36 .. 260 bytes per lane): naf_xna_cos_select answers -NAF_ERR_UNSUPPORTED for them and the caller composes.
+// (tools/cosine_head_time.py --resources compiles with -DNAF_XNA_COS_ALL to put the figures of the excluded ones on record.)
+#ifdef NAF_XNA_COS_ALL
+constexpr bool xna_cos_served(int ks, int nct) { return xna_cos_fits(ks, nct); }
+#else
+constexpr bool xna_cos_served(int ks, int nct) { return xna_cos_fits(ks, nct) && !(ks >= 13 && nct >= 10); }
+#endif
+
+template <int KS, int NCT>
+__global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosParams p, const XnaCosEpilogue epi) {
+    constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
+    constexpr int TPW = xna_cos_tpw(KS, NCT);
+    using G = XnaGeom<KS, 1>;
+    constexpr int NSLOT = G::NSLOT, MT = G::MT, KST = G::KST, KROW = G::KROW;
+    constexpr int DVT = NCT * 16, VROW = XnaVRow<DVT>::VROW, VCH = DVT / 8;
+    constexpr int DVC = XNA_COS_DVC, WROW = XnaVRow<DVC>::VROW, WCH = DVC / 8;
+
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    bf16_t* Ks = reinterpret_cast<bf16_t*>(smem);
+    bf16_t* Vs = Ks + NSLOT * KROW;     // the PV window
+    bf16_t* Ws = Vs + NSLOT * VROW;     // a chunk of the value window
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int col = lane & 15;  // MFMA column (query within the tile) / A-row index (key or channel)
+    const int grp = lane >> 4;  // MFMA k-group / result row group
+
+    uint32_t L = xna_block_order(blockIdx.x, p.nblocks, 16, 1u);
+    const int cx = L % p.w;
+    L /= p.w;
+    const int cy = L % p.h;
+    const int b = L / p.h;
+    const int y0 = min(max(cy - KS / 2, 0), p.h - KS);   // the cell's clamped window
+    const int x0 = min(max(cx - KS / 2, 0), p.w - KS);
+
+    const int tpr = (p.dx + 15) >> 4;      // row tiles per cell row (host: xna_row_tiles_ok(dx))
+    const int ntile = p.dy * tpr;          // <= 1024 (host)
+    const uint32_t tmagic = (1u << 20) / (uint32_t)tpr + 1u;   // t / tpr for t, tpr <= 1024
+    const bool rope = p.tab_y != nullptr;
+    const int nchunk = (p.dv + DVC - 1) / DVC;
+    const bf16_t* q_cell = p.q + b * p.qs[0] + (int64_t)(cy * p.dy) * p.qs[2] + (int64_t)(cx * p.dx) * p.qs[3];
+    float* o_cell = p.out + b * p.os[0] + (int64_t)(cy * p.dy) * p.os[1] + (int64_t)(cx * p.dx) * p.os[2];
+    const bf16_t* kb = p.k + b * p.ks[0];
+    const bf16_t* vb = p.pv + b * p.vs[0];
+    const bf16_t* wb = p.v + b * p.ws[0];
+
+    // key slots >= NSLOT are not stored: their reads are clamped to the last real row, their logits masked, P = 0
+    auto ka_of = [&](int mt) __attribute__((always_inline)) {
+        const int row = (mt * 16 + 15 < NSLOT) ? mt * 16 + col : min(mt * 16 + col, NSLOT - 1);
+        return Ks + row * KROW + grp * 8;
+    };
+    auto va_row = [&](int blk) __attribute__((always_inline)) {
+        const int r = blk * 16 + grp * 4 + (col >> 2);
+        return (blk * 16 + 15 < NSLOT) ? r : min(r, NSLOT - 1);
+    };
+    // A-fragment (16 channels x 32 key slots) of a row-major [slots][ROW] window through the transposing LDS read
+    auto a_frag = [&](const bf16_t* win, int ROW, int ks, int c0) __attribute__((always_inline)) {
+        const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((NAF_LDS bf16x4_t*)(win + va_row(ks * 2) * ROW + (col & 3) * 4 + c0));
+        const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4bf16((NAF_LDS bf16x4_t*)(win + va_row(ks * 2 + 1) * ROW + (col & 3) * 4 + c0));
+        bf16x8_t a;
+        a[0] = lo[0]; a[1] = lo[1]; a[2] = lo[2]; a[3] = lo[3];
+        a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
+        return a;
+    };
+
+    for (int t0 = 0; t0 < ntile; t0 += NW * TPW) {
+        // this wave's tiles of the round: t0 + u * NW + wave (wave-uniform); a tile past the cell is computed on clamped
+        // addresses and never stored
+        int tyv[TPW], tx0v[TPW];
+        bool livev[TPW];
+        const bf16_t* qpv[TPW];
+        f32x4_t cs[TPW][4] = {};
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            const int tt = t0 + u * NW + wave;
+            livev[u] = tt < ntile;
+            const int ttc = min(tt, ntile - 1);
+            tyv[u] = (int)(((uint32_t)ttc * tmagic) >> 20);
+            tx0v[u] = (ttc - tyv[u] * tpr) * 16;
+            const int xl = min(tx0v[u] + col, p.dx - 1);   // lanes past a partial last tile re-read its last pixel
+            qpv[u] = q_cell + (int64_t)tyv[u] * p.qs[2] + (int64_t)xl * p.qs[3] + grp * 8;
+            if (rope) {
+                // head dims [grp*8, +8) and their partners +32: dims < 16 turn with the row angle, dims >= 16 with the column angle
+                const float* tr = ((grp >> 1) ? p.tab_x + (int64_t)(cx * p.dx + xl) * 32 : p.tab_y + (int64_t)(cy * p.dy + tyv[u]) * 32) + (grp & 1) * 8;
+                cs[u][0] = *reinterpret_cast<const f32x4_t*>(tr);
+                cs[u][1] = *reinterpret_cast<const f32x4_t*>(tr + 4);
+                cs[u][2] = *reinterpret_cast<const f32x4_t*>(tr + 16);
+                cs[u][3] = *reinterpret_cast<const f32x4_t*>(tr + 20);
+            }
+        }
+        f32x4_t acc[TPW][NCT];
+        float ssq[TPW];   // the lane's share of the pixel's squared norm: channels grp*4 + r of every 16-channel tile, all heads
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            ssq[u] = 0.f;
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) acc[u][ct] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        }
+
+        for (int head = 0; head < p.heads; ++head) {
+            // the head's queries are requested first: their latency hides under the window staging and the barrier
+            bf16x8_t qf[TPW][2];
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                const bf16_t* qp = qpv[u] + head * p.qs[1];
+                qf[u][0] = *reinterpret_cast<const bf16x8_t*>(qp);
+                qf[u][1] = *reinterpret_cast<const bf16x8_t*>(qp + 32);
+            }
+            bf16x8_t pf[TPW][KST];   // P of the wave's tiles, packed once per head, used by the numerator and by every value chunk
+            const bf16_t* wh = wb + head * p.ws[1];
+            for (int chunk = 0; chunk < nchunk; ++chunk) {
+                __syncthreads();   // every wave is done with the windows staged before
+                if (chunk == 0) {
+                    // ---- stage the K and PV windows (L2 -> registers -> LDS): all loads of a batch before its first LDS write
+                    const bf16_t* kh = kb + head * p.ks[1];
+                    const bf16_t* vh = vb + head * p.vs[1];
+                    constexpr int KTOT = NSLOT * 8, VTOT = NSLOT * VCH;
+                    constexpr int KIT = (KTOT + NT - 1) / NT, VIT = (VTOT + NT - 1) / NT;
+                    constexpr int BATCH = 8;
+                    const int vch_mem = p.npad >> 3;   // 16-byte chunks a pv row holds in memory; the rest of the LDS row is zero
+#pragma unroll
+                    for (int j0 = 0; j0 < KIT + VIT; j0 += BATCH) {
+                        u32x4_t val[BATCH];
+#pragma unroll
+                        for (int e = 0; e < BATCH; ++e) {
+                            const int j = j0 + e;
+                            if (j < KIT) {
+                                const int i = min(j * NT + tid, KTOT - 1);
+                                const int key = i >> 3, c = i & 7;
+                                const int ry = key / KS, rx = key - ry * KS;
+                                val[e] = *reinterpret_cast<const u32x4_t*>(kh + (int64_t)(y0 + ry) * p.ks[2] + (int64_t)(x0 + rx) * p.ks[3] + c * 8);
+                            } else if (j < KIT + VIT) {
+                                const int i = min((j - KIT) * NT + tid, VTOT - 1);
+                                const int key = i / VCH, c = i - key * VCH;
+                                const int ry = key / KS, rx = key - ry * KS;
+                                const u32x4_t ld = *reinterpret_cast<const u32x4_t*>(vh + (int64_t)(y0 + ry) * p.vs[2] + (int64_t)(x0 + rx) * p.vs[3] + min(c, vch_mem - 1) * 8);
+                                val[e] = c < vch_mem ? ld : u32x4_t{0u, 0u, 0u, 0u};
+                            }
+                        }
+#pragma unroll
+                        for (int e = 0; e < BATCH; ++e) {
+                            const int j = j0 + e;
+                            if (j < KIT) {
+                                const int i = j * NT + tid;
+                                if ((KTOT % NT == 0) || i < KTOT) *reinterpret_cast<u32x4_t*>(Ks + (i >> 3) * KROW + (i & 7) * 8) = val[e];
+                            } else if (j < KIT + VIT) {
+                                const int i = (j - KIT) * NT + tid;
+                                const int key = i / VCH, c = i - key * VCH;
+                                if ((VTOT % NT == 0) || i < VTOT) *reinterpret_cast<u32x4_t*>(Vs + key * VROW + c * 8) = val[e];
+                            }
+                        }
+                    }
+                }
+                const int c0 = chunk * DVC;
+                const int wch_mem = min(p.dv - c0, DVC) >> 3;   // 16-byte chunks of this value chunk that exist (>= 2); the rest of the LDS row is zero
+                {
+                    // ---- stage value channels [c0, c0 + 64) of the window ----
+                    constexpr int WTOT = NSLOT * WCH, WIT = (WTOT + NT - 1) / NT;
+                    u32x4_t val[WIT];
+#pragma unroll
+                    for (int j = 0; j < WIT; ++j) {
+                        const int i = min(j * NT + tid, WTOT - 1);
+                        const int key = i / WCH, c = i - key * WCH;
+                        const int ry = key / KS, rx = key - ry * KS;
+                        const u32x4_t ld = *reinterpret_cast<const u32x4_t*>(wh + (int64_t)(y0 + ry) * p.ws[2] + (int64_t)(x0 + rx) * p.ws[3] + c0 + min(c, wch_mem - 1) * 8);
+                        val[j] = c < wch_mem ? ld : u32x4_t{0u, 0u, 0u, 0u};
+                    }
+#pragma unroll
+                    for (int j = 0; j < WIT; ++j) {
+                        const int i = j * NT + tid;
+                        const int key = i / WCH, c = i - key * WCH;
+                        if ((WTOT % NT == 0) || i < WTOT) *reinterpret_cast<u32x4_t*>(Ws + key * WROW + c * 8) = val[j];
+                    }
+                }
+                __syncthreads();
+
+#pragma unroll
+                for (int u = 0; u < TPW; ++u) {
+                    if (!livev[u]) continue;   // wave-uniform
+                    if (chunk == 0) {
+                        if (rope) {
+#pragma unroll
+                            for (int i = 0; i < 8; ++i) {
+                                float o1, o2;
+                                naf_rope_rotate((float)qf[u][0][i], (float)qf[u][1][i], cs[u][i >> 2][i & 3], cs[u][2 + (i >> 2)][i & 3], o1, o2);
+                                qf[u][0][i] = (bf16_t)o1;
+                                qf[u][1][i] = (bf16_t)o2;
+                            }
+                        }
+                        // ---- S^T = K . Q^T: lane (col, grp) gets key slots mt*16 + grp*4 + r of query col ----
+                        f32x4_t s[MT];
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt) {
+                            s[mt] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int ks = 0; ks < 2; ++ks) {
+                                const bf16x8_t ka = *reinterpret_cast<const bf16x8_t*>(ka_of(mt) + ks * 32);
+                                s[mt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[u][ks], s[mt], 0, 0, 0);
+                            }
+                        }
+                        // ---- softmax over the key slots, fp32; P is normalised before it is rounded to bf16 ----
+                        float m = -INFINITY;
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                if (mt * 16 + 15 >= NSLOT) {   // tile contains pad slots: mask them
+                                    const bool valid = (mt * 16 + r + grp * 4) < NSLOT;
+                                    s[mt][r] = valid ? s[mt][r] : -INFINITY;
+                                }
+                                m = fmaxf(m, s[mt][r]);
+                            }
+                        m = naf_rows_max(m);
+                        float sum = 0.f;
+                        const float mc = m * p.scale_log2e;
+#pragma unroll
+                        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float e = __builtin_amdgcn_exp2f(fmaf(s[mt][r], p.scale_log2e, -mc));
+                                s[mt][r] = e;
+                                sum += e;
+                            }
+                        sum = naf_rows_sum(sum);
+                        const float inv = __builtin_amdgcn_rcpf(sum);   // sum >= 1
+                        // pack P to bf16 B-fragments: k index (g, j) <-> slot ks*32 + (j>>2)*16 + g*4 + (j&3)
+#pragma unroll
+                        for (int ks = 0; ks < KST; ++ks)
+#pragma unroll
+                            for (int j = 0; j < 8; ++j) pf[u][ks][j] = (bf16_t)(s[2 * ks + (j >> 2)][j & 3] * inv);
+                        // ---- numerator: O^T += PV^T . P^T: lane (col, grp) owns channels ct*16 + grp*4 + r of query col ----
+#pragma unroll
+                        for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                            for (int ks = 0; ks < KST; ++ks)
+                                acc[u][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag(Vs, VROW, ks, ct * 16), pf[u][ks], acc[u][ct], 0, 0, 0);
+                            // wide heads: keep the scheduler from hoisting every channel tile's PV^T fragments above the first MFMA (it spills)
+                            if constexpr (NCT * KST >= 40) __builtin_amdgcn_sched_barrier(0);
+                        }
+                    }
+                    // ---- denominator: F^T = V^T . P^T of this chunk's channel tiles, squared and dropped ----
+#pragma unroll
+                    for (int vt = 0; vt < DVC / 16; ++vt) {
+                        if (vt * 2 >= wch_mem) continue;   // wave-uniform: the tile lies past Dv (dv is a multiple of 16)
+                        f32x4_t f = f32x4_t{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                        for (int ks = 0; ks < KST; ++ks) f = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a_frag(Ws, WROW, ks, vt * 16), pf[u][ks], f, 0, 0, 0);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) ssq[u] = __builtin_fmaf(f[r], f[r], ssq[u]);
+                    }
+                }
+            }
+        }
+
+        // ---- epilogue: the pixel's norm over all heads' channels, out = logit_scale * (acc / max(norm, 1e-12)) ----
+        // its own arguments, fetched from the kernel-argument segment HERE: the empty asm makes the address opaque, so the scalar loads
+        // cannot be hoisted above the head loop and held in registers across it; the same for the lane's coordinates
+        const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        int ecol = col, egrp = grp;
+        asm volatile("" : "+v"(ecol), "+v"(egrp));
+        const XnaCosEpilogue __attribute__((address_space(4)))* x = reinterpret_cast<const XnaCosEpilogue __attribute__((address_space(4)))*>(ka + XNA_COS_ARG_OFFSET);
+#pragma unroll
+        for (int u = 0; u < TPW; ++u) {
+            if (!livev[u]) continue;   // wave-uniform: the four-lane reduction below runs on whole waves
+            const float nrm = sqrtf(naf_rows_sum(ssq[u]));
+            const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+            if (tx0v[u] + ecol >= p.dx) continue;
+            float* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ch = ct * 16 + egrp * 4 + r;
+                    if (ch < p.N) op[ch] = x->logit_scale * (acc[u][ct][r] * inv);
+                }
+            }
+            if (x->norms != nullptr && egrp == 0)
+                x->norms[b * x->ns[0] + (int64_t)(cy * p.dy + tyv[u]) * x->ns[1] + (int64_t)(cx * p.dx + tx0v[u] + ecol) * x->ns[2]] = nrm;
+        }
+    }
+}
+
+template <int KS, int NCT>
+static int xna_cos_launch_one(const XnaCosParams& p, const XnaCosEpilogue& epi, hipStream_t s) {
+    if constexpr (!xna_cos_served(KS, NCT)) {
+        naf_set_error("naf_xna_cos_fwd: no kernel for kernel_size=%d channel tiles=%d", KS, NCT);
+        return NAF_ERR_UNSUPPORTED;
+    } else {
+        constexpr size_t lds = xna_cos_lds_for(KS, NCT);
+        auto kern = xna_cos_kernel<KS, NCT>;
+        if (lds > 48 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) {
+                naf_set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize=%zu): %s", lds, hipGetErrorString(e));
+                return NAF_ERR_LAUNCH;
+            }
+        }
+        hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, epi);
+        return naf_check_launch("xna_cos_kernel");
+    }
+}
+
+// The window's entry point, one explicit instantiation per window in xna_cos_inst.hip.
+template <int KS>
+int xna_cos_launch_ks(const XnaCosParams& p, const XnaCosEpilogue& epi, hipStream_t s) {
+    const int nct = xna_head_nct(p.npad);
+    if (nct == 2) return xna_cos_launch_one<KS, 2>(p, epi, s);
+    if (nct == 4) return xna_cos_launch_one<KS, 4>(p, epi, s);
+    if (nct == 10) return xna_cos_launch_one<KS, 10>(p, epi, s);
+    if (nct == 16) return xna_cos_launch_one<KS, 16>(p, epi, s);
+    naf_set_error("naf_xna_cos_fwd: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
+    return NAF_ERR_UNSUPPORTED;
+}
+
+// xna_cos_inst.hip (-DNAF_KS=<KS>) defines it, xna_cos.hip declares it (extern) and dispatches on the window.
+#define NAF_XNA_COS_WINDOW(LINKAGE, KS) LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosEpilogue&, hipStream_t);

@@ -24,6 +24,7 @@ view of a channels-last buffer -- the same view the reference returns on its fus
 from __future__ import annotations
 
 import collections
+import math
 import os
 
 from typing import Optional, Tuple
@@ -683,6 +684,37 @@ def _apply_head(head, x: torch.Tensor) -> torch.Tensor:
     return F.conv2d(x.to(weight.dtype), weight, None if bias is None else bias.to(weight.dtype))
 
 
+def _cosine_head(head, channels: int) -> torch.Tensor:
+    """The embedding matrix [N, C] of a ``cosine=True`` call: a tensor, a ``(weight, None)`` pair, or the weight of a bias-free ``nn.Linear`` /
+    plain 1x1 ``nn.Conv2d``; any float dtype.  TypeError for other forms, ValueError for a bias or a shape that does not fit."""
+    if isinstance(head, torch.Tensor):
+        weight, bias = head, None
+    elif isinstance(head, (nn.Conv2d, nn.Linear)):
+        weight, bias = head.weight, head.bias
+        if isinstance(head, nn.Conv2d):
+            pad = head.padding
+            pad_ok = pad in ("valid", "same") if isinstance(pad, str) else all(int(v) == 0 for v in pad)
+            if tuple(head.kernel_size) != (1, 1) or tuple(head.stride) != (1, 1) or head.groups != 1 or tuple(head.dilation) != (1, 1) or not pad_ok:
+                raise ValueError(f"head: the convolution must be a plain 1x1 one (kernel 1, stride 1, no padding, dilation 1, groups 1), got {head}")
+    elif isinstance(head, (tuple, list)) and len(head) == 2 and isinstance(head[0], torch.Tensor) and (head[1] is None or isinstance(head[1], torch.Tensor)):
+        weight, bias = head
+    else:
+        raise TypeError(f"cosine=True: head must be an [N, C] tensor, a (weight, None) pair, or a bias-free nn.Linear / 1x1 nn.Conv2d; got {type(head).__name__}")
+    if bias is not None:
+        raise ValueError("cosine=True: the head must have no bias (a cosine is taken against the rows of its weight)")
+    if weight.dim() == 4 and tuple(weight.shape[2:]) == (1, 1):
+        weight = weight[:, :, 0, 0]
+    if weight.dim() != 2 or not weight.is_floating_point():
+        raise ValueError(f"cosine=True: the embeddings must be a floating-point [N, C] or [N, C, 1, 1] tensor, got {tuple(weight.shape)} {weight.dtype}")
+    if weight.shape[1] != channels or weight.shape[0] < 1:
+        raise ValueError(f"cosine=True: the embeddings are {tuple(weight.shape)}, the features have {channels} channels")
+    return weight
+
+
+def _lib_last_error() -> str:
+    return ops._lib.last_error()
+
+
 PointQuery = collections.namedtuple("PointQuery", ["features", "logits", "probs", "window_y", "window_x"])
 PointQuery.__doc__ = """Result of ``NAF.query``: ``features`` [N, C] fp32 or None, ``logits`` / ``probs`` [N, heads, ky*kx] fp32 or None,
 ``window_y`` [N, ky] / ``window_x`` [N, kx] int32: the low-res rows / columns each point attends to (-1 for a point outside the grid)."""
@@ -1054,7 +1086,8 @@ class NAF(nn.Module):
         return (out, logits) if return_weights else out
 
     def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
-                reduction="mean", predict=False, confusion=None, regress=None, regress_path="auto", **kwargs):
+                reduction="mean", predict=False, confusion=None, regress=None, regress_path="auto", cosine=False, logit_scale=1.0,
+                return_norms=False, cosine_path="auto", **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -1129,7 +1162,25 @@ class NAF(nn.Module):
         the encoder as today's step does, from a ``dout`` that carries one bf16 rounding instead of two.  Without a gradient the inference stem
         and materialised queries feed the loss-only launch (nothing but the loss is written).  ``regress`` together with ``head``,
         ``target``, ``predict``, ``confusion`` or ``return_weights`` raises ValueError; shape, dtype and device mismatches raise before any
-        device work.  Not offered: other losses, the reference's unused ``normalize=True``, ``capture()`` of this call."""
+        device work.  Not offered: other losses, the reference's unused ``normalize=True``, ``capture()`` of this call.
+
+        ``cosine``, ``logit_scale``, ``return_norms``, ``cosine_path`` (keyword only, with ``head``): open-vocabulary logits and
+        similarity heat maps.  ``head`` is then an embedding matrix ``E`` [N, C] of any float dtype -- a tensor, a ``(weight, None)`` pair,
+        or an ``nn.Linear`` / 1x1 ``nn.Conv2d`` WITHOUT bias whose weight it is -- and the call returns, in fp32 [B, N, Ho, Wo],
+            ``logit_scale * einsum("nc,bchw->bnhw", F.normalize(E.float(), dim=1), F.normalize(naf(image, features, size).float(), dim=1))``
+        (eps 1e-12 in both: a pixel whose upsampled feature is zero gets exactly 0, never NaN); with ``return_norms=True``
+        ``(cos, norms)``, ``norms`` [B, Ho, Wo] fp32 = the feature's unclamped 2-norm.  ``cosine_path="auto"`` takes it from the attention
+        kernel (``ops.xna_cos_forward``: the [B, C, Ho, Wo] features, their fp32 copy and the normalised copy never exist) for bf16 features
+        on the geometries ``head=`` is fused for (windows 13 and 15 up to 64 embeddings), and is the expression above in torch ops on the
+        plain forward everywhere else: fp16 / fp32 features, non-integer ratios, ratio 1, and whenever a gradient is enabled and ``E``
+        requires one (that route is differentiable with respect to ``E``; the fused one is inference-only).  ``"fused"`` insists
+        (NafHipError with the library's reason); ``"composed"`` is the A/B arm.  ``cosine=True`` with ``predict=True`` or with ``target=`` and
+        ``confusion=`` runs those calls with ``head=(F.normalize(E.float(), dim=1), None)``: the argmax does not see the per-pixel positive
+        scale.  ValueError: a head with a bias, ``target=`` without ``confusion=`` (no loss on cosines), ``regress=``, ``return_weights``,
+        ``return_norms`` with ``predict`` / ``confusion``.  Not offered: a gradient through the fused route, ``capture()`` of this call."""
+        if cosine:
+            return self._forward_cosine(image, features, output_size, return_weights, head, target, ignore_index, reduction, predict, confusion,
+                                        regress, logit_scale, return_norms, cosine_path)
         if isinstance(image, Guidance):
             self._check_guidance_call(image, features, return_weights, regress, confusion)
         if regress is not None:
@@ -1298,6 +1349,73 @@ class NAF(nn.Module):
             with ops._Timed("attention"):
                 loss, _ = ops.xna_mse_forward(q5, k5, v5, regress, ksz, scale=self.upsampler.scale, grad=False)
         return loss
+
+    def _forward_cosine(self, image, features, output_size, return_weights, head, target, ignore_index, reduction, predict, confusion,
+                        regress, logit_scale, return_norms, path):
+        """``forward(..., head=E, cosine=True)``: see ``forward``.  Every refusal comes before anything touches the device."""
+        if path not in ("auto", "fused", "composed"):
+            raise ValueError(f"cosine_path must be 'auto', 'fused' or 'composed', got {path!r}")
+        if regress is not None or return_weights:
+            raise ValueError("naf(..., cosine=True) returns cosines against the rows of head=E: it does not combine with regress / return_weights")
+        if head is None:
+            raise ValueError("naf(..., cosine=True) needs the embeddings: pass head=E ([N, C] tensor, or a bias-free nn.Linear / 1x1 nn.Conv2d)")
+        if not isinstance(features, torch.Tensor) or features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(getattr(features, 'shape', ()))}")
+        weight = _cosine_head(head, features.shape[1])
+        evaluation = confusion is not None and confusion is not False
+        if target is not None and not evaluation:
+            raise ValueError("naf(..., cosine=True, target=...) without confusion=: a loss on scaled cosines is not offered (labels: predict=True; "
+                             "evaluation: confusion=)")
+        if not math.isfinite(float(logit_scale)):
+            raise ValueError(f"logit_scale must be finite, got {logit_scale}")
+        if predict or evaluation:
+            if return_norms:
+                raise ValueError("naf(..., cosine=True, return_norms=True) goes with the cosines, not with predict / confusion")
+            # the argmax over n of logit_scale * cos is that of E^ . f for logit_scale > 0: the existing labels / confusion launches
+            if float(logit_scale) <= 0:
+                raise ValueError(f"naf(..., cosine=True, predict / confusion) needs logit_scale > 0 (the labels are the argmax), got {logit_scale}")
+            with torch.no_grad():
+                e_hat = ops.normalize_embeddings(weight)
+            return self.forward(image, features, output_size, head=(e_hat, None), target=target, ignore_index=ignore_index, reduction=reduction,
+                                predict=predict, confusion=confusion)
+        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
+            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
+                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
+        if isinstance(image, Guidance):
+            self._check_guidance_call(image, features, False, None, None)
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, C, N = features.shape[0], features.shape[1], weight.shape[0]
+        if B == 0:
+            cos = torch.empty((0, ho, wo, N), dtype=torch.float32, device=features.device).permute(0, 3, 1, 2)
+            return (cos, torch.empty((0, ho, wo), dtype=torch.float32, device=features.device)) if return_norms else cos
+        heads, ksz, enc = self.upsampler.num_heads, self.upsampler.kernel_size, self.image_encoder
+        grad = torch.is_grad_enabled()
+        reason = None       # why the fused kernel does not take the call
+        if grad and weight.requires_grad:
+            reason = "the fused cosine kernel is inference-only and the embeddings require a gradient"
+        elif grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+            reason = "the fused cosine kernel is inference-only and the call wants a gradient for the upsampler or its inputs"
+        elif features.dtype != torch.bfloat16:
+            reason = f"the fused cosine kernel reads bfloat16 features, got {features.dtype}"
+        elif C % heads or enc.out_channels % heads:
+            reason = f"feature channels {C} / guidance channels {enc.out_channels} not divisible by {heads} heads"
+        else:
+            probe = torch.empty((B, ho, wo, heads, enc.out_channels // heads), dtype=torch.bfloat16, device="meta").permute(0, 3, 1, 2, 4)
+            if ops.xna_cos_select(probe, features.shape[-2:], C // heads, N, ksz) != "fused":
+                reason = _lib_last_error() or f"naf_xna_cos_select refuses {N} embeddings"
+        if path == "fused" and reason is not None:
+            raise ops._lib.NafHipError(f"naf(..., cosine=True, cosine_path='fused'): {reason}")
+        if path == "composed" or reason is not None:
+            with ops._Timed("cosine_composed"):
+                return ops.cosine_from_features(self.forward(image, features, output_size), ops.normalize_embeddings(weight), logit_scale, return_norms)
+        with torch.no_grad():
+            lr = features.shape[-2:]
+            fusable = lambda q5, tabs: ops.xna_cos_select(q5, lr, C // heads, N, ksz, rope_tables=tabs) == "fused"
+            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
+            v5 = ops.pack_values(features).view(B, lr[0], lr[1], heads, C // heads).permute(0, 3, 1, 2, 4)
+            with ops._Timed("attention"):
+                return ops.xna_cos_forward(q5, k5, v5, weight, ksz, logit_scale=logit_scale, return_norms=return_norms, path="fused",
+                                           scale=self.upsampler.scale, rope_tables=tabs)
 
     def _head_call(self, image, features, output_size, return_weights, head, reduction="mean", target=None, confusion=None):
         """Host-side validation the three ``head=`` entries share, in the order they raise (nothing has touched the device yet):

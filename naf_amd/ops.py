@@ -1297,6 +1297,159 @@ def xna_head_forward(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, b
         return o.to(out_dtype).contiguous().permute(0, 3, 1, 2)
 
 
+# ---- ... and a cosine head: scaled cosines between the upsampled feature and N embeddings (open vocabulary, heat maps) -----------
+def normalize_embeddings(embeddings: torch.Tensor) -> torch.Tensor:
+    """``F.normalize(E.float(), dim=1)`` (eps 1e-12) of an [N, C] or [N, C, 1, 1] embedding matrix: the rows the cosine head projects with."""
+    if embeddings.dim() == 4 and tuple(embeddings.shape[2:]) == (1, 1):
+        embeddings = embeddings[:, :, 0, 0]
+    if embeddings.dim() != 2 or not embeddings.is_floating_point():
+        raise ValueError(f"cosine head: embeddings must be a floating-point [N, C] or [N, C, 1, 1] tensor, got {tuple(embeddings.shape)} {embeddings.dtype}")
+    return torch.nn.functional.normalize(embeddings.float(), dim=1)
+
+
+def _check_cos_operands(who: str, q, k_lr, v_lr, embeddings, path):
+    for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
+        _gpu(t, n)
+        if t.dim() != 5 or t.stride(4) != 1:
+            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    if q.dtype != torch.bfloat16 or k_lr.dtype != torch.bfloat16:
+        raise TypeError(f"{who}: q and k_lr must be bfloat16, got {q.dtype} / {k_lr.dtype}")
+    if path not in _HEAD_PATHS:
+        raise ValueError(f"{who}: path must be one of {_HEAD_PATHS}, got {path!r}")
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w, Dv = v_lr.shape[2:]
+    if k_lr.shape != (B, heads, h, w, Dq) or v_lr.shape[:2] != (B, heads):
+        raise ValueError(f"{who}: k_lr {tuple(k_lr.shape)} / v_lr {tuple(v_lr.shape)} do not match q {tuple(q.shape)}")
+    e = normalize_embeddings(embeddings)
+    if e.shape[1] != heads * Dv or e.shape[0] < 1:
+        raise ValueError(f"{who}: embeddings {tuple(e.shape)} do not match the {heads} x {Dv} = {heads * Dv} value channels")
+    if e.device != q.device:
+        raise ValueError(f"{who}: embeddings on {e.device}, q on {q.device}")
+    return e, (B, heads, Ho, Wo, Dq, h, w, Dv)
+
+
+def _fill_xna_cos(q, k, pv, v, out, norms, n_out, ky, kx, path, scale, logit_scale, rope_tables=None) -> "_lib.XnaCosArgs":
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w, Dv = v.shape[2:]
+    a = _lib.XnaCosArgs()
+    a.q, a.k_lr, a.pv_lr, a.v_lr, a.out = q.data_ptr(), k.data_ptr(), pv.data_ptr(), v.data_ptr(), out.data_ptr()
+    a.norms = norms.data_ptr() if norms is not None else None
+    if rope_tables is not None:
+        ty, tx = rope_tables
+        if ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
+                or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
+            raise ValueError("xna_cos: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
+        a.rope_tab_y, a.rope_tab_x = ty.data_ptr(), tx.data_ptr()
+    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, int(n_out), ky, kx
+    a.path = _lib.XNA_HEAD_FUSED if path == "fused" else _lib.XNA_HEAD_AUTO
+    a.scale = float(scale) if scale else 0.0
+    a.logit_scale = float(logit_scale)
+    a.q_stride = _strides4(q, (0, 1, 2, 3))
+    a.k_stride = _strides4(k, (0, 1, 2, 3))
+    a.pv_stride = _strides4(pv, (0, 1, 2, 3))
+    a.v_stride = _strides4(v, (0, 1, 2, 3))
+    a.o_stride = _strides3(out)
+    if norms is not None:
+        a.norms_stride = _strides3(norms)
+    return a
+
+
+def xna_cos_select(q: torch.Tensor, lr_size, Dv: int, n_out: int, kernel_size, *, value_dtype: torch.dtype = torch.bfloat16,
+                   rope_tables=None) -> str:
+    """Which route ``xna_cos_forward(path="auto")`` takes for these shapes: "fused" (``naf_xna_cos_select`` grants the cosine-head kernel)
+    or "composed" (the plain forward, normalised, times the normalised embeddings).  ``q``: the 5-D [B, heads, Ho, Wo, Dq] bf16 queries --
+    with ``rope_tables`` the un-rotated guidance; ``Dv``: value channels per head; ``value_dtype``: the features' (the kernel reads
+    bfloat16 values).  A host-side query: nothing is launched or read, CPU tensors do.  Invalid arguments raise ValueError."""
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or value_dtype != torch.bfloat16 or not 1 <= int(n_out) <= 256 or int(Dv) < 1:
+        return "composed"
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    npad, Dv = head_npad(n_out), int(Dv)
+    a = _lib.XnaCosArgs()
+    a.q = a.k_lr = a.pv_lr = a.v_lr = a.out = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, int(n_out), ky, kx
+    a.path, a.scale, a.logit_scale = _lib.XNA_HEAD_AUTO, 0.0, 1.0
+    a.q_stride = _strides4(q, (0, 1, 2, 3))
+    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
+    a.pv_stride = I64x4(heads * h * w * npad, h * w * npad, w * npad, npad)
+    a.v_stride = I64x4(h * w * heads * Dv, Dv, w * heads * Dv, heads * Dv)
+    a.o_stride = I64x3(Ho * Wo * int(n_out), Wo * int(n_out), int(n_out))
+    sel = lib.naf_xna_cos_select(C.byref(a))
+    if sel == -1:
+        _lib.check(1, "naf_xna_cos_select")
+    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
+
+
+def cosine_from_features(f: torch.Tensor, e_hat: torch.Tensor, logit_scale: float = 1.0, return_norms: bool = False):
+    """The definition in torch ops: ``logit_scale * einsum("nc,bchw->bnhw", e_hat, F.normalize(f.float(), dim=1))`` for f [B, C, H, W] and
+    normalised rows ``e_hat`` [N, C] fp32 (``normalize_embeddings``); with ``return_norms`` also ``f.float().norm(dim=1)``.  A zero feature
+    gives exactly 0.  Differentiable; the result is a logical [B, N, H, W] view of a dense channels-last buffer, as the kernel's."""
+    ff = f.float().permute(0, 2, 3, 1)
+    nrm = ff.norm(dim=3)
+    cos = (torch.matmul(ff / nrm.clamp_min(1e-12).unsqueeze(3), e_hat.t()) * float(logit_scale)).permute(0, 3, 1, 2)
+    return (cos, nrm) if return_norms else cos
+
+
+def xna_cos_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, embeddings: torch.Tensor, kernel_size, *,
+                    logit_scale: float = 1.0, return_norms: bool = False, path: str = "auto", scale: Optional[float] = None,
+                    rope_tables=None):
+    """Cross-scale neighbourhood attention with a cosine head folded in: per pixel, ``logit_scale`` times the cosine between the upsampled
+    feature ``f = attention(q, k_lr, v_lr)`` (all heads' channels) and each of the N rows of ``embeddings``, without writing ``f``.
+
+    q [B, heads, Ho, Wo, Dq] bf16, k_lr [B, heads, h, w, Dq] bf16, v_lr [B, heads, h, w, Dv] (5-D strided views, last dim contiguous),
+    embeddings [N, heads * Dv] (or [N, C, 1, 1]) of any float dtype on the same device.  Returns fp32 ``cos`` as a logical [B, N, Ho, Wo]
+    view of a dense channels-last [B, Ho, Wo, N] buffer; with ``return_norms`` also ``||f||_2`` [B, Ho, Wo] fp32 (unclamped).  A pixel whose
+    feature is zero gets exactly 0.  Inference only on the fused route (no graph is recorded).
+    ``path="auto"``: the kernel (``naf_xna_cos_fwd``: the numerator through ``E^ @ V`` on the low-res grid as in ``xna_head_forward``, the
+    norm from ``P . V`` on the matrix cores, squared and dropped) where ``naf_xna_cos_select`` grants it and no gradient is wanted for the
+    embeddings, else the composition: ``xna_forward``, ``F.normalize`` and a matrix product as torch ops (``cosine_from_features``;
+    differentiable with respect to the embeddings).  ``"fused"`` insists and raises NafHipError where the kernel does not serve the call
+    or a gradient is wanted for the embeddings; ``"composed"`` insists on the composition.
+    ``rope_tables``: as in ``xna_forward`` (q is the un-rotated guidance)."""
+    e_hat, (B, heads, Ho, Wo, Dq, h, w, Dv) = _check_cos_operands("xna_cos_forward", q, k_lr, v_lr, embeddings, path)
+    ky, kx = _ksize(kernel_size)
+    N = e_hat.shape[0]
+    if not math.isfinite(float(logit_scale)):
+        raise ValueError(f"xna_cos_forward: logit_scale must be finite, got {logit_scale}")
+    lib = _lib.load()
+    dev = q.device
+    wants_grad = torch.is_grad_enabled() and embeddings.requires_grad
+    if path == "fused" and wants_grad:
+        raise _lib.NafHipError("xna_cos_forward: the fused cosine kernel is inference-only; the embeddings require a gradient "
+                               "(path='composed' is differentiable)")
+    if path != "composed" and not wants_grad and (path == "fused" or (v_lr.dtype == torch.bfloat16 and N <= 256)):
+        if v_lr.dtype != torch.bfloat16:
+            raise _lib.NafHipError(f"xna_cos_forward: the fused kernel needs bfloat16 values, got {v_lr.dtype}")
+        with torch.no_grad():
+            pv = torch.einsum("ngd,bghwd->bghwn", e_hat.reshape(N, heads, Dv), v_lr.float())
+            pad = head_npad(N) - N
+            pv5 = (torch.nn.functional.pad(pv, (0, pad)) if pad else pv).to(torch.bfloat16)
+            out = torch.empty((B, Ho, Wo, N), dtype=torch.float32, device=dev)
+            norms = torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev) if return_norms else None
+            a = _fill_xna_cos(q, k_lr, pv5, v_lr, out, norms, N, ky, kx, path, scale, logit_scale, rope_tables)
+            sel = lib.naf_xna_cos_select(C.byref(a))
+            if sel == _lib.XNA_HEAD_FUSED:
+                with torch.cuda.device(dev), _Timed("xna_cos"):
+                    rc = lib.naf_xna_cos_fwd(C.byref(a), _stream(q))
+                _lib.check(rc, "naf_xna_cos_fwd")
+                cos = out.permute(0, 3, 1, 2)
+                return (cos, norms) if return_norms else cos
+            if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
+                _lib.check(-sel, "naf_xna_cos_select")
+            del out, norms, pv5, pv
+    with _Timed("xna_cos_composed"):
+        with torch.no_grad():
+            odt = v_lr.dtype if v_lr.dtype in (torch.bfloat16, torch.float16) else torch.float32
+            o5 = xna_forward(q, k_lr, v_lr if v_lr.dtype in (torch.bfloat16, torch.float16) else v_lr.to(torch.bfloat16), (ky, kx),
+                             out_dtype=odt, path="auto", scale=scale, rope_tables=rope_tables)
+            f = o5.permute(0, 1, 4, 2, 3).reshape(B, heads * Dv, Ho, Wo)
+        return cosine_from_features(f, e_hat, logit_scale, return_norms)
+
+
 def head_dlogits_channels(n_out: int) -> int:
     """Channels of a ``dlogits`` row for ``n_out`` classes: the value width the cell backward serves that holds Npad (``_BWD_DV``)."""
     npad = head_npad(n_out)
