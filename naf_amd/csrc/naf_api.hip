@@ -51,6 +51,25 @@ static int xna_geometry_validate(const char* who, const A* a, int Dv) {
     return NAF_OK;
 }
 
+// What the entries of the two head-summed families ask alike (A: naf_xna_head_args or naf_xna_cos_args, not NULL), in two pieces so
+// that each entry keeps the order of its own checks between and after them.  `other_ptrs`: the entry's further non-NULL pointers.
+template <typename A>
+static int xna_headsum_validate_sizes(const char* who, const A* a, int Dv, bool other_ptrs) {
+    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && other_ptrs, "%s: NULL tensor pointer", who);
+    const int rc = xna_geometry_validate(who, a, Dv);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(a->N >= 1 && a->N <= 256, "%s: N must be in 1 .. 256, got %d", who, a->N);
+    return NAF_OK;
+}
+template <typename A>
+static int xna_headsum_validate_route(const char* who, const A* a) {
+    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "%s: path %d", who, a->path);
+    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "%s: rope_tab_y and rope_tab_x must be given together", who);
+    NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "%s: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)", who,
+                (long long)a->pv_stride[3], a->N);
+    return NAF_OK;
+}
+
 extern "C" {
 
 int naf_version(void) { return NAF_HIP_VERSION; }
@@ -394,15 +413,11 @@ int naf_xna_fwd(const naf_xna_args* a, naf_stream_t stream) {
 // need_out = false: the classification entry (naf_xna_head_ce_*), where `out` is optional
 static int xna_head_validate(const naf_xna_head_args* a, bool need_out = true) {
     NAF_REQUIRE(a != nullptr, "naf_xna_head_fwd: args is NULL");
-    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && (a->out || !need_out), "naf_xna_head_fwd: NULL tensor pointer");
-    const int rc = xna_geometry_validate("naf_xna_head_fwd", a, 1);   // the value channels are N, with a range of their own
+    int rc = xna_headsum_validate_sizes("naf_xna_head_fwd", a, 1, a->out || !need_out);   // the value channels are N, with a range of their own
     if (rc != NAF_OK) return rc;
-    NAF_REQUIRE(a->N >= 1 && a->N <= 256, "naf_xna_head_fwd: N must be in 1 .. 256, got %d", a->N);
     NAF_REQUIRE(a->out_dtype == NAF_BF16 || a->out_dtype == NAF_F32, "naf_xna_head_fwd: out_dtype %d", a->out_dtype);
-    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "naf_xna_head_fwd: path %d", a->path);
-    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_head_fwd: rope_tab_y and rope_tab_x must be given together");
-    NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "naf_xna_head_fwd: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)",
-                (long long)a->pv_stride[3], a->N);
+    rc = xna_headsum_validate_route("naf_xna_head_fwd", a);
+    if (rc != NAF_OK) return rc;
     NAF_REQUIRE(a->out == nullptr || a->o_stride[2] >= a->N, "naf_xna_head_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
     return NAF_OK;
 }
@@ -484,14 +499,9 @@ int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream) {
 // ---- the cosine head: scaled cosines between the upsampled feature and N embeddings (after the image-preparation entries) ----
 static int xna_cos_validate(const naf_xna_cos_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_cos_fwd: args is NULL");
-    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && a->v_lr && a->out, "naf_xna_cos_fwd: NULL tensor pointer");
-    const int rc = xna_geometry_validate("naf_xna_cos_fwd", a, a->Dv);
+    int rc = xna_headsum_validate_sizes("naf_xna_cos_fwd", a, a->Dv, a->v_lr && a->out);
+    if (rc == NAF_OK) rc = xna_headsum_validate_route("naf_xna_cos_fwd", a);
     if (rc != NAF_OK) return rc;
-    NAF_REQUIRE(a->N >= 1 && a->N <= 256, "naf_xna_cos_fwd: N must be in 1 .. 256, got %d", a->N);
-    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "naf_xna_cos_fwd: path %d", a->path);
-    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "naf_xna_cos_fwd: rope_tab_y and rope_tab_x must be given together");
-    NAF_REQUIRE(a->pv_stride[3] >= ((a->N + 15) & ~15), "naf_xna_cos_fwd: pv_lr rows must hold N rounded up to 16 channels (x stride %lld, N %d)",
-                (long long)a->pv_stride[3], a->N);
     NAF_REQUIRE(a->v_stride[3] >= a->Dv, "naf_xna_cos_fwd: v_lr x stride %lld smaller than Dv %d", (long long)a->v_stride[3], a->Dv);
     NAF_REQUIRE(a->o_stride[2] >= a->N, "naf_xna_cos_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
     NAF_REQUIRE(reinterpret_cast<uintptr_t>(a->out) % 4 == 0 && reinterpret_cast<uintptr_t>(a->norms) % 4 == 0, "naf_xna_cos_fwd: out / norms not 4-byte aligned");

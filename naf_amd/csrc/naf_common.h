@@ -268,3 +268,38 @@ __host__ __device__ inline bool xna_row_tiles_ok(int dx) {
     const int pad = ((dx + 15) & ~15) - dx;
     return pad * 6 <= dx;
 }
+
+// ---- the two head-summed families (A: naf_xna_head_args or naf_xna_cos_args; `fam` prefixes the messages: "naf_xna_head", "naf_xna_cos") ----
+// The geometry their cell kernel serves: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set.
+template <typename A>
+inline int xna_headsum_shape_eligible(const char* fam, const A* a) {
+    if (!xna_cell_shape_ok(a)) {   // which of its conditions (an even window never gets here: the entries refuse it)
+        const int ks = a->ky;
+        if (a->ky != a->kx || ks < 3 || ks > 15) naf_set_error("%s: the fused kernel needs a square window 3 .. 15 (got %dx%d)", fam, a->ky, a->kx);
+        else if (a->Dq != 64) naf_set_error("%s: the fused kernel needs Dq = 64 (got %d)", fam, a->Dq);
+        else if (a->h < ks || a->w < ks) naf_set_error("%s: the fused kernel needs h, w >= window (got %dx%d, window %d)", fam, a->h, a->w, ks);
+        else naf_set_error("%s: the fused kernel needs an integer ratio (got %dx%d -> %dx%d)", fam, a->h, a->w, a->Ho, a->Wo);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    const int dy = a->Ho / a->h, dx = a->Wo / a->w;
+    if (!xna_row_tiles_ok(dx) || (int64_t)dy * ((dx + 15) / 16) > 1024) {
+        naf_set_error("%s: the fused kernel needs row tiles (Wo/w a multiple of 16, or 14, 15, 28, 30 ...; at most 1024 tiles per cell; got %dx%d -> %dx%d)",
+                      fam, a->h, a->w, a->Ho, a->Wo);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    return NAF_OK;
+}
+
+// What both families' parameter structs (P: XnaHeadParams, XnaCosParams) take from their arguments, and the grid; `who` names the entry.
+template <typename P, typename A>
+inline int xna_headsum_fill(P& p, const A* a, float scale, const char* who) {
+    xna_fill_common(p, a, a->pv_stride, scale);
+    p.pv = static_cast<const bf16_t*>(a->pv_lr);
+    p.out = a->out;
+    p.tab_y = a->rope_tab_y; p.tab_x = a->rope_tab_x;
+    p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
+    p.N = a->N;
+    p.npad = (a->N + 15) & ~15;
+    for (int i = 0; i < 3; ++i) p.os[i] = a->o_stride[i];
+    return xna_grid(who, (int64_t)a->B * a->h * a->w, &p.nblocks);
+}

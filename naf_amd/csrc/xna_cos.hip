@@ -9,20 +9,8 @@ NAF_FOR_WINDOWS(NAF_X)
 // NAF_OK when the kernel serves the (validated) request; otherwise NAF_ERR_UNSUPPORTED with the reason in the error string.  The geometry
 // and layout rules are the head family's (naf_common.h): what naf_xna_head_select grants, this kernel is asked to serve.
 int naf_xna_cos_eligible(const naf_xna_cos_args* a) {
-    if (!xna_cell_shape_ok(a)) {   // which of its conditions (an even window never gets here: the entries refuse it)
-        const int ks = a->ky;
-        if (a->ky != a->kx || ks < 3 || ks > 15) naf_set_error("naf_xna_cos: the fused kernel needs a square window 3 .. 15 (got %dx%d)", a->ky, a->kx);
-        else if (a->Dq != 64) naf_set_error("naf_xna_cos: the fused kernel needs Dq = 64 (got %d)", a->Dq);
-        else if (a->h < ks || a->w < ks) naf_set_error("naf_xna_cos: the fused kernel needs h, w >= window (got %dx%d, window %d)", a->h, a->w, ks);
-        else naf_set_error("naf_xna_cos: the fused kernel needs an integer ratio (got %dx%d -> %dx%d)", a->h, a->w, a->Ho, a->Wo);
-        return NAF_ERR_UNSUPPORTED;
-    }
-    const int dy = a->Ho / a->h, dx = a->Wo / a->w;
-    if (!xna_row_tiles_ok(dx) || (int64_t)dy * ((dx + 15) / 16) > 1024) {
-        naf_set_error("naf_xna_cos: the fused kernel needs row tiles (Wo/w a multiple of 16, or 14, 15, 28, 30 ...; at most 1024 tiles per cell; got %dx%d -> %dx%d)",
-                      a->h, a->w, a->Ho, a->Wo);
-        return NAF_ERR_UNSUPPORTED;
-    }
+    const int rc = xna_headsum_shape_eligible("naf_xna_cos", a);
+    if (rc != NAF_OK) return rc;
     if (a->Dv % 16 != 0) {
         naf_set_error("naf_xna_cos: the fused kernel needs Dv a multiple of 16 (got %d)", a->Dv);
         return NAF_ERR_UNSUPPORTED;
@@ -43,23 +31,15 @@ int naf_xna_cos_eligible(const naf_xna_cos_args* a) {
 
 int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s) {
     XnaCosParams p;
-    xna_fill_common(p, a, a->pv_stride, scale);
-    p.pv = static_cast<const bf16_t*>(a->pv_lr);
+    const int rc = xna_headsum_fill(p, a, scale, "naf_xna_cos_fwd");
+    if (rc != NAF_OK) return rc;
     p.v = static_cast<const bf16_t*>(a->v_lr);
-    p.out = a->out;
-    p.tab_y = a->rope_tab_y; p.tab_x = a->rope_tab_x;
-    p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
-    p.N = a->N;
-    p.npad = (a->N + 15) & ~15;
     p.dv = a->Dv;
     for (int i = 0; i < 4; ++i) p.ws[i] = a->v_stride[i];
-    for (int i = 0; i < 3; ++i) p.os[i] = a->o_stride[i];
     XnaCosEpilogue e;
     e.norms = a->norms;
     for (int i = 0; i < 3; ++i) e.ns[i] = a->norms != nullptr ? a->norms_stride[i] : 0;
     e.logit_scale = a->logit_scale;
-    const int rc = xna_grid("naf_xna_cos_fwd", (int64_t)a->B * a->h * a->w, &p.nblocks);
-    if (rc != NAF_OK) return rc;
     switch (a->ky) {
 #define NAF_X(K) case K: return xna_cos_launch_ks<K>(p, e, s);
         NAF_FOR_WINDOWS(NAF_X)

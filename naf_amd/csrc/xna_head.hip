@@ -10,20 +10,8 @@ NAF_FOR_WINDOWS(NAF_X)
 
 // NAF_OK when the kernel serves the (validated) request; otherwise NAF_ERR_UNSUPPORTED with the reason in the error string.
 int naf_xna_head_eligible(const naf_xna_head_args* a) {
-    if (!xna_cell_shape_ok(a)) {   // which of its conditions (an even window never gets here: the entries refuse it)
-        const int ks = a->ky;
-        if (a->ky != a->kx || ks < 3 || ks > 15) naf_set_error("naf_xna_head: the fused kernel needs a square window 3 .. 15 (got %dx%d)", a->ky, a->kx);
-        else if (a->Dq != 64) naf_set_error("naf_xna_head: the fused kernel needs Dq = 64 (got %d)", a->Dq);
-        else if (a->h < ks || a->w < ks) naf_set_error("naf_xna_head: the fused kernel needs h, w >= window (got %dx%d, window %d)", a->h, a->w, ks);
-        else naf_set_error("naf_xna_head: the fused kernel needs an integer ratio (got %dx%d -> %dx%d)", a->h, a->w, a->Ho, a->Wo);
-        return NAF_ERR_UNSUPPORTED;
-    }
-    const int dy = a->Ho / a->h, dx = a->Wo / a->w;
-    if (!xna_row_tiles_ok(dx) || (int64_t)dy * ((dx + 15) / 16) > 1024) {
-        naf_set_error("naf_xna_head: the fused kernel needs row tiles (Wo/w a multiple of 16, or 14, 15, 28, 30 ...; at most 1024 tiles per cell; got %dx%d -> %dx%d)",
-                      a->h, a->w, a->Ho, a->Wo);
-        return NAF_ERR_UNSUPPORTED;
-    }
+    const int rc = xna_headsum_shape_eligible("naf_xna_head", a);
+    if (rc != NAF_OK) return rc;
     if (!xna_qkv_layout_ok(a, a->pv_lr, a->pv_stride)) {   // which half of it
         if (!naf_aligned(a->q, 16) || !naf_aligned(a->k_lr, 16) || !naf_aligned(a->pv_lr, 16)) naf_set_error("naf_xna_head: the fused kernel needs 16-byte aligned q, k_lr, pv_lr");
         else naf_set_error("naf_xna_head: the fused kernel needs q / k_lr / pv_lr strides that are multiples of 8 elements");
@@ -53,18 +41,10 @@ int naf_xna_head_ce_eligible(const naf_xna_head_ce_args* c) {
 
 // `tag` names the variant in the messages: the C entry point is naf_<tag>_fwd.
 static int head_fill_params(const naf_xna_head_args* a, float scale, const char* tag, XnaHeadParams& p) {
-    xna_fill_common(p, a, a->pv_stride, scale);
-    p.pv = static_cast<const bf16_t*>(a->pv_lr);
     p.bias = a->bias;
-    p.out = a->out;
-    p.tab_y = a->rope_tab_y; p.tab_x = a->rope_tab_x;
-    p.dy = a->Ho / a->h; p.dx = a->Wo / a->w;
-    p.N = a->N;
-    p.npad = (a->N + 15) & ~15;
-    for (int i = 0; i < 3; ++i) p.os[i] = a->o_stride[i];
     char who[32];
     snprintf(who, sizeof(who), "naf_%s_fwd", tag);
-    return xna_grid(who, (int64_t)a->B * a->h * a->w, &p.nblocks);
+    return xna_headsum_fill(p, a, scale, who);
 }
 
 // Fills the parameters and dispatches on the window; `what` names the launch in a launch error, `x` is the variant's extra kernel argument.

@@ -715,6 +715,12 @@ def _lib_last_error() -> str:
     return ops._lib.last_error()
 
 
+def _rocm_only(**where) -> RuntimeError:
+    """The error of a call with an operand off the ROCm device; ``where`` (name=tensor) is listed as "got <name> on <device>, ..."."""
+    got = ", ".join(f"{n} on {t.device}" for n, t in where.items())
+    return RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback)" + (f"; got {got}" if got else ""))
+
+
 PointQuery = collections.namedtuple("PointQuery", ["features", "logits", "probs", "window_y", "window_x"])
 PointQuery.__doc__ = """Result of ``NAF.query``: ``features`` [N, C] fp32 or None, ``logits`` / ``probs`` [N, heads, ky*kx] fp32 or None,
 ``window_y`` [N, ky] / ``window_x`` [N, kx] int32: the low-res rows / columns each point attends to (-1 for a point outside the grid)."""
@@ -742,7 +748,7 @@ class Guidance:
             raise ValueError(f"guide: expected an image [B, 3, H, W], got "
                              + (f"{tuple(image.shape)}" if isinstance(image, torch.Tensor) else type(image).__name__))
         if not image.is_cuda:
-            raise RuntimeError(f"naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got image on {image.device}")
+            raise _rocm_only(image=image)
         self.model, self.image = model, image
         self._stamp = self._stamp_now()
         self._stem, self._pooled, self._queries, self._keys, self._tables = {}, {}, {}, {}, {}
@@ -977,7 +983,7 @@ class NAF(nn.Module):
         if regress_path not in ("auto", "fused", "composed"):
             raise ValueError(f"regress_path must be 'auto', 'fused' or 'composed', got {regress_path!r}")
         if not (image.is_cuda and features.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback)")
+            raise _rocm_only()
         enc = self.image_encoder
         ho, wo = int(output_size[0]), int(output_size[1])
         h, w = features.shape[-2:]
@@ -1198,14 +1204,19 @@ class NAF(nn.Module):
             return self._forward_head_objective(image, features, output_size, return_weights, head, target, ignore_index, reduction, bool(predict))
         if head is not None:
             return self._forward_head(image, features, output_size, return_weights, head)
-        if torch.is_grad_enabled() and (image.requires_grad or features.requires_grad or
-                                        (self.training and any(p.requires_grad for p in self.parameters()))):
+        if self._wants_grad(image, features):
             # the library's own differentiable stem whenever it serves the width, with or without torch.autocast (round 6: the
             # bf16-activation contract is what the inference path computes); else the torch stem in the ambient precision.
             # return_weights (attentions.py:64-67 under autograd): (out, scores); True: scores without a gradient, "differentiable": with one
             return self.forward_train(image, features, output_size, amp="auto", return_weights=return_weights)
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)
+
+    def _wants_grad(self, *inputs) -> bool:
+        """This call wants a gradient for the upsampler or its ``inputs`` (image or ``Guidance``, features): gradient mode with an input
+        that requires one, or ``.train()`` with trainable parameters.  Such calls take the training path."""
+        return torch.is_grad_enabled() and (any(t.requires_grad for t in inputs) or
+                                            (self.training and any(p.requires_grad for p in self.parameters())))
 
     # ---- encode the image once ------------------------------------------------------------------------------------------------
     def guide(self, image: torch.Tensor, output_size=None) -> Guidance:
@@ -1227,8 +1238,7 @@ class NAF(nn.Module):
                              "the frozen encoder's output; pass the image (return_weights=True works)")
         g.check(self)
         evaluation = confusion is not None and confusion is not False        # never differentiable, whatever the gradient mode
-        if not evaluation and torch.is_grad_enabled() and (g.requires_grad or (isinstance(features, torch.Tensor) and features.requires_grad) or
-                                                           (self.training and any(p.requires_grad for p in self.parameters()))):
+        if not evaluation and self._wants_grad(g, *([features] if isinstance(features, torch.Tensor) else [])):
             raise RuntimeError("naf(guidance, ...): this call wants a gradient for the upsampler, the image or the features (gradient mode with an "
                                "input that requires grad, or .train() with trainable parameters) and would take the training path; a Guidance "
                                "serves inference calls -- use torch.no_grad() / .eval() / requires_grad_(False), or pass the image")
@@ -1276,7 +1286,7 @@ class NAF(nn.Module):
         if features is not None and (features.shape[0] != B or not features.is_cuda):
             if features.shape[0] != B:
                 raise ValueError(f"query: features of batch {features.shape[0]}, image of batch {B}")
-            raise RuntimeError(f"naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got features on {features.device}")
+            raise _rocm_only(features=features)
         if points.shape[1] == 2 and B != 1:
             raise ValueError(f"query: [N, 2] points name no image; the batch is {B}, pass [N, 3] of (b, y, x)")
         dev = g.device
@@ -1324,13 +1334,11 @@ class NAF(nn.Module):
         B, C = features.shape[:2]
         ops._check_regress_target("naf(..., regress=...)", regress, (B, C, ho, wo), features.device)
         if not (image.is_cuda and features.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
-                               f"image on {image.device}, features on {features.device}")
+            raise _rocm_only(image=image, features=features)
         composed = lambda: F.mse_loss(self.forward(image, features, output_size).float(), regress.float())
         if regress_path == "composed" or (B == 0 and regress_path == "auto"):
             return composed()
-        if torch.is_grad_enabled() and (image.requires_grad or features.requires_grad or
-                                        (self.training and any(p.requires_grad for p in self.parameters()))):
+        if self._wants_grad(image, features):
             return self.forward_train(image, features, output_size, amp="auto", regress=regress, regress_path=regress_path)
         enc, heads, ksz = self.image_encoder, self.upsampler.num_heads, self.upsampler.kernel_size
         hip_stem = enc.use_encoder and enc.stem_impl == "hip" and enc._hip_stem_ok() and enc.rope.num_heads == heads
@@ -1379,8 +1387,7 @@ class NAF(nn.Module):
             return self.forward(image, features, output_size, head=(e_hat, None), target=target, ignore_index=ignore_index, reduction=reduction,
                                 predict=predict, confusion=confusion)
         if not (image.is_cuda and features.is_cuda and weight.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
-                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
+            raise _rocm_only(image=image, features=features, head=weight)
         if isinstance(image, Guidance):
             self._check_guidance_call(image, features, False, None, None)
         ho, wo = int(output_size[0]), int(output_size[1])
@@ -1393,7 +1400,7 @@ class NAF(nn.Module):
         reason = None       # why the fused kernel does not take the call
         if grad and weight.requires_grad:
             reason = "the fused cosine kernel is inference-only and the embeddings require a gradient"
-        elif grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+        elif self._wants_grad(image, features):
             reason = "the fused cosine kernel is inference-only and the call wants a gradient for the upsampler or its inputs"
         elif features.dtype != torch.bfloat16:
             reason = f"the fused cosine kernel reads bfloat16 features, got {features.dtype}"
@@ -1435,8 +1442,7 @@ class NAF(nn.Module):
                 raise TypeError(f"confusion must be True or an int64 [N, N] tensor, got {type(confusion).__name__}")
             ops._check_confusion(confusion, weight.shape[0], features.device, "naf(..., confusion=...)")
         if not (image.is_cuda and features.is_cuda and weight.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
-                               f"image on {image.device}, features on {features.device}, head on {weight.device}")
+            raise _rocm_only(image=image, features=features, head=weight)
         return weight, bias, (ho, wo), target
 
     def _head_operands(self, image, features, weight, bias, out_size, head_grad, out_dtype=torch.float32):
@@ -1459,7 +1465,7 @@ class NAF(nn.Module):
         if image.shape[0] == 0:
             return torch.empty((0, ho, wo, N), dtype=weight.dtype, device=features.device).permute(0, 3, 1, 2)
         grad = torch.is_grad_enabled()
-        if grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters()))):
+        if self._wants_grad(image, features):
             # a gradient for the upsampler or its inputs: today's differentiable forward, then the head (unfused)
             return _apply_head(head, self.forward_train(image, features, output_size, amp="auto"))
         head_grad = grad and (weight.requires_grad or (bias is not None and bias.requires_grad))
@@ -1478,7 +1484,7 @@ class NAF(nn.Module):
         ignore_index = int(ignore_index)
         pack = lambda loss, labels: (loss, labels) if (target is not None and predict) else (loss if target is not None else labels)
         grad = torch.is_grad_enabled()
-        if B == 0 or (grad and (image.requires_grad or features.requires_grad or (self.training and any(p.requires_grad for p in self.parameters())))):
+        if B == 0 or self._wants_grad(image, features):
             # an empty batch (what torch returns for empty inputs of these shapes), or a gradient for the upsampler or its inputs: the
             # logits call (unfused there), then the objective as torch ops
             logits = self._forward_head(image, features, output_size, False, head).float()
@@ -1519,8 +1525,7 @@ class NAF(nn.Module):
 
     def _forward_inference(self, image, features, output_size, return_weights=False):
         if not (image.is_cuda and features.is_cuda):
-            raise RuntimeError("naf_amd.NAF runs only on a ROCm device (HIP kernels, no CPU fallback); got "
-                               f"image on {image.device}, features on {features.device}")
+            raise _rocm_only(image=image, features=features)
         if image.dim() != 4 or features.dim() != 4 or image.shape[0] != features.shape[0]:
             raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
         if image.shape[0] == 0:

@@ -614,8 +614,53 @@ def pack_values(v: torch.Tensor) -> torch.Tensor:
     return vp
 
 
+# ---- what every attention entry asks of its arguments; ``who`` names the entry in the messages -----------------------------------------
+def _rope_table_ptrs(who: str, rope_tables, Ho: int, Wo: int, Dq: int, whole_pairs: bool = False):
+    """The two pointers of a ``rope_tables`` pair after checking it against the queries' [.., Ho, Wo, Dq]; ``whole_pairs`` also refuses
+    Dq % 4 (the point kernel rotates whole (y, x) pairs itself)."""
+    ty, tx = rope_tables
+    if (whole_pairs and Dq % 4) or ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
+            or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
+        raise ValueError(f"{who}: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
+    return ty.data_ptr(), tx.data_ptr()
+
+
+def _check_operands(who: str, operands, *, gpu: bool = True, shape_first: bool = False) -> None:
+    """The 5-D operand checks: ``operands`` is (tensor, name, dtypes) triples, ``dtypes`` one of ``_BF16`` / ``_BF16_F16`` below (the
+    dtypes the entry reads there and their wording in the message) or None for any.  Per operand, in this order: a ROCm device
+    (``gpu``), the dtype (TypeError), 5-D with the last dim contiguous (ValueError) -- ``shape_first`` puts the last in front of the
+    dtype, as ``xna_points`` has it."""
+    for t, n, dtypes in operands:
+        if gpu:
+            _gpu(t, n)
+        shape_ok = isinstance(t, torch.Tensor) and t.dim() == 5 and t.stride(4) == 1
+        if dtypes is not None and (shape_ok or not shape_first) and t.dtype not in dtypes[0]:
+            raise TypeError(f"{who}: {n} must be {dtypes[1]}, got {t.dtype}")
+        if not shape_ok:
+            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+
+
+_BF16 = ((torch.bfloat16,), "bfloat16")
+_BF16_F16 = ((torch.bfloat16, torch.float16), "bfloat16 or float16")
+
+
+def _dense5(H: int, W: int, heads: int, D: int) -> I64x4:
+    """Strides of [B, heads, H, W, D] as a view of a dense channels-last [B, H, W, heads * D] buffer: what a shape query assumes."""
+    return I64x4(H * W * heads * D, D, W * heads * D, heads * D)
+
+
+def _fill_geometry(a, q, k, h: int, w: int, ky: int, kx: int, scale) -> None:
+    """Geometry, ``scale`` and the q / k strides of any of the attention descriptors (they share these fields).  ``k`` None: a shape
+    query without keys, the caller sets ``k_stride``."""
+    a.B, a.heads, a.Ho, a.Wo, a.Dq = q.shape
+    a.h, a.w, a.ky, a.kx = h, w, ky, kx
+    a.scale = float(scale) if scale else 0.0
+    a.q_stride = _strides4(q, (0, 1, 2, 3))
+    if k is not None:
+        a.k_stride = _strides4(k, (0, 1, 2, 3))
+
+
 def _fill_xna(q, k, v, out, logits, idx_y, idx_x, ky, kx, path, scale, rope_tables=None) -> XnaArgs:
-    B, heads, Ho, Wo, Dq = q.shape
     _, _, h, w, Dv = v.shape
     a = XnaArgs()
     a.q, a.k_lr, a.v_lr, a.out = q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr()
@@ -623,17 +668,11 @@ def _fill_xna(q, k, v, out, logits, idx_y, idx_x, ky, kx, path, scale, rope_tabl
     a.idx_y = idx_y.data_ptr() if idx_y is not None else None
     a.idx_x = idx_x.data_ptr() if idx_x is not None else None
     if rope_tables is not None:
-        ty, tx = rope_tables
-        if ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (q.shape[2], 2, q.shape[4] // 4) \
-                or tuple(tx.shape) != (q.shape[3], 2, q.shape[4] // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
-            raise ValueError("xna: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
-        a.rope_tab_y, a.rope_tab_x = ty.data_ptr(), tx.data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
+        a.rope_tab_y, a.rope_tab_x = _rope_table_ptrs("xna", rope_tables, q.shape[2], q.shape[3], q.shape[4])
+    _fill_geometry(a, q, k, h, w, ky, kx, scale)
+    a.Dv = Dv
     a.out_dtype = _DT_VALUES[out.dtype]
     a.path = _PATH[path]
-    a.scale = float(scale) if scale else 0.0
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = _strides4(k, (0, 1, 2, 3))
     a.v_stride = _strides4(v, (0, 1, 2, 3))
     a.o_stride = _strides4(out, (0, 1, 2, 3))
     return a
@@ -663,12 +702,7 @@ def xna_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, kernel_
             raise ValueError(f"xna_forward: out must be a [B, heads, Ho, Wo, Dv] = {want} buffer on q's device ({q.device}) with Dv contiguous, got "
                              + (f"shape {tuple(out.shape)}, strides {tuple(out.stride())} on {out.device}" if isinstance(out, torch.Tensor) else type(out).__name__))
     half = v_lr.dtype == torch.float16 or out_dtype == torch.float16 or (out is not None and out.dtype == torch.float16)
-    for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
-        _gpu(t, n)
-        if t.dtype != torch.bfloat16 and not (half and t is v_lr):
-            raise TypeError(f"xna_forward: {n} must be bfloat16, got {t.dtype}")
-        if t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"xna_forward: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    _check_operands("xna_forward", ((q, "q", _BF16), (k_lr, "k_lr", _BF16), (v_lr, "v_lr", None if half else _BF16)))
     if half and not (v_lr.dtype == torch.float16 and out_dtype == torch.float16 and (out is None or out.dtype == torch.float16)):
         raise TypeError(f"xna_forward: float16 values go with out_dtype=torch.float16 and only with it "
                         f"(v_lr {v_lr.dtype}, out_dtype {out_dtype}{'' if out is None else f', out {out.dtype}'})")
@@ -713,14 +747,8 @@ def xna_points(q: torch.Tensor, k_lr: torch.Tensor, v_lr: Optional[torch.Tensor]
     rows; nothing is read for it.  ``logits`` / ``probs`` / ``out``: a caller's dense fp32 buffers of exactly those shapes to write instead
     (giving one asks for that output).  N = 0 launches nothing."""
     who = "xna_points"
-    for t, n in ((q, "q"), (k_lr, "k_lr")) + (((v_lr, "v_lr"),) if v_lr is not None else ()):
-        if not isinstance(t, torch.Tensor) or t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
-        if t is v_lr:
-            if t.dtype not in (torch.bfloat16, torch.float16):
-                raise TypeError(f"{who}: v_lr must be bfloat16 or float16, got {t.dtype}")
-        elif t.dtype != torch.bfloat16:
-            raise TypeError(f"{who}: {n} must be bfloat16, got {t.dtype}")
+    _check_operands(who, ((q, "q", _BF16), (k_lr, "k_lr", _BF16)) + (((v_lr, "v_lr", _BF16_F16),) if v_lr is not None else ()),
+                    gpu=False, shape_first=True)
     ky, kx = _ksize(kernel_size)
     B, heads, Ho, Wo, Dq = q.shape
     h, w = int(k_lr.shape[2]), int(k_lr.shape[3])
@@ -746,11 +774,7 @@ def xna_points(q: torch.Tensor, k_lr: torch.Tensor, v_lr: Optional[torch.Tensor]
         if buf is not None and (not isinstance(buf, torch.Tensor) or buf.dtype != torch.float32 or tuple(buf.shape) != shape
                                 or not buf.is_contiguous() or buf.device != q.device):
             raise ValueError(f"{who}: {n} must be a dense float32 {shape} buffer on q's device")
-    if rope_tables is not None:
-        ty, tx = rope_tables
-        if Dq % 4 or ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
-                or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
-            raise ValueError(f"{who}: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
+    rope_ptrs = None if rope_tables is None else _rope_table_ptrs(who, rope_tables, Ho, Wo, Dq, whole_pairs=True)
     for t, n in ((q, "q"), (k_lr, "k_lr"), (points, "points")) + (((v_lr, "v_lr"),) if v_lr is not None else ()):
         _gpu(t, n)
         if t.device != q.device:
@@ -771,16 +795,14 @@ def xna_points(q: torch.Tensor, k_lr: torch.Tensor, v_lr: Optional[torch.Tensor]
     a = _lib.XnaPointsArgs()
     a.q, a.k_lr, a.v_lr, a.points = q.data_ptr(), k_lr.data_ptr(), (v_lr.data_ptr() if v_lr is not None else None), points.data_ptr()
     a.idx_y, a.idx_x = iy.data_ptr(), ix.data_ptr()
-    if rope_tables is not None:
-        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    if rope_ptrs is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_ptrs
     a.logits = logits.data_ptr() if logits is not None else None
     a.probs = probs.data_ptr() if probs is not None else None
     a.out = out.data_ptr() if out is not None else None
-    a.N, a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = N, B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
+    _fill_geometry(a, q, k_lr, h, w, ky, kx, scale)
+    a.N, a.Dv = N, Dv
     a.v_dtype = _DT_VALUES[v_lr.dtype] if v_lr is not None else _lib.NAF_BF16
-    a.scale = float(scale) if scale else 0.0
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = _strides4(k_lr, (0, 1, 2, 3))
     if v_lr is not None:
         a.v_stride = _strides4(v_lr, (0, 1, 2, 3))
     with torch.cuda.device(dev), _Timed("xna_points"):
@@ -790,14 +812,13 @@ def xna_points(q: torch.Tensor, k_lr: torch.Tensor, v_lr: Optional[torch.Tensor]
 
 
 def _fill_xna_bwd(q, k, v, dout, dq, dk, dv, ky, kx, scale) -> XnaBwdArgs:
-    B, heads, Ho, Wo, Dq = q.shape
     _, _, h, w, Dv = v.shape
     a = XnaBwdArgs()
     a.q, a.k_lr, a.v_lr, a.dout, a.dq = q.data_ptr(), k.data_ptr(), v.data_ptr(), dout.data_ptr(), dq.data_ptr()
     a.dk_lr, a.dv_lr = dk.data_ptr(), dv.data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
-    a.scale = float(scale) if scale else 0.0
-    a.q_stride, a.k_stride, a.v_stride = _strides4(q, (0, 1, 2, 3)), _strides4(k, (0, 1, 2, 3)), _strides4(v, (0, 1, 2, 3))
+    _fill_geometry(a, q, k, h, w, ky, kx, scale)
+    a.Dv = Dv
+    a.v_stride = _strides4(v, (0, 1, 2, 3))
     a.dout_stride, a.dq_stride = _strides4(dout, (0, 1, 2, 3)), _strides4(dq, (0, 1, 2, 3))
     return a
 
@@ -823,8 +844,7 @@ def _bwd_query_args(q, k_lr, v_lr, kernel_size) -> XnaBwdArgs:
     a = _fill_xna_bwd(q, k_lr, v_lr, q, q, q, q, *_ksize(kernel_size), None)
     B, heads, Ho, Wo, Dq = q.shape
     Dv = v_lr.shape[-1]
-    a.dout_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
-    a.dq_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
+    a.dout_stride, a.dq_stride = _dense5(Ho, Wo, heads, Dv), _dense5(Ho, Wo, heads, Dq)
     return a
 
 
@@ -1017,11 +1037,7 @@ def _check_regress_target(who: str, target, shape, device) -> None:
 
 
 def _check_mse_operands(who: str, q, k_lr, v_lr, target) -> None:
-    for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
-        if t.dtype != torch.bfloat16:
-            raise TypeError(f"{who}: {n} must be bfloat16, got {t.dtype}")
-        if t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    _check_operands(who, ((q, "q", _BF16), (k_lr, "k_lr", _BF16), (v_lr, "v_lr", _BF16)), gpu=False)
     B, heads, Ho, Wo, Dq = q.shape
     _, _, h, w, Dv = v_lr.shape
     if tuple(k_lr.shape) != (B, heads, h, w, Dq) or v_lr.shape[:2] != (B, heads):
@@ -1037,7 +1053,7 @@ def _fill_xna_mse(q, k_lr, v_lr, target, dout, ky, kx, scale) -> "_lib.XnaMSEArg
     m.a.out_dtype = _lib.NAF_BF16
     if dout is None:
         m.a.out = None
-        m.a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+        m.a.o_stride = _dense5(Ho, Wo, heads, Dv)
     m.target, m.target_dtype = target.data_ptr(), _DT[target.dtype]
     m.target_stride = _strides4(target, (0, 1, 2, 3))
     return m
@@ -1108,10 +1124,8 @@ def xna_mse_auto(B: int, heads: int, Dq: int, Dv: int, lr_size, out_size, kernel
     a.q = a.k_lr = a.v_lr = a.out = 4096               # shape / alignment query only
     a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, ky, kx
     a.out_dtype, a.path, a.scale = _DT[out_dtype], _lib.XNA_AUTO, 0.0
-    a.q_stride = I64x4(Ho * Wo * heads * Dq, Dq, Wo * heads * Dq, heads * Dq)
-    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
-    a.v_stride = I64x4(h * w * heads * Dv, Dv, w * heads * Dv, heads * Dv)
-    a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    a.q_stride, a.k_stride = _dense5(Ho, Wo, heads, Dq), _dense5(h, w, heads, Dq)
+    a.v_stride, a.o_stride = _dense5(h, w, heads, Dv), _dense5(Ho, Wo, heads, Dv)
     if lib.naf_xna_select(C.byref(a)) != _lib.XNA_UNION:
         return False
     a.out_dtype = _lib.NAF_BF16
@@ -1191,20 +1205,38 @@ def _fill_xna_head(q, k, pv, bias, out, n_out, ky, kx, path, scale, rope_tables=
     a.q, a.k_lr, a.pv_lr, a.out = q.data_ptr(), k.data_ptr(), pv.data_ptr(), out.data_ptr()
     a.bias = bias.data_ptr() if bias is not None else None
     if rope_tables is not None:
-        ty, tx = rope_tables
-        if ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
-                or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
-            raise ValueError("xna_head: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
-        a.rope_tab_y, a.rope_tab_x = ty.data_ptr(), tx.data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, int(n_out), ky, kx
+        a.rope_tab_y, a.rope_tab_x = _rope_table_ptrs("xna_head", rope_tables, Ho, Wo, Dq)
+    _fill_geometry(a, q, k, h, w, ky, kx, scale)
+    a.N = int(n_out)
     a.out_dtype = _DT[out.dtype]
     a.path = _lib.XNA_HEAD_FUSED if path == "fused" else _lib.XNA_HEAD_AUTO
-    a.scale = float(scale) if scale else 0.0
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = _strides4(k, (0, 1, 2, 3))
     a.pv_stride = _strides4(pv, (0, 1, 2, 3))
     a.o_stride = _strides3(out)
     return a
+
+
+def _head_route(a, entry: str, q, lr_size, n_out: int, kernel_size, rope_tables, Dv: Optional[int] = None) -> str:
+    """The answer of ``naf_xna_head_select`` / ``naf_xna_cos_select`` (``entry``) to a shape / alignment query: fills the fresh descriptor
+    ``a`` for queries ``q`` with dense channels-last keys, projected values, (``Dv``: the cosine head's) values and output."""
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    _, heads, Ho, Wo, Dq = q.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    npad, n_out = head_npad(n_out), int(n_out)
+    a.q = a.k_lr = a.pv_lr = a.out = ptr = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    _fill_geometry(a, q, None, h, w, ky, kx, None)
+    a.N, a.path = n_out, _lib.XNA_HEAD_AUTO
+    a.k_stride = _dense5(h, w, heads, Dq)
+    a.pv_stride = I64x4(heads * h * w * npad, h * w * npad, w * npad, npad)
+    a.o_stride = I64x3(Ho * Wo * n_out, Wo * n_out, n_out)
+    if Dv is not None:
+        a.v_lr, a.Dv, a.logit_scale, a.v_stride = ptr, Dv, 1.0, _dense5(h, w, heads, Dv)
+    sel = getattr(lib, entry)(C.byref(a))
+    if sel == -1:
+        _lib.check(1, entry)
+    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
 
 
 def xna_head_select(q: torch.Tensor, lr_size, n_out: int, kernel_size, *, out_dtype: torch.dtype = torch.float32, rope_tables=None) -> str:
@@ -1213,36 +1245,15 @@ def xna_head_select(q: torch.Tensor, lr_size, n_out: int, kernel_size, *, out_dt
     with ``rope_tables`` the un-rotated guidance.  A host-side query: nothing is launched or read.  Invalid arguments raise ValueError."""
     if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or out_dtype not in _DT or not 1 <= int(n_out) <= 256:
         return "composed"
-    lib = _lib.load()
-    ky, kx = _ksize(kernel_size)
-    B, heads, Ho, Wo, Dq = q.shape
-    h, w = int(lr_size[0]), int(lr_size[1])
-    npad = head_npad(n_out)
     a = XnaHeadArgs()
-    a.q = a.k_lr = a.pv_lr = a.out = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
-    if rope_tables is not None:
-        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, int(n_out), ky, kx
-    a.out_dtype, a.path, a.scale = _DT[out_dtype], _lib.XNA_HEAD_AUTO, 0.0
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
-    a.pv_stride = I64x4(heads * h * w * npad, h * w * npad, w * npad, npad)
-    a.o_stride = I64x3(Ho * Wo * int(n_out), Wo * int(n_out), int(n_out))
-    sel = lib.naf_xna_head_select(C.byref(a))
-    if sel == -1:
-        _lib.check(1, "naf_xna_head_select")
-    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
+    a.out_dtype = _DT[out_dtype]
+    return _head_route(a, "naf_xna_head_select", q, lr_size, n_out, kernel_size, rope_tables)
 
 
 def _check_head_operands(who: str, q, k_lr, pv_lr, bias, kernel_size, n_out, path):
     """What ``xna_head_forward`` and ``xna_head_objective`` ask of their operands; ``who`` names the caller in the messages.
     Returns (ky, kx, B, heads, Ho, Wo, Dq, h, w, npad, n_out)."""
-    for t, n in ((q, "q"), (k_lr, "k_lr"), (pv_lr, "pv_lr")):
-        _gpu(t, n)
-        if t.dtype != torch.bfloat16:
-            raise TypeError(f"{who}: {n} must be bfloat16, got {t.dtype}")
-        if t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    _check_operands(who, ((q, "q", _BF16), (k_lr, "k_lr", _BF16), (pv_lr, "pv_lr", _BF16)))
     if path not in _HEAD_PATHS:
         raise ValueError(f"{who}: path must be one of {_HEAD_PATHS}, got {path!r}")
     ky, kx = _ksize(kernel_size)
@@ -1308,10 +1319,7 @@ def normalize_embeddings(embeddings: torch.Tensor) -> torch.Tensor:
 
 
 def _check_cos_operands(who: str, q, k_lr, v_lr, embeddings, path):
-    for t, n in ((q, "q"), (k_lr, "k_lr"), (v_lr, "v_lr")):
-        _gpu(t, n)
-        if t.dim() != 5 or t.stride(4) != 1:
-            raise ValueError(f"{who}: {n} must be 5-D [B, heads, H, W, D] with D contiguous")
+    _check_operands(who, ((q, "q", None), (k_lr, "k_lr", None), (v_lr, "v_lr", None)))
     if q.dtype != torch.bfloat16 or k_lr.dtype != torch.bfloat16:
         raise TypeError(f"{who}: q and k_lr must be bfloat16, got {q.dtype} / {k_lr.dtype}")
     if path not in _HEAD_PATHS:
@@ -1335,17 +1343,11 @@ def _fill_xna_cos(q, k, pv, v, out, norms, n_out, ky, kx, path, scale, logit_sca
     a.q, a.k_lr, a.pv_lr, a.v_lr, a.out = q.data_ptr(), k.data_ptr(), pv.data_ptr(), v.data_ptr(), out.data_ptr()
     a.norms = norms.data_ptr() if norms is not None else None
     if rope_tables is not None:
-        ty, tx = rope_tables
-        if ty.dtype != torch.float32 or tx.dtype != torch.float32 or tuple(ty.shape) != (Ho, 2, Dq // 4) \
-                or tuple(tx.shape) != (Wo, 2, Dq // 4) or not (ty.is_contiguous() and tx.is_contiguous()):
-            raise ValueError("xna_cos: rope_tables must be the fp32 [Ho,2,Dq/4] / [Wo,2,Dq/4] pair from ops.rope_tables")
-        a.rope_tab_y, a.rope_tab_x = ty.data_ptr(), tx.data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, int(n_out), ky, kx
+        a.rope_tab_y, a.rope_tab_x = _rope_table_ptrs("xna_cos", rope_tables, Ho, Wo, Dq)
+    _fill_geometry(a, q, k, h, w, ky, kx, scale)
+    a.Dv, a.N = Dv, int(n_out)
     a.path = _lib.XNA_HEAD_FUSED if path == "fused" else _lib.XNA_HEAD_AUTO
-    a.scale = float(scale) if scale else 0.0
     a.logit_scale = float(logit_scale)
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = _strides4(k, (0, 1, 2, 3))
     a.pv_stride = _strides4(pv, (0, 1, 2, 3))
     a.v_stride = _strides4(v, (0, 1, 2, 3))
     a.o_stride = _strides3(out)
@@ -1362,26 +1364,7 @@ def xna_cos_select(q: torch.Tensor, lr_size, Dv: int, n_out: int, kernel_size, *
     bfloat16 values).  A host-side query: nothing is launched or read, CPU tensors do.  Invalid arguments raise ValueError."""
     if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or value_dtype != torch.bfloat16 or not 1 <= int(n_out) <= 256 or int(Dv) < 1:
         return "composed"
-    lib = _lib.load()
-    ky, kx = _ksize(kernel_size)
-    B, heads, Ho, Wo, Dq = q.shape
-    h, w = int(lr_size[0]), int(lr_size[1])
-    npad, Dv = head_npad(n_out), int(Dv)
-    a = _lib.XnaCosArgs()
-    a.q = a.k_lr = a.pv_lr = a.v_lr = a.out = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
-    if rope_tables is not None:
-        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.N, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, Dv, int(n_out), ky, kx
-    a.path, a.scale, a.logit_scale = _lib.XNA_HEAD_AUTO, 0.0, 1.0
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
-    a.pv_stride = I64x4(heads * h * w * npad, h * w * npad, w * npad, npad)
-    a.v_stride = I64x4(h * w * heads * Dv, Dv, w * heads * Dv, heads * Dv)
-    a.o_stride = I64x3(Ho * Wo * int(n_out), Wo * int(n_out), int(n_out))
-    sel = lib.naf_xna_cos_select(C.byref(a))
-    if sel == -1:
-        _lib.check(1, "naf_xna_cos_select")
-    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
+    return _head_route(_lib.XnaCosArgs(), "naf_xna_cos_select", q, lr_size, n_out, kernel_size, rope_tables, Dv=int(Dv))
 
 
 def cosine_from_features(f: torch.Tensor, e_hat: torch.Tensor, logit_scale: float = 1.0, return_norms: bool = False):
@@ -1770,12 +1753,9 @@ def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables
     a = XnaArgs()
     a.q = a.k_lr = a.v_lr = a.out = q.data_ptr()      # shape / alignment query only: nothing is dereferenced
     a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
-    a.B, a.heads, a.Ho, a.Wo, a.h, a.w, a.Dq, a.Dv, a.ky, a.kx = B, heads, Ho, Wo, h, w, Dq, int(Dv), ky, kx
-    a.out_dtype, a.path, a.scale = _DT_VALUES[out_dtype], _PATH[path], 0.0
-    a.q_stride = _strides4(q, (0, 1, 2, 3))
-    a.k_stride = I64x4(h * w * heads * Dq, Dq, w * heads * Dq, heads * Dq)
-    a.v_stride = I64x4(h * w * heads * Dv, Dv, w * heads * Dv, heads * Dv)
-    a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    _fill_geometry(a, q, None, h, w, ky, kx, None)
+    a.Dv, a.out_dtype, a.path = int(Dv), _DT_VALUES[out_dtype], _PATH[path]
+    a.k_stride, a.v_stride, a.o_stride = _dense5(h, w, heads, Dq), _dense5(h, w, heads, Dv), _dense5(Ho, Wo, heads, Dv)
     return lib.naf_xna_select(C.byref(a)) == _lib.XNA_MFMA
 
 
@@ -1788,7 +1768,7 @@ def xna_select(q, k_lr, v_lr, kernel_size, out_dtype=torch.bfloat16, return_logi
     out = torch.empty((1, 1, 1, heads, Dv), dtype=out_dtype, device=q.device).permute(0, 3, 1, 2, 4)
     fake = torch.empty((1,), dtype=torch.float32, device=q.device) if return_logits else None
     a = _fill_xna(q, k_lr, v_lr, out, fake, None, None, ky, kx, path, None)
-    a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    a.o_stride = _dense5(Ho, Wo, heads, Dv)
     sel = lib.naf_xna_select(C.byref(a))
     if sel < 0:
         _lib.check(-sel, "naf_xna_select")
@@ -1805,7 +1785,7 @@ def xna_union_plan(q, k_lr, v_lr, kernel_size) -> Optional[Dict[str, int]]:
     Dv = v_lr.shape[-1]
     a = _fill_xna(q, k_lr, v_lr, q, None, None, None, ky, kx, "auto", None)
     a.out_dtype = _lib.NAF_BF16
-    a.o_stride = I64x4(Ho * Wo * heads * Dv, Dv, Wo * heads * Dv, heads * Dv)
+    a.o_stride = _dense5(Ho, Wo, heads, Dv)
     out = (C.c_int32 * 7)()
     if lib.naf_xna_union_plan(C.byref(a), out) != 1:
         return None
