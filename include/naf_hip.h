@@ -75,7 +75,9 @@ extern "C" {
  * naf_propagate_plan -- the kernel instance, key blocks, buffering and LDS naf_propagate_fwd chooses (host-only, naf_propagate_args unchanged); and
  * after that naf_image_prep_select / naf_image_prep -- resized, normalised views of one decoded frame from one launch (naf_image_prep_args); and
  * after those naf_xna_cos_select / naf_xna_cos_fwd -- the attention with a cosine head folded in: scaled cosines between the upsampled feature
- * and N embeddings, and the feature's norm (naf_xna_cos_args). */
+ * and N embeddings, and the feature's norm (naf_xna_cos_args); and after those naf_xna_cos_ce_select / naf_xna_cos_ce_fwd -- that
+ * attention with a cross-entropy on the scaled cosines in its epilogue: loss, labels, the gradient for the embeddings' projection and
+ * for the scale (naf_xna_cos_ce_args, which embeds naf_xna_cos_args unchanged). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -472,7 +474,10 @@ int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t
  *                  size, any strides {b, y, x} (out: x stride >= N).
  *   naf_xna_mse_fwd              the rules of NAF_XNA_UNION for q, k_lr, v_lr and out (the gradient); otherwise -NAF_ERR_UNSUPPORTED.
  *   naf_xna_cos_fwd              as naf_xna_head_fwd, with v_lr held to the rule of q, k_lr and pv_lr; out and norms are stored element by
- *                  element: 4-byte aligned, any strides {b, y, x} (out: x stride >= N). */
+ *                  element: 4-byte aligned, any strides {b, y, x} (out: x stride >= N).
+ *   naf_xna_cos_ce_fwd           as naf_xna_cos_fwd; dlogits held to the rule of naf_xna_head_ce_fwd's (16-byte aligned, strides {b, y, x}
+ *                  multiples of 8 elements, x stride >= dlogits_channels, else -NAF_ERR_UNSUPPORTED); target, loss, labels and dscale are
+ *                  read / stored element by element: aligned to their element size, any strides {b, y, x}. */
 
 /* ---- cross-scale neighbourhood attention forward -------------------------------------------------
  * Replaces legacy_attention (attentions.py:16-29: na2d_qk -> *scale -> softmax -> na2d_av), the fused
@@ -1350,6 +1355,60 @@ typedef struct naf_xna_cos_args {
 } naf_xna_cos_args;
 int naf_xna_cos_select(const naf_xna_cos_args* a);
 int naf_xna_cos_fwd(const naf_xna_cos_args* a, naf_stream_t stream);
+
+/* ---- ... with a classification objective on the scaled cosines (added after the cosine entries; detect by symbol) ------------
+ * Training against cosines -- a cosine classifier as a dense probe, prompt / embedding tuning for open-vocabulary segmentation, a
+ * learnable CLIP-style temperature: a cross-entropy on z[n] = s * cos[n] of naf_xna_cos_fwd.  A pixel's N cosines are in the registers
+ * of four lanes when that kernel is done, so this entry computes, per pixel and in fp32, over the N channels, with
+ * inv = 1 / max(||f||, 1e-12) and c[n] = (E^[n] . f) * inv the unscaled cosine,
+ *     lse = max z + ln sum exp(z - max z),   label = argmax z (lowest index among equal maxima),   loss = lse - z[t]
+ *     dlogits[n] = (s * inv) * (exp(z[n] - lse) - (n == t))       the gradient with respect to E^[n] . f
+ *     dscale     = sum_n (exp(z[n] - lse) - (n == t)) * c[n]      the pixel's share of dloss / ds
+ * and stores only what is asked for; neither the [B, C, Ho, Wo] features nor the [B, N, Ho, Wo] cosines need exist.  ||f|| does not depend
+ * on the embeddings, so dlogits is the whole gradient of the loss with respect to pv_lr's attention output: it is the `dout` of
+ * naf_xna_bwd for all heads at once (head stride 0) and that entry's dv_lr is dloss / dpv_lr; the caller carries it to E through the
+ * low-res projection and the normalisation.  dloss / ds is the sum of the dscale map.
+ *   cos        naf_xna_cos_args as for naf_xna_cos_fwd, except that `out` may be NULL; when given it receives the scaled cosines, bit for
+ *              bit what naf_xna_cos_fwd stores for the same scale; norms as there
+ *   target     device int64 [B, Ho, Wo], element strides t_stride {b, y, x}; NULL when only labels / cosines are wanted.  A pixel is
+ *              IGNORED when target == ignore_index or target is outside [0, N) (the rule of naf_xna_head_ce_args)
+ *   loss       device float [B, Ho, Wo] (loss_stride), or NULL: lse - z[t], 0 for an ignored pixel.  Needs target.  The caller reduces it
+ *   labels     device uint8 [B, Ho, Wo] (labels_stride), or NULL; written for ignored pixels too
+ *   dlogits    device bf16 [B, Ho, Wo, dlogits_channels] (dlogits_stride {b, y, x}, channel axis contiguous), 16-byte aligned, strides
+ *              multiples of 8 elements, or NULL: rounded once to bf16, NOT divided by the number of valid pixels; a zero row for an ignored
+ *              pixel AND for a pixel with ||f|| = 0 (every cosine is 0 there, the loss of a counted pixel is ln N and its exact gradient
+ *              is 0 because f = 0; s * 1e12 * (softmax - onehot) is never stored).  EVERY one of the dlogits_channels channels is written
+ *              (zeros from N up), so the buffer needs no clearing.  dlogits_channels: a multiple of 8, >= N rounded up to 16, <= 256.  Needs target
+ *   dscale     device float [B, Ho, Wo] (dscale_stride), or NULL: 0 for an ignored pixel.  Needs target
+ *   logit_scale_ptr   NULL, or one fp32 device value that is used in place of cos.logit_scale (read once by every workgroup, after
+ *              its attention): a learnable temperature costs no host synchronisation per step.  cos.logit_scale must still be finite
+ * No atomics, nothing crosses a workgroup: every output is deterministic, bit for bit.  A power-of-two factor on the values changes no
+ * bit of loss or labels.
+ * Served: what naf_xna_cos_fwd serves (profiles/cosine_objective.txt holds the compiler's figures of every instantiation).
+ * naf_xna_cos_ce_select answers as naf_xna_cos_select does and additionally refuses: no output requested; loss / dlogits / dscale without
+ * target; a bad dlogits_channels or a dlogits x stride below it; a loss / dscale that is not 4-byte aligned; non-zero reserved fields
+ * (all -NAF_ERR_INVALID); a dlogits that is not 16-byte aligned or whose strides are not multiples of 8 elements (-NAF_ERR_UNSUPPORTED).
+ * The differences from torch.nn.functional.cross_entropy are those listed for naf_xna_head_ce_args.  The struct must be
+ * zero-initialised.  Caller-owned memory and stream; capturable; no workspace. */
+typedef struct naf_xna_cos_ce_args {
+    naf_xna_cos_args cos; /* cos.out may be NULL */
+    const int64_t* target;
+    float* loss;
+    uint8_t* labels;
+    void* dlogits;
+    float* dscale;
+    const float* logit_scale_ptr;
+    int64_t ignore_index;
+    int32_t dlogits_channels;
+    int32_t reserved; /* must be 0 */
+    int64_t t_stride[3];
+    int64_t loss_stride[3];
+    int64_t labels_stride[3];
+    int64_t dlogits_stride[3];
+    int64_t dscale_stride[3];
+} naf_xna_cos_ce_args;
+int naf_xna_cos_ce_select(const naf_xna_cos_ce_args* a);
+int naf_xna_cos_ce_fwd(const naf_xna_cos_ce_args* a, naf_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,16 @@ class XnaCosArgs(C.Structure):
     ]
 
 
+class XnaCosCEArgs(C.Structure):
+    """naf_xna_cos_ce_args (added after the cosine entries, detected by symbol): naf_xna_cos_args plus the classification epilogue's maps."""
+    _fields_ = [
+        ("cos", XnaCosArgs), ("target", C.c_void_p), ("loss", C.c_void_p), ("labels", C.c_void_p), ("dlogits", C.c_void_p),
+        ("dscale", C.c_void_p), ("logit_scale_ptr", C.c_void_p),
+        ("ignore_index", C.c_int64), ("dlogits_channels", C.c_int32), ("reserved", C.c_int32),
+        ("t_stride", I64x3), ("loss_stride", I64x3), ("labels_stride", I64x3), ("dlogits_stride", I64x3), ("dscale_stride", I64x3),
+    ]
+
+
 class XnaMSEArgs(C.Structure):
     """naf_xna_mse_args (added after the PCA entries, detected by symbol): naf_xna_args plus the regression target of the training objective."""
     _fields_ = [
@@ -386,6 +396,8 @@ SIGNATURES = {
     "naf_xna_head_cm_fwd": (C.c_int, [C.POINTER(XnaHeadCMArgs), C.c_void_p]),
     "naf_xna_cos_select": (C.c_int, [C.POINTER(XnaCosArgs)]),
     "naf_xna_cos_fwd": (C.c_int, [C.POINTER(XnaCosArgs), C.c_void_p]),
+    "naf_xna_cos_ce_select": (C.c_int, [C.POINTER(XnaCosCEArgs)]),
+    "naf_xna_cos_ce_fwd": (C.c_int, [C.POINTER(XnaCosCEArgs), C.c_void_p]),
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
     "naf_propagate_plan": (C.c_int, [C.POINTER(PropagateArgs), C.POINTER(C.c_int32)]),

@@ -497,13 +497,14 @@ int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream) {
 }
 
 // ---- the cosine head: scaled cosines between the upsampled feature and N embeddings (after the image-preparation entries) ----
-static int xna_cos_validate(const naf_xna_cos_args* a) {
+// need_out = false: the classification entry (naf_xna_cos_ce_*), where `out` is optional
+static int xna_cos_validate(const naf_xna_cos_args* a, bool need_out = true) {
     NAF_REQUIRE(a != nullptr, "naf_xna_cos_fwd: args is NULL");
-    int rc = xna_headsum_validate_sizes("naf_xna_cos_fwd", a, a->Dv, a->v_lr && a->out);
+    int rc = xna_headsum_validate_sizes("naf_xna_cos_fwd", a, a->Dv, a->v_lr && (a->out || !need_out));
     if (rc == NAF_OK) rc = xna_headsum_validate_route("naf_xna_cos_fwd", a);
     if (rc != NAF_OK) return rc;
     NAF_REQUIRE(a->v_stride[3] >= a->Dv, "naf_xna_cos_fwd: v_lr x stride %lld smaller than Dv %d", (long long)a->v_stride[3], a->Dv);
-    NAF_REQUIRE(a->o_stride[2] >= a->N, "naf_xna_cos_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
+    NAF_REQUIRE(a->out == nullptr || a->o_stride[2] >= a->N, "naf_xna_cos_fwd: out x stride %lld smaller than N %d", (long long)a->o_stride[2], a->N);
     NAF_REQUIRE(reinterpret_cast<uintptr_t>(a->out) % 4 == 0 && reinterpret_cast<uintptr_t>(a->norms) % 4 == 0, "naf_xna_cos_fwd: out / norms not 4-byte aligned");
     NAF_REQUIRE(a->logit_scale == a->logit_scale && a->logit_scale - a->logit_scale == 0.f, "naf_xna_cos_fwd: logit_scale must be finite");
     NAF_REQUIRE(a->reserved[0] == 0 && a->reserved[1] == 0, "naf_xna_cos_fwd: reserved fields must be 0");
@@ -520,6 +521,41 @@ int naf_xna_cos_fwd(const naf_xna_cos_args* a, naf_stream_t stream) {
     const int sel = naf_xna_cos_select(a);
     if (sel < 0) return -sel;
     return naf_launch_xna_cos(a, xna_scale(a->scale, a->Dq), static_cast<hipStream_t>(stream));
+}
+
+// ---- ... and a classification objective on the scaled cosines folded into its epilogue (after the cosine entries) ----
+static int xna_cos_ce_validate(const naf_xna_cos_ce_args* c) {
+    NAF_REQUIRE(c != nullptr, "naf_xna_cos_ce: args is NULL");
+    const int rc = xna_cos_validate(&c->cos, false);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(c->cos.out || c->cos.norms || c->loss || c->labels || c->dlogits || c->dscale,
+                "naf_xna_cos_ce: no output requested (out, norms, loss, labels, dlogits and dscale are all NULL)");
+    NAF_REQUIRE(c->target != nullptr || (c->loss == nullptr && c->dlogits == nullptr && c->dscale == nullptr), "naf_xna_cos_ce: loss, dlogits and dscale need a target");
+    NAF_REQUIRE(reinterpret_cast<uintptr_t>(c->target) % 8 == 0, "naf_xna_cos_ce: target not 8-byte aligned");
+    NAF_REQUIRE(reinterpret_cast<uintptr_t>(c->loss) % 4 == 0 && reinterpret_cast<uintptr_t>(c->dscale) % 4 == 0 && reinterpret_cast<uintptr_t>(c->logit_scale_ptr) % 4 == 0,
+                "naf_xna_cos_ce: loss / dscale / logit_scale_ptr not 4-byte aligned");
+    if (c->dlogits != nullptr) {
+        const int npad = (c->cos.N + 15) & ~15;
+        NAF_REQUIRE(c->dlogits_channels % 8 == 0, "naf_xna_cos_ce: dlogits_channels must be a multiple of 8, got %d", c->dlogits_channels);
+        NAF_REQUIRE(c->dlogits_channels >= npad, "naf_xna_cos_ce: dlogits_channels %d smaller than N rounded up to 16 (%d)", c->dlogits_channels, npad);
+        NAF_REQUIRE(c->dlogits_channels <= 256, "naf_xna_cos_ce: dlogits_channels %d above 256", c->dlogits_channels);
+        NAF_REQUIRE(c->dlogits_stride[2] >= c->dlogits_channels, "naf_xna_cos_ce: dlogits x stride %lld smaller than dlogits_channels %d",
+                    (long long)c->dlogits_stride[2], c->dlogits_channels);
+    }
+    NAF_REQUIRE(c->reserved == 0, "naf_xna_cos_ce: reserved field must be 0");
+    return NAF_OK;
+}
+
+int naf_xna_cos_ce_select(const naf_xna_cos_ce_args* a) {
+    int rc = xna_cos_ce_validate(a);
+    if (rc == NAF_OK) rc = naf_xna_cos_ce_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
+}
+
+int naf_xna_cos_ce_fwd(const naf_xna_cos_ce_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_cos_ce_select(a);
+    if (sel < 0) return -sel;
+    return naf_launch_xna_cos_ce(a, xna_scale(a->cos.scale, a->cos.Dq), static_cast<hipStream_t>(stream));
 }
 
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {

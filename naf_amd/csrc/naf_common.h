@@ -81,6 +81,8 @@ int naf_launch_xna_head_cm(const naf_xna_head_cm_args* a, float scale, hipStream
 int naf_xna_head_ce_eligible(const naf_xna_head_ce_args* a);                          // xna_head.hip: naf_xna_head_eligible plus the dlogits layout
 int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s);     // xna_cos.hip: the cosine head
 int naf_xna_cos_eligible(const naf_xna_cos_args* a);                              // xna_cos.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
+int naf_launch_xna_cos_ce(const naf_xna_cos_ce_args* a, float scale, hipStream_t s);   // xna_cos.hip: ... with the classification epilogue
+int naf_xna_cos_ce_eligible(const naf_xna_cos_ce_args* a);                            // xna_cos.hip: naf_xna_cos_eligible plus the dlogits layout
 int naf_tile_span(int L_out, int L_in, int k);                                   // xna_rows.hip: low-res columns under 16 consecutive queries
 // `sg` (0.4.3): the gradient of the scores (naf_xna_bwd_scores); nullptr = the plain backward, the same launches as before
 int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, const naf_xna_bwd_scores_args* sg = nullptr);   // xna_bwd.hip

@@ -29,22 +29,77 @@ int naf_xna_cos_eligible(const naf_xna_cos_args* a) {
     return NAF_OK;
 }
 
-int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s) {
-    XnaCosParams p;
-    const int rc = xna_headsum_fill(p, a, scale, "naf_xna_cos_fwd");
+// What the classification epilogue asks beyond naf_xna_cos_eligible (the request is validated: naf_api.hip).
+int naf_xna_cos_ce_eligible(const naf_xna_cos_ce_args* c) {
+    const int rc = naf_xna_cos_eligible(&c->cos);
+    if (rc != NAF_OK) return rc;
+    if (!xna_cos_ce_served(c->cos.ky, xna_head_nct((c->cos.N + 15) & ~15))) {
+        naf_set_error("naf_xna_cos_ce: no fused kernel for window %d with N = %d (registers: the instantiation would spill)", c->cos.ky, c->cos.N);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    if (c->dlogits != nullptr) {
+        if (!naf_aligned(c->dlogits, 16)) {
+            naf_set_error("naf_xna_cos_ce: the fused kernel needs a 16-byte aligned dlogits");
+            return NAF_ERR_UNSUPPORTED;
+        }
+        for (int i = 0; i < 3; ++i) {
+            if (c->dlogits_stride[i] % 8) {
+                naf_set_error("naf_xna_cos_ce: the fused kernel needs dlogits strides that are multiples of 8 elements");
+                return NAF_ERR_UNSUPPORTED;
+            }
+        }
+    }
+    return NAF_OK;
+}
+
+// `who` names the entry in the messages.
+static int cos_fill(const naf_xna_cos_args* a, float scale, const char* who, XnaCosParams& p, XnaCosEpilogue& e) {
+    const int rc = xna_headsum_fill(p, a, scale, who);
     if (rc != NAF_OK) return rc;
     p.v = static_cast<const bf16_t*>(a->v_lr);
     p.dv = a->Dv;
     for (int i = 0; i < 4; ++i) p.ws[i] = a->v_stride[i];
-    XnaCosEpilogue e;
     e.norms = a->norms;
     for (int i = 0; i < 3; ++i) e.ns[i] = a->norms != nullptr ? a->norms_stride[i] : 0;
     e.logit_scale = a->logit_scale;
+    return NAF_OK;
+}
+
+int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s) {
+    XnaCosParams p;
+    XnaCosEpilogue e;
+    const int rc = cos_fill(a, scale, "naf_xna_cos_fwd", p, e);
+    if (rc != NAF_OK) return rc;
     switch (a->ky) {
 #define NAF_X(K) case K: return xna_cos_launch_ks<K>(p, e, s);
         NAF_FOR_WINDOWS(NAF_X)
 #undef NAF_X
     }
     naf_set_error("naf_xna_cos_fwd: kernel size %d has no instantiation", a->ky);
+    return NAF_ERR_UNSUPPORTED;
+}
+
+int naf_launch_xna_cos_ce(const naf_xna_cos_ce_args* c, float scale, hipStream_t s) {
+    XnaCosParams p;
+    XnaCosCEEpilogue x;
+    const int rc = cos_fill(&c->cos, scale, "naf_xna_cos_ce_fwd", p, x.cos);
+    if (rc != NAF_OK) return rc;
+    x.target = c->target;
+    x.loss = c->loss;
+    x.labels = c->labels;
+    x.dlogits = static_cast<bf16_t*>(c->dlogits);
+    x.dscale = c->dscale;
+    x.scale_ptr = c->logit_scale_ptr;
+    x.ignore_index = c->ignore_index;
+    x.gc = c->dlogits != nullptr ? c->dlogits_channels : 0;
+    for (int i = 0; i < 3; ++i) {
+        x.ts[i] = c->t_stride[i]; x.ls[i] = c->loss_stride[i]; x.bs[i] = c->labels_stride[i]; x.gs[i] = c->dlogits_stride[i]; x.ds[i] = c->dscale_stride[i];
+    }
+    switch (c->cos.ky) {
+#define NAF_X(K) case K: return xna_cos_launch_ks<K>(p, x, s);
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
+    }
+    naf_set_error("naf_xna_cos_ce_fwd: kernel size %d has no instantiation", c->cos.ky);
     return NAF_ERR_UNSUPPORTED;
 }

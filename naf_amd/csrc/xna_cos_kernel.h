@@ -25,6 +25,21 @@
 //     scalar registers the loop does not have.
 // Which (window, channel tiles) instantiations exist and which of them the dispatcher serves is decided by the compiler's figures
 // (profiles/cosine_head.txt): xna_cos_served below.
+//
+// Classification epilogue (template parameter Epi = XnaCosCEEpilogue, naf_xna_cos_ce_fwd): the cosine instantiations (Epi = XnaCosEpilogue)
+// are the code they were (`if constexpr`).  With it a pixel's N scaled cosines z[n] = s * (acc[n] * inv) sit, in fp32, in the four lanes
+// col + 16 * grp of its tile, where xna_head_kernel.h's classification epilogue finds its logits, and the arithmetic is that epilogue's:
+//     m = max z, lse = m + ln(sum exp(z - m)), label = lowest n with z[n] = m, loss = lse - z[t],
+//     g'[n] = (s * inv) * (exp(z[n] - lse) - (n == t))          rounded once to bf16: dL/d(acc[n]), the `dout` of naf_xna_bwd for all heads
+//     ds    = sum_n (exp(z[n] - lse) - (n == t)) * (acc[n] * inv)   fp32, the lane's channels in ascending order, then naf_rows_sum
+//   The norm does not depend on the embeddings, so g' is the whole gradient with respect to PV.  acc keeps the UNSCALED cosines and z is
+//   formed from them where it is used; the block contracts nothing (fp contract off), so every use of z[n] has the bits the cosine
+//   instantiation stores.  The target is only compared with channel indices; t == ignore_index or t outside [0, N): loss 0, g' = 0, ds = 0.
+//   A pixel of norm 0 has every cosine 0 and loss ln N; its exact gradient is 0 (dE^ = sum_px g' f, f = 0): g' is stored as zeros, not as
+//   1e12 * (softmax - onehot); ds = 0 follows from acc = 0.  g' is written as 8-byte vectors over all gc channels, zeros from N up, also
+//   past the NCT*16 accumulator channels.  s is the struct's float, or one fp32 device value behind scale_ptr, read once per round of the
+//   epilogue.  Every output is optional (NULL: a wave-uniform branch); vector stores only, no atomics, nothing crosses a workgroup.
+//   Tiles per wave and which pairs exist: xna_cos_ce_tpw / xna_cos_ce_served (profiles/cosine_objective.txt).
 #pragma once
 #include "xna_head_kernel.h"
 
@@ -51,6 +66,21 @@ struct XnaCosEpilogue {
     int64_t ns[3];       // {b, y, x}
     float logit_scale;
 };
+// ... and with the classification epilogue: XnaCosEpilogue first, so both are read through the same pointer (cos.out / norms stay optional)
+struct XnaCosCEEpilogue {
+    XnaCosEpilogue cos;
+    const int64_t* target;     // [B, Ho, Wo] or nullptr
+    float* loss;               // per-pixel lse - z[t], or nullptr
+    uint8_t* labels;           // per-pixel argmax, or nullptr
+    bf16_t* dlogits;           // [B, Ho, Wo, gc] g', or nullptr
+    float* dscale;             // per-pixel ds, or nullptr
+    const float* scale_ptr;    // one fp32 device value that replaces cos.logit_scale, or nullptr
+    int64_t ignore_index;
+    int64_t ts[3], ls[3], bs[3], gs[3], ds[3];   // {b, y, x} element strides of target / loss / labels / dlogits / dscale
+    int32_t gc;                // channels of a dlogits row the kernel writes (multiple of 8, >= npad)
+};
+template <typename T> struct XnaCosIsCE { static constexpr bool value = false; };
+template <> struct XnaCosIsCE<XnaCosCEEpilogue> { static constexpr bool value = true; };
 constexpr size_t XNA_COS_ARG_OFFSET = (sizeof(XnaCosParams) + alignof(XnaCosEpilogue) - 1) / alignof(XnaCosEpilogue) * alignof(XnaCosEpilogue);
 
 constexpr int XNA_COS_DVC = 64;   // value channels staged at a time
@@ -69,10 +99,22 @@ constexpr bool xna_cos_served(int ks, int nct) { return xna_cos_fits(ks, nct); }
 constexpr bool xna_cos_served(int ks, int nct) { return xna_cos_fits(ks, nct) && !(ks >= 13 && nct >= 10); }
 #endif
 
-template <int KS, int NCT>
-__global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosParams p, const XnaCosEpilogue epi) {
+// the classification epilogue's instantiations: tiles per wave and which exist, from the compiler's figures as above
+// (profiles/cosine_objective.txt; tools/cosine_objective_time.py --resources).  Sixteen channel tiles with two tiles per wave spill in
+// the epilogue at windows 3 and 5 (24 / 36 bytes per lane): one tile per wave there.  With that, every pair the cosine kernel serves is
+// free of scratch with the epilogue too; windows 13 and 15 with 10 or 16 channel tiles spill in the head loop as the cosine kernel does.
+constexpr int xna_cos_ce_tpw(int ks, int nct) { return nct >= 16 ? 1 : xna_cos_tpw(ks, nct); }
+#ifdef NAF_XNA_COS_ALL
+constexpr bool xna_cos_ce_served(int ks, int nct) { return xna_cos_fits(ks, nct); }
+#else
+constexpr bool xna_cos_ce_served(int ks, int nct) { return xna_cos_served(ks, nct); }
+#endif
+
+template <int KS, int NCT, typename Epi = XnaCosEpilogue>
+__global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosParams p, const Epi epi) {
+    constexpr bool CE = XnaCosIsCE<Epi>::value;
     constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
-    constexpr int TPW = xna_cos_tpw(KS, NCT);
+    constexpr int TPW = CE ? xna_cos_ce_tpw(KS, NCT) : xna_cos_tpw(KS, NCT);
     using G = XnaGeom<KS, 1>;
     constexpr int NSLOT = G::NSLOT, MT = G::MT, KST = G::KST, KROW = G::KROW;
     constexpr int DVT = NCT * 16, VROW = XnaVRow<DVT>::VROW, VCH = DVT / 8;
@@ -324,35 +366,143 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosP
         int ecol = col, egrp = grp;
         asm volatile("" : "+v"(ecol), "+v"(egrp));
         const XnaCosEpilogue __attribute__((address_space(4)))* x = reinterpret_cast<const XnaCosEpilogue __attribute__((address_space(4)))*>(ka + XNA_COS_ARG_OFFSET);
+        if constexpr (CE) {
+            // ---- classification epilogue (see the header comment): softmax over the classes of the scaled cosines ----
+#pragma clang fp contract(off)
+            constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
+            const XnaCosCEEpilogue __attribute__((address_space(4)))* xc = reinterpret_cast<const XnaCosCEEpilogue __attribute__((address_space(4)))*>(ka + XNA_COS_ARG_OFFSET);
+            const float* sp = xc->scale_ptr;
+            const float ls = sp != nullptr ? *sp : x->logit_scale;
 #pragma unroll
-        for (int u = 0; u < TPW; ++u) {
-            if (!livev[u]) continue;   // wave-uniform: the four-lane reduction below runs on whole waves
-            const float nrm = sqrtf(naf_rows_sum(ssq[u]));
-            const float inv = 1.0f / fmaxf(nrm, 1e-12f);
-            if (tx0v[u] + ecol >= p.dx) continue;
-            float* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u]) continue;   // wave-uniform: the four-lane reductions below run on whole waves
+                const float nrm = sqrtf(naf_rows_sum(ssq[u]));
+                const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+                const bool inpx = tx0v[u] + ecol < p.dx;
+                const int64_t gy = cy * p.dy + tyv[u];
+                const int64_t gx = cx * p.dx + min(tx0v[u] + ecol, p.dx - 1);   // lanes past a partial last tile repeat its last pixel, store nothing
+                // acc <- the unscaled cosine; z = ls * acc is the expression of the cosine epilogue, so a stored z is what naf_xna_cos_fwd stores
+                float m = -INFINITY;
+                int am = 0;
 #pragma unroll
-            for (int ct = 0; ct < NCT; ++ct) {
+                for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int ch = ct * 16 + egrp * 4 + r;
-                    if (ch < p.N) op[ch] = x->logit_scale * (acc[u][ct][r] * inv);
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + egrp * 4 + r;
+                        if (ch < p.N) {
+                            const float c = acc[u][ct][r] * inv;
+                            acc[u][ct][r] = c;
+                            const float z = ls * c;
+                            if (z > m) {   // a lane's channels ascend with (ct, r): the first of equal maxima stays
+                                m = z;
+                                am = ch;
+                            }
+                        }
+                    }
+                const float mall = naf_rows_max(m);
+                // lowest index among the lanes that hold the maximum: indices <= 255 are exact in fp32
+                const int label = (int)(-naf_rows_max(m == mall ? -(float)am : -INFINITY));
+                int t = -1;   // the target as a channel index, -1 = ignored
+                if (xc->target != nullptr) {
+                    const int64_t tv = xc->target[b * xc->ts[0] + gy * xc->ts[1] + gx * xc->ts[2]];
+                    t = (tv != xc->ignore_index && tv >= 0 && tv < (int64_t)p.N) ? (int)tv : -1;
+                }
+                // every pass forms z again from its own copy of the scale: sixteen channel tiles of z kept next to acc spill
+                float ls2 = ls, ls3 = ls;
+                asm volatile("" : "+v"(ls2), "+v"(ls3));
+                float sum = 0.f, zt = 0.f;
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + egrp * 4 + r;
+                        if (ch < p.N) {
+                            const float z = ls2 * acc[u][ct][r];
+                            sum += __builtin_amdgcn_exp2f((z - mall) * LOG2E);
+                            zt += ch == t ? z : 0.f;   // one lane of the four holds z[t]
+                        }
+                    }
+                sum = naf_rows_sum(sum);   // >= 1: the maximum contributes exp2(0)
+                zt = naf_rows_sum(zt);
+                if (egrp == 0 && inpx) {
+                    if (xc->loss != nullptr)
+                        xc->loss[b * xc->ls[0] + gy * xc->ls[1] + gx * xc->ls[2]] = t >= 0 ? (mall + __builtin_amdgcn_logf(sum) * LN2) - zt : 0.f;
+                    if (xc->labels != nullptr) xc->labels[b * xc->bs[0] + gy * xc->bs[1] + gx * xc->bs[2]] = (uint8_t)label;
+                    if (x->norms != nullptr) x->norms[b * x->ns[0] + gy * x->ns[1] + gx * x->ns[2]] = nrm;
+                }
+                if (p.out != nullptr && inpx) {
+                    float* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ch = ct * 16 + egrp * 4 + r;
+                            if (ch < p.N) op[ch] = ls * acc[u][ct][r];
+                        }
+                }
+                if (xc->dlogits != nullptr || xc->dscale != nullptr) {   // wave-uniform
+                    bf16_t* gp = xc->dlogits != nullptr && inpx ? xc->dlogits + b * xc->gs[0] + gy * xc->gs[1] + gx * xc->gs[2] : nullptr;
+                    const float rs = __builtin_amdgcn_rcpf(sum);
+                    // the exponentials are formed again, not kept from the sum above (64 more registers at sixteen channel tiles: it spills)
+                    float mg = mall;
+                    asm volatile("" : "+v"(mg));
+                    const bool counted = t >= 0;
+                    const float gf = (counted && nrm > 0.f) ? ls * inv : 0.f;   // a zero feature: the exact gradient row is zero
+                    float dsl = 0.f;
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) {
+                        const int c0 = ct * 16 + egrp * 4;
+                        bf16x4_t gv;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ch = c0 + r;
+                            const float e = __builtin_amdgcn_exp2f((ls3 * acc[u][ct][r] - mg) * LOG2E) * rs - (ch == t ? 1.f : 0.f);
+                            const bool on = ch < p.N && counted;
+                            dsl += on ? e * acc[u][ct][r] : 0.f;
+                            gv[r] = (bf16_t)((on && gf != 0.f) ? gf * e : 0.f);
+                        }
+                        // gc is a multiple of 8: a lane's four channels are all inside or all outside
+                        if (gp != nullptr && c0 < xc->gc) *reinterpret_cast<bf16x4_t*>(gp + c0) = gv;
+                    }
+                    // channels past the accumulators (Npad = 160 -> gc = 192): plain zero stores
+                    if (gp != nullptr)
+                        for (int c0 = DVT + egrp * 4; c0 < xc->gc; c0 += 16) *reinterpret_cast<bf16x4_t*>(gp + c0) = bf16x4_t{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+                    dsl = naf_rows_sum(dsl);
+                    if (xc->dscale != nullptr && egrp == 0 && inpx) xc->dscale[b * xc->ds[0] + gy * xc->ds[1] + gx * xc->ds[2]] = dsl;
                 }
             }
-            if (x->norms != nullptr && egrp == 0)
-                x->norms[b * x->ns[0] + (int64_t)(cy * p.dy + tyv[u]) * x->ns[1] + (int64_t)(cx * p.dx + tx0v[u] + ecol) * x->ns[2]] = nrm;
+        } else {
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u]) continue;   // wave-uniform: the four-lane reduction below runs on whole waves
+                const float nrm = sqrtf(naf_rows_sum(ssq[u]));
+                const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+                if (tx0v[u] + ecol >= p.dx) continue;
+                float* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + egrp * 4 + r;
+                        if (ch < p.N) op[ch] = x->logit_scale * (acc[u][ct][r] * inv);
+                    }
+                }
+                if (x->norms != nullptr && egrp == 0)
+                    x->norms[b * x->ns[0] + (int64_t)(cy * p.dy + tyv[u]) * x->ns[1] + (int64_t)(cx * p.dx + tx0v[u] + ecol) * x->ns[2]] = nrm;
+            }
         }
     }
 }
 
-template <int KS, int NCT>
-static int xna_cos_launch_one(const XnaCosParams& p, const XnaCosEpilogue& epi, hipStream_t s) {
-    if constexpr (!xna_cos_served(KS, NCT)) {
-        naf_set_error("naf_xna_cos_fwd: no kernel for kernel_size=%d channel tiles=%d", KS, NCT);
+template <int KS, int NCT, typename Epi>
+static int xna_cos_launch_one(const XnaCosParams& p, const Epi& epi, hipStream_t s) {
+    constexpr bool CE = XnaCosIsCE<Epi>::value;
+    if constexpr (!(CE ? xna_cos_ce_served(KS, NCT) : xna_cos_served(KS, NCT))) {
+        naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", CE ? "naf_xna_cos_ce_fwd" : "naf_xna_cos_fwd", KS, NCT);
         return NAF_ERR_UNSUPPORTED;
     } else {
         constexpr size_t lds = xna_cos_lds_for(KS, NCT);
-        auto kern = xna_cos_kernel<KS, NCT>;
+        auto kern = xna_cos_kernel<KS, NCT, Epi>;
         if (lds > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
             if (e != hipSuccess) {
@@ -361,21 +511,23 @@ static int xna_cos_launch_one(const XnaCosParams& p, const XnaCosEpilogue& epi, 
             }
         }
         hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, epi);
-        return naf_check_launch("xna_cos_kernel");
+        return naf_check_launch(CE ? "xna_cos_kernel (classification epilogue)" : "xna_cos_kernel");
     }
 }
 
 // The window's entry point, one explicit instantiation per window in xna_cos_inst.hip.
-template <int KS>
-int xna_cos_launch_ks(const XnaCosParams& p, const XnaCosEpilogue& epi, hipStream_t s) {
+template <int KS, typename Epi>
+int xna_cos_launch_ks(const XnaCosParams& p, const Epi& epi, hipStream_t s) {
     const int nct = xna_head_nct(p.npad);
-    if (nct == 2) return xna_cos_launch_one<KS, 2>(p, epi, s);
-    if (nct == 4) return xna_cos_launch_one<KS, 4>(p, epi, s);
-    if (nct == 10) return xna_cos_launch_one<KS, 10>(p, epi, s);
-    if (nct == 16) return xna_cos_launch_one<KS, 16>(p, epi, s);
-    naf_set_error("naf_xna_cos_fwd: no kernel for kernel_size=%d channel tiles=%d", KS, nct);
+    if (nct == 2) return xna_cos_launch_one<KS, 2, Epi>(p, epi, s);
+    if (nct == 4) return xna_cos_launch_one<KS, 4, Epi>(p, epi, s);
+    if (nct == 10) return xna_cos_launch_one<KS, 10, Epi>(p, epi, s);
+    if (nct == 16) return xna_cos_launch_one<KS, 16, Epi>(p, epi, s);
+    naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", XnaCosIsCE<Epi>::value ? "naf_xna_cos_ce_fwd" : "naf_xna_cos_fwd", KS, nct);
     return NAF_ERR_UNSUPPORTED;
 }
 
-// xna_cos_inst.hip (-DNAF_KS=<KS>) defines it, xna_cos.hip declares it (extern) and dispatches on the window.
-#define NAF_XNA_COS_WINDOW(LINKAGE, KS) LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosEpilogue&, hipStream_t);
+// xna_cos_inst.hip (-DNAF_KS=<KS>) defines the two, xna_cos.hip declares them (extern) and dispatches on the window.
+#define NAF_XNA_COS_WINDOW(LINKAGE, KS)                                                                                    \
+    LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosEpilogue&, hipStream_t);                   \
+    LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosCEEpilogue&, hipStream_t);

@@ -1093,7 +1093,7 @@ class NAF(nn.Module):
 
     def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
                 reduction="mean", predict=False, confusion=None, regress=None, regress_path="auto", cosine=False, logit_scale=1.0,
-                return_norms=False, cosine_path="auto", **kwargs):
+                return_norms=False, cosine_path="auto", loss=None, **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -1179,14 +1179,36 @@ class NAF(nn.Module):
         kernel (``ops.xna_cos_forward``: the [B, C, Ho, Wo] features, their fp32 copy and the normalised copy never exist) for bf16 features
         on the geometries ``head=`` is fused for (windows 13 and 15 up to 64 embeddings), and is the expression above in torch ops on the
         plain forward everywhere else: fp16 / fp32 features, non-integer ratios, ratio 1, and whenever a gradient is enabled and ``E``
-        requires one (that route is differentiable with respect to ``E``; the fused one is inference-only).  ``"fused"`` insists
+        requires one (that route is differentiable with respect to ``E``; the fused one is inference-only without ``loss=``).  ``"fused"`` insists
         (NafHipError with the library's reason); ``"composed"`` is the A/B arm.  ``cosine=True`` with ``predict=True`` or with ``target=`` and
         ``confusion=`` runs those calls with ``head=(F.normalize(E.float(), dim=1), None)``: the argmax does not see the per-pixel positive
-        scale.  ValueError: a head with a bias, ``target=`` without ``confusion=`` (no loss on cosines), ``regress=``, ``return_weights``,
-        ``return_norms`` with ``predict`` / ``confusion``.  Not offered: a gradient through the fused route, ``capture()`` of this call."""
+        scale.  ValueError: a head with a bias, ``target=`` without ``confusion=`` or ``loss=`` (the loss is ``loss="ce"``, below), ``regress=``, ``return_weights``,
+        ``return_norms`` with ``predict`` / ``confusion``.  Not offered: ``capture()`` of this call.
+
+        ``loss="ce"`` (keyword only, with ``cosine=True`` and ``target``): TRAINING against the cosines -- a cosine classifier as a dense
+        probe, prompt / embedding tuning, a learnable temperature.  The call returns
+            ``F.cross_entropy(cos.float(), target, ignore_index=ignore_index, reduction=reduction)``
+        on the scaled cosines ``cos`` defined above (a 0-dim fp32 tensor, [B, Ho, Wo] for ``reduction="none"``; targets outside [0, N) are
+        ignored as for ``head=probe``), or ``(loss, pred)`` with ``predict=True`` (``pred`` int64 [B, Ho, Wo], from the same launch).
+        ``logit_scale`` is a float or a 1-element fp32 tensor; a tensor is read on the device (no host synchronisation) and receives a
+        gradient when it requires one, as do the embeddings.  ``cosine_path="auto"`` takes loss, labels and both gradients from the
+        attention kernel's epilogue (``ops.XnaCosCEFunction`` / ``ops.xna_cos_objective``: one forward launch, and for the embeddings one
+        launch of the attention backward; the [B, C, Ho, Wo] features, their copies and the [B, N, Ho, Wo] cosines never exist) where
+        ``naf_xna_cos_ce_select`` grants the geometry, the features are bf16 and no gradient is wanted for the upsampler or its inputs;
+        everything else is the expression above in torch ops on the plain forward (``forward_train`` when the upsampler wants a
+        gradient).  ``"fused"`` insists (NafHipError with the reason); ``"composed"`` is the A/B arm.  ``image`` may be a ``Guidance``.
+        ValueError, before any device work: ``loss`` other than None / "ce"; ``loss`` without ``cosine=True``, without ``target``, with
+        ``return_norms`` or with ``confusion``; a float ``logit_scale <= 0`` with ``predict``.  Not offered: a gradient for the upsampler
+        through the fused route, class weights, label smoothing, soft targets, fp16 / fp32 features on the fused route."""
+        if loss is not None:
+            if loss != "ce":
+                raise ValueError(f"loss must be None or 'ce', got {loss!r}")
+            if not cosine:
+                raise ValueError("naf(..., loss='ce') is the objective of the cosine head: pass head=E and cosine=True as well "
+                                 "(a linear probe's cross-entropy is head=probe, target=...)")
         if cosine:
             return self._forward_cosine(image, features, output_size, return_weights, head, target, ignore_index, reduction, predict, confusion,
-                                        regress, logit_scale, return_norms, cosine_path)
+                                        regress, logit_scale, return_norms, cosine_path, loss)
         if isinstance(image, Guidance):
             self._check_guidance_call(image, features, return_weights, regress, confusion)
         if regress is not None:
@@ -1359,7 +1381,7 @@ class NAF(nn.Module):
         return loss
 
     def _forward_cosine(self, image, features, output_size, return_weights, head, target, ignore_index, reduction, predict, confusion,
-                        regress, logit_scale, return_norms, path):
+                        regress, logit_scale, return_norms, path, loss=None):
         """``forward(..., head=E, cosine=True)``: see ``forward``.  Every refusal comes before anything touches the device."""
         if path not in ("auto", "fused", "composed"):
             raise ValueError(f"cosine_path must be 'auto', 'fused' or 'composed', got {path!r}")
@@ -1371,9 +1393,12 @@ class NAF(nn.Module):
             raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(getattr(features, 'shape', ()))}")
         weight = _cosine_head(head, features.shape[1])
         evaluation = confusion is not None and confusion is not False
+        if loss is not None:
+            return self._forward_cosine_objective(image, features, output_size, weight, target, ignore_index, reduction, predict, evaluation,
+                                                  logit_scale, return_norms, path)
         if target is not None and not evaluation:
-            raise ValueError("naf(..., cosine=True, target=...) without confusion=: a loss on scaled cosines is not offered (labels: predict=True; "
-                             "evaluation: confusion=)")
+            raise ValueError("naf(..., cosine=True, target=...) without confusion=: the cross-entropy on the scaled cosines is loss='ce' "
+                             "(labels: predict=True; evaluation: confusion=)")
         if not math.isfinite(float(logit_scale)):
             raise ValueError(f"logit_scale must be finite, got {logit_scale}")
         if predict or evaluation:
@@ -1423,6 +1448,80 @@ class NAF(nn.Module):
             with ops._Timed("attention"):
                 return ops.xna_cos_forward(q5, k5, v5, weight, ksz, logit_scale=logit_scale, return_norms=return_norms, path="fused",
                                            scale=self.upsampler.scale, rope_tables=tabs)
+
+    def _forward_cosine_objective(self, image, features, output_size, weight, target, ignore_index, reduction, predict, evaluation,
+                                  logit_scale, return_norms, path):
+        """``forward(..., head=E, cosine=True, target=t, loss="ce")``: see ``forward``.  Every refusal comes before anything touches the device."""
+        if target is None:
+            raise ValueError("naf(..., cosine=True, loss='ce') needs target=...: integer class indices [B, Ho, Wo]")
+        if return_norms:
+            raise ValueError("naf(..., cosine=True, loss='ce') returns the loss: return_norms goes with the cosines")
+        if evaluation:
+            raise ValueError("naf(..., cosine=True, loss='ce') does not combine with confusion= (the evaluation is a call of its own)")
+        if reduction not in ops._REDUCTIONS:
+            raise ValueError(f"reduction must be one of {ops._REDUCTIONS}, got {reduction!r}")
+        learnable = isinstance(logit_scale, torch.Tensor)
+        if learnable:
+            if logit_scale.numel() != 1 or logit_scale.dtype != torch.float32:
+                raise ValueError(f"logit_scale must be a float or a 1-element float32 tensor, got {tuple(logit_scale.shape)} {logit_scale.dtype}")
+        else:
+            if not math.isfinite(float(logit_scale)):
+                raise ValueError(f"logit_scale must be finite, got {logit_scale}")
+            if predict and float(logit_scale) <= 0:
+                raise ValueError(f"naf(..., cosine=True, loss='ce', predict=True) needs logit_scale > 0 (the labels are the argmax), got {logit_scale}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, C, N = features.shape[0], features.shape[1], weight.shape[0]
+        ignore_index = int(ignore_index)
+        target = ops._check_target(target, (B, ho, wo), features.device, "naf(..., loss='ce')")
+        if not (image.is_cuda and features.is_cuda and weight.is_cuda and (not learnable or logit_scale.is_cuda)):
+            raise _rocm_only(image=image, features=features, head=weight)
+        if isinstance(image, Guidance):
+            self._check_guidance_call(image, features, False, None, None)
+        pack = lambda loss, labels: (loss, labels) if predict else loss
+        heads, ksz, enc = self.upsampler.num_heads, self.upsampler.kernel_size, self.image_encoder
+        head_grad = torch.is_grad_enabled() and (weight.requires_grad or (learnable and logit_scale.requires_grad))
+        reason = None       # why the fused kernel does not take the call
+        if B == 0:
+            reason = "an empty batch"
+        elif self._wants_grad(image, features):
+            reason = "the call wants a gradient for the upsampler or its inputs, which the fused route does not carry"
+        elif features.dtype != torch.bfloat16:
+            reason = f"the fused cosine kernel reads bfloat16 features, got {features.dtype}"
+        elif C % heads or enc.out_channels % heads:
+            reason = f"feature channels {C} / guidance channels {enc.out_channels} not divisible by {heads} heads"
+        else:
+            probe = torch.empty((B, ho, wo, heads, enc.out_channels // heads), dtype=torch.bfloat16, device="meta").permute(0, 3, 1, 2, 4)
+            if ops.xna_cos_ce_select(probe, features.shape[-2:], C // heads, N, ksz) != "fused":
+                reason = _lib_last_error() or f"naf_xna_cos_ce_select refuses {N} embeddings"
+        if path == "fused" and reason is not None:
+            raise ops._lib.NafHipError(f"naf(..., cosine=True, loss='ce', cosine_path='fused'): {reason}")
+        if path == "composed" or reason is not None:
+            with ops._Timed("cosine_objective_composed"):
+                if B == 0:
+                    z = torch.empty((0, N, ho, wo), dtype=torch.float32, device=features.device)
+                else:
+                    z = ops.cosine_from_features(self.forward(image, features, output_size), ops.normalize_embeddings(weight), 1.0) * logit_scale
+                val = F.cross_entropy(z.float(), ops.head_sanitized_target(target, ignore_index, N), ignore_index=ignore_index, reduction=reduction)
+                return pack(val, z.detach().argmax(1) if predict else None)
+        lr = features.shape[-2:]
+        with torch.no_grad():
+            # a recorded graph reads materialised (rotated) queries: the backward kernels have no rotate-on-load
+            fusable = None if head_grad else (lambda q5, tabs: ops.xna_cos_ce_select(q5, lr, C // heads, N, ksz, rope_tables=tabs) == "fused")
+            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
+            v5 = ops.pack_values(features).view(B, lr[0], lr[1], heads, C // heads).permute(0, 3, 1, 2, 4)
+        with ops._Timed("attention"):
+            if head_grad:
+                pv5 = ops.project_cosine_values(weight, v5)       # with the graph on: the embeddings' gradient enters autograd here
+                res = ops.XnaCosCEFunction.apply(q5, k5, pv5, v5, weight, logit_scale, target, ksz, ignore_index, reduction, bool(predict), "fused",
+                                                 self.upsampler.scale)
+                val, labels = res if predict else (res, None)
+            else:
+                with torch.no_grad():
+                    loss_map, labels, _, _ = ops.xna_cos_objective(q5, k5, v5, weight, ksz, target=target, ignore_index=ignore_index,
+                                                                   logit_scale=logit_scale, want_loss=True, want_labels=bool(predict), path="fused",
+                                                                   scale=self.upsampler.scale, rope_tables=tabs)
+                    val = ops.reduce_head_loss(loss_map, target, ignore_index, N, reduction)
+        return pack(val, None if labels is None else labels.long())
 
     def _head_call(self, image, features, output_size, return_weights, head, reduction="mean", target=None, confusion=None):
         """Host-side validation the three ``head=`` entries share, in the order they raise (nothing has touched the device yet):

@@ -1215,9 +1215,10 @@ def _fill_xna_head(q, k, pv, bias, out, n_out, ky, kx, path, scale, rope_tables=
     return a
 
 
-def _head_route(a, entry: str, q, lr_size, n_out: int, kernel_size, rope_tables, Dv: Optional[int] = None) -> str:
+def _head_route(a, entry: str, q, lr_size, n_out: int, kernel_size, rope_tables, Dv: Optional[int] = None, outer=None) -> str:
     """The answer of ``naf_xna_head_select`` / ``naf_xna_cos_select`` (``entry``) to a shape / alignment query: fills the fresh descriptor
-    ``a`` for queries ``q`` with dense channels-last keys, projected values, (``Dv``: the cosine head's) values and output."""
+    ``a`` for queries ``q`` with dense channels-last keys, projected values, (``Dv``: the cosine head's) values and output.  ``outer``: the
+    struct ``a`` is the first member of, where the entry takes that one (``naf_xna_cos_ce_select``)."""
     lib = _lib.load()
     ky, kx = _ksize(kernel_size)
     _, heads, Ho, Wo, Dq = q.shape
@@ -1233,7 +1234,7 @@ def _head_route(a, entry: str, q, lr_size, n_out: int, kernel_size, rope_tables,
     a.o_stride = I64x3(Ho * Wo * n_out, Wo * n_out, n_out)
     if Dv is not None:
         a.v_lr, a.Dv, a.logit_scale, a.v_stride = ptr, Dv, 1.0, _dense5(h, w, heads, Dv)
-    sel = getattr(lib, entry)(C.byref(a))
+    sel = getattr(lib, entry)(C.byref(a if outer is None else outer))
     if sel == -1:
         _lib.check(1, entry)
     return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
@@ -1738,6 +1739,221 @@ class XnaHeadCEFunction(torch.autograd.Function):
                 dv = dv * factor
             dpv = dv.to(pv_lr.dtype)
         return (None, None, dpv, dbias) + (None,) * 8
+
+
+# ---- ... and the same objective on the cosine head's scaled cosines (cosine classifier, prompt tuning, learnable temperature) ----------
+def project_cosine_values(embeddings: torch.Tensor, v_lr: torch.Tensor) -> torch.Tensor:
+    """The low-res half of the cosine head: ``PV_g = E^[:, g*Dv:(g+1)*Dv] @ V_g`` with ``E^ = normalize_embeddings(E)`` for v_lr
+    [B, heads, h, w, Dv] -> pv5 [B, heads, h, w, Npad] bf16 with zero pad channels.  Pure torch and differentiable: this is where the
+    embeddings' gradient enters autograd (``XnaCosCEFunction`` returns the gradient of pv5)."""
+    e_hat = normalize_embeddings(embeddings)
+    _, heads, _, _, Dv = v_lr.shape
+    N = e_hat.shape[0]
+    pv = torch.einsum("ngd,bghwd->bghwn", e_hat.reshape(N, heads, Dv), v_lr.float())
+    pad = head_npad(N) - N
+    return (torch.nn.functional.pad(pv, (0, pad)) if pad else pv).to(torch.bfloat16)
+
+
+def _check_logit_scale(who: str, logit_scale, device):
+    """-> (float for the struct, 1-element fp32 device tensor or None).  A tensor is read by the kernel through a pointer: no host sync."""
+    if isinstance(logit_scale, torch.Tensor):
+        if logit_scale.numel() != 1 or logit_scale.dtype != torch.float32:
+            raise ValueError(f"{who}: a logit_scale tensor must hold one float32 value, got {tuple(logit_scale.shape)} {logit_scale.dtype}")
+        if logit_scale.device != device:
+            raise ValueError(f"{who}: logit_scale is on {logit_scale.device}, the features on {device}")
+        return 1.0, logit_scale.detach()
+    if not math.isfinite(float(logit_scale)):
+        raise ValueError(f"{who}: logit_scale must be finite, got {logit_scale}")
+    return float(logit_scale), None
+
+
+def xna_cos_ce_select(q: torch.Tensor, lr_size, Dv: int, n_out: int, kernel_size, *, value_dtype: torch.dtype = torch.bfloat16,
+                      rope_tables=None) -> str:
+    """Which route ``xna_cos_objective(path="auto")`` takes for these shapes: "fused" (``naf_xna_cos_ce_select`` grants the kernel) or
+    "composed".  Arguments and conventions as ``xna_cos_select``; a host-side query, CPU / meta tensors do."""
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or value_dtype != torch.bfloat16 or not 1 <= int(n_out) <= 256 or int(Dv) < 1:
+        return "composed"
+    a = _lib.XnaCosCEArgs()
+    return _head_route(a.cos, "naf_xna_cos_ce_select", q, lr_size, n_out, kernel_size, rope_tables, Dv=int(Dv), outer=a)
+
+
+def cosine_objective_from_features(f: torch.Tensor, e_hat: torch.Tensor, logit_scale=1.0, target: Optional[torch.Tensor] = None,
+                                   ignore_index: int = -100, *, want_loss: bool = False, want_labels: bool = False,
+                                   want_dlogits: bool = False, want_dscale: bool = False, dlogits_channels: Optional[int] = None):
+    """The classification epilogue of ``naf_xna_cos_ce_fwd`` as torch ops on a materialised feature map f [B, C, H, W] (any device): what
+    ``xna_cos_objective`` composes where the kernel does not serve the call, same contract.  ``e_hat``: normalised rows [N, C] fp32;
+    ``logit_scale``: a float or a 1-element tensor.  Returns ``(loss_map, labels, dlogits, dscale)``, each None unless wanted: with
+    ``c = cosines``, ``z = s * c`` and ``d = softmax(z) - onehot(t)`` -- ``logsumexp(z) - z[t]`` [B, H, W] fp32; ``argmax z`` (uint8 up to
+    256 classes); ``(s / max(||f||, 1e-12)) * d`` bf16 channels-last [B, H, W, dlogits_channels] with zero pad channels; ``sum_n d * c``
+    [B, H, W] fp32.  Ignored pixels (``head_valid_pixels``) have loss 0 and zero ``dlogits`` / ``dscale``; a pixel with ``||f|| = 0`` has a zero
+    ``dlogits`` row (its exact gradient: every cosine is 0 whatever the embeddings)."""
+    ff = f.float().permute(0, 2, 3, 1)
+    nrm = ff.norm(dim=3)
+    inv = 1.0 / nrm.clamp_min(1e-12)
+    c = torch.matmul(ff * inv.unsqueeze(3), e_hat.t())
+    s = logit_scale.detach().reshape(()).float() if isinstance(logit_scale, torch.Tensor) else float(logit_scale)
+    z = c * s
+    N = e_hat.shape[0]
+    if (want_loss or want_dlogits or want_dscale) and target is None:
+        raise ValueError("cosine objective: the loss and the gradients need a target")
+    loss = labels = g = ds = None
+    if want_labels:
+        labels = z.argmax(dim=3)
+        if N <= 256:
+            labels = labels.to(torch.uint8)
+    if want_loss or want_dlogits or want_dscale:
+        valid = head_valid_pixels(target, ignore_index, N)
+        tc = torch.where(valid, target, torch.zeros_like(target))
+        lse = torch.logsumexp(z, dim=3)
+        if want_loss:
+            loss = torch.where(valid, lse - z.gather(3, tc.unsqueeze(3))[..., 0], torch.zeros_like(lse))
+        if want_dlogits or want_dscale:
+            d = (torch.exp(z - lse.unsqueeze(3)) - torch.nn.functional.one_hot(tc, N).to(z.dtype)) * valid.unsqueeze(3).to(z.dtype)
+            if want_dscale:
+                ds = (d * c).sum(dim=3)
+            if want_dlogits:
+                gc = int(dlogits_channels) if dlogits_channels is not None else head_dlogits_channels(N)
+                if gc < N:
+                    raise ValueError(f"cosine objective: dlogits_channels {gc} smaller than the {N} classes")
+                gf = torch.where(nrm > 0, inv * s, torch.zeros_like(inv))
+                g = torch.nn.functional.pad(d * gf.unsqueeze(3), (0, gc - N)).to(torch.bfloat16)
+    return loss, labels, g, ds
+
+
+def xna_cos_objective(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, embeddings: torch.Tensor, kernel_size, *,
+                      target: Optional[torch.Tensor] = None, ignore_index: int = -100, logit_scale=1.0, want_loss: bool = False,
+                      want_labels: bool = False, want_dlogits: bool = False, want_dscale: bool = False, path: str = "auto",
+                      scale: Optional[float] = None, rope_tables=None, pv_lr: Optional[torch.Tensor] = None):
+    """``xna_cos_forward`` with a classification objective on the scaled cosines in the kernel's epilogue (``naf_xna_cos_ce_fwd``): one launch
+    gives any of the per-pixel cross-entropy, the argmax labels and the two gradients, and neither the [B, C, Ho, Wo] features nor the
+    [B, N, Ho, Wo] cosines are written.  No graph is recorded here (``XnaCosCEFunction`` is the differentiable form).
+
+    Operands as ``xna_cos_forward``; ``target`` integer [B, Ho, Wo] (any strides; converted to int64), needed for everything but the labels;
+    ``logit_scale`` a float or a 1-element fp32 device tensor (read by the kernel through a pointer: no host synchronisation).  Returns
+    ``(loss_map, labels, dlogits, dscale)``, each None unless asked for, with ``inv = 1 / max(||f||, 1e-12)``, ``c`` the cosines, ``z = s * c``:
+    fp32 [B, Ho, Wo] ``logsumexp(z) - z[t]``, 0 where the pixel is ignored; uint8 [B, Ho, Wo] (int64 beyond 256 embeddings), the lowest index
+    among equal maxima, written for ignored pixels too; bf16 [B, Ho, Wo, Gc] ``g' = (s * inv) * (softmax(z) - onehot(t))`` with
+    ``Gc = head_dlogits_channels(N)``, every channel written, NOT divided by the number of valid pixels -- the gradient with respect to
+    ``E^ . f`` before the division by the norm, i.e. the ``dout`` the attention backward takes for the projected values of all heads at
+    once (``_head_values_grad``); fp32 [B, Ho, Wo] ``ds = sum_n (softmax(z) - onehot(t))[n] * c[n]``, whose sum is dloss / ds.  Ignored pixels
+    (``target == ignore_index`` or outside [0, N)) have zero ``g'`` and ``ds``; so has, for ``g'``, a pixel whose feature is zero.
+    ``pv_lr``: the projected values ``project_cosine_values(embeddings, v_lr)`` when the caller has formed them (with a graph).
+    ``path="auto"``: the kernel where ``naf_xna_cos_ce_select`` grants it and the values are bf16, else the composition -- the plain forward and
+    ``cosine_objective_from_features`` as torch ops, same contract; ``"fused"`` insists and raises NafHipError; ``"composed"`` insists on the
+    composition."""
+    e_hat, (B, heads, Ho, Wo, Dq, h, w, Dv) = _check_cos_operands("xna_cos_objective", q, k_lr, v_lr, embeddings, path)
+    ky, kx = _ksize(kernel_size)
+    N = e_hat.shape[0]
+    if not (want_loss or want_labels or want_dlogits or want_dscale):
+        raise ValueError("xna_cos_objective: nothing asked for (want_loss / want_labels / want_dlogits / want_dscale)")
+    dev = q.device
+    ls, ls_t = _check_logit_scale("xna_cos_objective", logit_scale, dev)
+    needs_target = want_loss or want_dlogits or want_dscale
+    if needs_target and target is None:
+        raise ValueError("xna_cos_objective: the loss and the gradients need a target")
+    if target is not None:
+        target = _check_target(target, (B, Ho, Wo), dev, "xna_cos_objective")
+    gc = head_dlogits_channels(N)
+    lib = _lib.load()
+    with torch.no_grad():
+        if path != "composed" and (path == "fused" or (v_lr.dtype == torch.bfloat16 and N <= 256)):
+            if v_lr.dtype != torch.bfloat16:
+                raise _lib.NafHipError(f"xna_cos_objective: the fused kernel needs bfloat16 values, got {v_lr.dtype}")
+            pv5 = pv_lr.detach() if pv_lr is not None else project_cosine_values(embeddings, v_lr)
+            if tuple(pv5.shape) != (B, heads, h, w, head_npad(N)) or pv5.dtype != torch.bfloat16:
+                raise ValueError(f"xna_cos_objective: pv_lr must be bfloat16 {(B, heads, h, w, head_npad(N))}, got {pv5.dtype} {tuple(pv5.shape)}")
+            loss = torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev) if want_loss else None
+            labels = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=dev) if want_labels else None
+            g = torch.empty((B, Ho, Wo, gc), dtype=torch.bfloat16, device=dev) if want_dlogits else None     # the kernel writes every channel
+            ds = torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev) if want_dscale else None
+            a = _lib.XnaCosCEArgs()
+            a.cos = _fill_xna_cos(q, k_lr, pv5, v_lr, q, None, N, ky, kx, path, scale, ls, rope_tables)
+            a.cos.out = None
+            a.cos.o_stride = I64x3(0, 0, 0)
+            a.ignore_index, a.dlogits_channels = int(ignore_index), gc
+            if ls_t is not None:
+                a.logit_scale_ptr = ls_t.data_ptr()
+            for t, ptr, st in ((target if needs_target else None, "target", "t_stride"), (loss, "loss", "loss_stride"),
+                               (labels, "labels", "labels_stride"), (g, "dlogits", "dlogits_stride"), (ds, "dscale", "dscale_stride")):
+                if t is not None:
+                    setattr(a, ptr, t.data_ptr())
+                    setattr(a, st, _strides3(t))
+            sel = lib.naf_xna_cos_ce_select(C.byref(a))
+            if sel == _lib.XNA_HEAD_FUSED:
+                with torch.cuda.device(dev), _Timed("xna_cos_ce"):
+                    rc = lib.naf_xna_cos_ce_fwd(C.byref(a), _stream(q))
+                _lib.check(rc, "naf_xna_cos_ce_fwd")
+                return loss, labels, g, ds
+            if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
+                _lib.check(-sel, "naf_xna_cos_ce_select")
+            del loss, labels, g, ds, pv5
+        with _Timed("xna_cos_ce_composed"):
+            odt = v_lr.dtype if v_lr.dtype in (torch.bfloat16, torch.float16) else torch.float32
+            o5 = xna_forward(q, k_lr, v_lr if v_lr.dtype in (torch.bfloat16, torch.float16) else v_lr.to(torch.bfloat16), (ky, kx),
+                             out_dtype=odt, path="auto", scale=scale, rope_tables=rope_tables)
+            f = o5.permute(0, 1, 4, 2, 3).reshape(B, heads * Dv, Ho, Wo)
+            loss, labels, g, ds = cosine_objective_from_features(f, e_hat, ls_t if ls_t is not None else ls, target, ignore_index,
+                                                                 want_loss=want_loss, want_labels=want_labels, want_dlogits=want_dlogits,
+                                                                 want_dscale=want_dscale, dlogits_channels=gc)
+            return loss, labels, g, ds
+
+
+class XnaCosCEFunction(torch.autograd.Function):
+    """Differentiable cross-entropy of the cosine head's scaled cosines, with respect to the projected values ``pv_lr`` (and through them the
+    embeddings) and the logit scale -- the queries, keys and values come from a frozen upsampler, as for ``XnaHeadCEFunction``, which this
+    mirrors.  The forward is ONE launch (``xna_cos_objective``) that leaves the loss map, ``g'`` (bf16, the attention backward's width,
+    unnormalised) and the ``ds`` map; the backward hands ``g'`` to ``xna_backward`` as the ``dout`` of every head (stride 0) and scales the
+    low-res result by the incoming gradient and, for "mean", by 1 / number of valid pixels; ``dscale.sum()`` times the same factor is the
+    gradient of a ``logit_scale`` tensor.  reduction="none": the incoming gradient is a map, ``g'`` and ``ds`` are scaled per pixel first.
+    ``pv_lr = project_cosine_values(embeddings, v_lr)`` is formed by the caller WITH the graph on: autograd carries its gradient to the
+    embeddings through the low-res product and the normalisation.  ``embeddings`` itself gets no gradient from this function (the
+    composed route needs its values).  Returns the reduced loss, or ``(loss, labels)`` with ``want_labels``.  ``q`` holds materialised (rotated)
+    queries.  Not here: a gradient for q, k_lr or v_lr, class weights, label smoothing, soft targets."""
+
+    @staticmethod
+    def forward(ctx, q, k_lr, pv_lr, v_lr, embeddings, logit_scale, target, kernel_size, ignore_index=-100, reduction="mean",
+                want_labels=False, path="auto", scale=None):
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"reduction must be one of {_REDUCTIONS}, got {reduction!r}")
+        scale_grad = isinstance(logit_scale, torch.Tensor) and ctx.needs_input_grad[5]
+        loss_map, labels, g, ds = xna_cos_objective(q, k_lr, v_lr, embeddings.detach(), kernel_size, target=target, ignore_index=ignore_index,
+                                                    logit_scale=logit_scale, want_loss=True, want_labels=want_labels, want_dlogits=True,
+                                                    want_dscale=scale_grad, path=path, scale=scale, pv_lr=pv_lr)
+        n_out = embeddings.shape[0]
+        tgt = target if target.dtype == torch.int64 else target.long()
+        saved = [q, k_lr, pv_lr, g]
+        ctx.has_ds = ds is not None
+        if ds is not None:
+            saved.append(ds)
+        if reduction == "mean":
+            saved.append(head_valid_pixels(tgt, ignore_index, n_out).sum().float().reciprocal())
+        ctx.save_for_backward(*saved)
+        ctx.kernel_size, ctx.scale, ctx.reduction = kernel_size, scale, reduction
+        ctx.ls_shape = tuple(logit_scale.shape) if isinstance(logit_scale, torch.Tensor) else None
+        loss = reduce_head_loss(loss_map, tgt, ignore_index, n_out, reduction)
+        if want_labels:
+            ctx.mark_non_differentiable(labels)
+            return loss, labels
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss, *rest):
+        q, k_lr, pv_lr, g = ctx.saved_tensors[:4]
+        ds = ctx.saved_tensors[4] if ctx.has_ds else None
+        dpv = dls = None
+        if ctx.reduction == "none":
+            g = (g.float() * dloss.unsqueeze(-1)).to(torch.bfloat16)
+            factor = None
+        else:
+            factor = dloss.float() * ctx.saved_tensors[-1] if ctx.reduction == "mean" else dloss.float()
+        if ds is not None:
+            dls = ((ds * dloss).sum() if factor is None else ds.sum() * factor).reshape(ctx.ls_shape)
+        if ctx.needs_input_grad[2]:
+            dv = _head_values_grad(q, k_lr, pv_lr, g, ctx.kernel_size, ctx.scale)
+            if factor is not None:
+                dv = dv * factor
+            dpv = dv.to(pv_lr.dtype)
+        return (None, None, dpv, None, None, dls) + (None,) * 7
 
 
 def xna_rope_fusable(q: torch.Tensor, lr_size, Dv: int, kernel_size, rope_tables, out_dtype=torch.bfloat16,

@@ -56,7 +56,7 @@ def resources(say):
                    "-o", os.path.join(tmp, "o.o")]
             txt = subprocess.run(cmd, capture_output=True, text=True, check=True).stderr
         seen = set()
-        for m in re.finditer(r"Function Name: _Z14xna_cos_kernelILi(\d+)ELi(\d+)E.*?LDS Size[^\n]*", txt, flags=re.S):
+        for m in re.finditer(r"Function Name: _Z14xna_cos_kernelILi(\d+)ELi(\d+)E14XnaCosEpilogueE.*?LDS Size[^\n]*", txt, flags=re.S):
             nct = int(m.group(2))
             g = lambda key: int(re.search(key + r"[^:\n]*: (\d+)", m.group(0)).group(1))
             lds = ks * ks * (72 + nct * 16 + 16 + 64 + 16) * 2
