@@ -476,8 +476,10 @@ int naf_pack_values(void* vp, const void* v, int32_t v_dtype, int32_t B, int32_t
  *   naf_xna_cos_fwd              as naf_xna_head_fwd, with v_lr held to the rule of q, k_lr and pv_lr; out and norms are stored element by
  *                  element: 4-byte aligned, any strides {b, y, x} (out: x stride >= N).
  *   naf_xna_cos_ce_fwd           as naf_xna_cos_fwd; dlogits held to the rule of naf_xna_head_ce_fwd's (16-byte aligned, strides {b, y, x}
- *                  multiples of 8 elements, x stride >= dlogits_channels, else -NAF_ERR_UNSUPPORTED); target, loss, labels and dscale are
- *                  read / stored element by element: aligned to their element size, any strides {b, y, x}. */
+ *                  multiples of 8 elements, else -NAF_ERR_UNSUPPORTED; x stride >= dlogits_channels); target, loss, labels and dscale are
+ *                  read / stored element by element: aligned to their element size, any strides {b, y, x}.
+ *                  A row too short for what is stored in it (out: x stride < N, dlogits: x stride < dlogits_channels) is no layout any
+ *                  kernel could serve: -NAF_ERR_INVALID, for these two entries as for the head's. */
 
 /* ---- cross-scale neighbourhood attention forward -------------------------------------------------
  * Replaces legacy_attention (attentions.py:16-29: na2d_qk -> *scale -> softmax -> na2d_av), the fused

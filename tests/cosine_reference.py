@@ -67,14 +67,18 @@ NCT_OF = lambda n: 2 if n <= 32 else 4 if n <= 64 else 10 if n <= 160 else 16
 WINDOWS = (3, 5, 7, 9, 11, 13, 15)
 
 
-def make_inputs(name, seed=5100, zero_block=None, const_v=False):
+def make_inputs(name, seed=5100, zero_block=None, const_v=False, geom=None, chan_offset=0.0):
     """q [B, heads*64, Ho, Wo], k [B, heads*64, h, w], v [B, C, h, w] fp32 tensors holding bf16 values, E [N, C] fp32.
-    ``zero_block`` = (y0, y1, x0, x1): the features of those low-res cells are zero.  ``const_v``: every cell holds the same vector."""
-    B, heads, Dv, (h, w), (dy, dx), ks, N = CASES[name]
+    ``zero_block`` = (y0, y1, x0, x1): the features of those low-res cells are zero.  ``const_v``: every cell holds the same vector.
+    ``geom``: a geometry in the form of a CASES entry, used in place of CASES[name] (tests/layout_contract.py: COS_GEOMS).
+    ``chan_offset``: every value channel gets an offset of its own, hash_normal((1, C, 1, 1), seed) times this, before the bf16 rounding,
+    so that a head, a channel or an image read from the wrong place shows."""
+    B, heads, Dv, (h, w), (dy, dx), ks, N = CASES[name] if geom is None else geom
     C = heads * Dv
     q = S.bf16r(O.hash_normal((B, heads * DQ, h * dy, w * dx), seed + 1))
     k = S.bf16r(O.hash_normal((B, heads * DQ, h, w), seed + 2))
-    v = S.bf16r(O.hash_normal((B, C, h, w), seed + 3) + (0.5 if const_v else 0.0))
+    off = O.hash_normal((1, C, 1, 1), seed) * chan_offset if chan_offset else 0.0
+    v = S.bf16r(O.hash_normal((B, C, h, w), seed + 3) + off + (0.5 if const_v else 0.0))
     if const_v:
         v = v[:, :, :1, :1].expand(B, C, h, w).contiguous()
     if zero_block is not None:

@@ -2,8 +2,8 @@
 tests/test_gpu_layout_contract.py on one).  Plain helper module: no test in it.
 
 The contract (include/naf_hip.h, "LAYOUT CONTRACT OF THE ATTENTION ENTRIES"): every operand of naf_xna_fwd, naf_xna_head_fwd,
-naf_xna_head_ce_fwd, naf_xna_mse_fwd and naf_xna_bwd is a pointer plus four element strides {b, head, y, x} with the last dim
-contiguous, and the kernels honour every stride of every operand on its own.  The matrix-core kernels take 16-byte aligned pointers and
+naf_xna_head_ce_fwd, naf_xna_cos_fwd, naf_xna_cos_ce_fwd, naf_xna_mse_fwd and naf_xna_bwd is a pointer plus four element strides {b, head,
+y, x} with the last dim contiguous, and the kernels honour every stride of every operand on its own.  The matrix-core kernels take 16-byte aligned pointers and
 strides that are multiples of 8 elements (4 for `out` of the forward); everything else runs, under AUTO, a kernel that reads and writes
 that operand element by element, and is refused with NAF_ERR_UNSUPPORTED where a path is insisted on.
 
@@ -219,6 +219,13 @@ def head_admits(q, k, pv, dlogits=None):
     return vec_ok(q) and vec_ok(k) and vec_ok(pv) and (dlogits is None or vec_ok(dlogits))
 
 
+def cos_admits(q, k, pv, v, dlogits=None):
+    """xna_cos.hip:22-23 (naf_xna_cos_eligible): q / k / pv AND v vectorisable (`out` and norms are stored element by element: any
+    strides); :40-50 (naf_xna_cos_ce_eligible): dlogits too -- 16-byte aligned, its strides {b, y, x} multiples of 8 (target, loss, labels
+    and dscale are read / stored element by element)."""
+    return vec_ok(q) and vec_ok(k) and vec_ok(pv) and vec_ok(v) and (dlogits is None or vec_ok(dlogits))
+
+
 # ---- the cases of tests/test_gpu_layout_contract.py (here so that the CPU table sweeps the same geometries) -----------------------
 B2 = 2
 # (FWD_CASES id, out dtype, variant): variant None, "logits" (return_logits), "rope" (rotate-on-load), "half" (float16 values and output)
@@ -240,6 +247,37 @@ HEAD_N = 21
 # 14 of a row tile's 16 lanes hold a pixel and the epilogues mask the other two
 HEAD_GEOMS = {"tiles16": (B2, 8, 8, 8, 16, 7, 4), "patch14": (B2, 8, 9, 2, 14, 7, 2)}
 MSE_CASE = "b_f4_k3"                            # tests/regress_reference.py: B = 2, ratio 4.6 x 4.3, a 14-pixel partial tile
+# The cosine head, (B, heads, Dv, (h, w), (dy, dx), window, N) as tests/cosine_reference.CASES: the smallest geometries that reach the
+# paths named, each with Dv != head_npad(N), so that pv_lr's strides and v_lr's differ in every family
+COS_GEOMS = {
+    "tiles16": (B2, 4, 48, (8, 8), (8, 16), 7, 21),       # whole 16-pixel row tiles, one partly filled 64-channel value chunk, two channel tiles
+    "patch14": (B2, 2, 80, (8, 9), (2, 14), 7, 21),       # 14 of 16 lanes hold a pixel, two value chunks of which the second is partial
+    "n151": (B2, 2, 128, (5, 6), (2, 16), 5, 151),        # ten channel tiles, two whole value chunks
+}
+COS_SCALE = {"tiles16": 1.0, "patch14": 1.0, "n151": 14.285714}        # one CLIP-style temperature, as tests/test_gpu_cosine_head.py has
+COS_IGNORE = 255
+
+
+def cos_inputs(gname):
+    """cosine_reference.make_inputs on a COS_GEOMS geometry, the value channels with offsets of their own: (q, k, v, E) on the host."""
+    import cosine_reference as CR
+    return CR.make_inputs(None, geom=COS_GEOMS[gname], chan_offset=1.0)
+
+
+def cos_shapes(gname):
+    """(window, N, {operand: 5-D shape}) of a COS_GEOMS geometry; the maps of the entries are [B, 1, Ho, Wo, channels]."""
+    from naf_amd import ops
+    B, heads, Dv, (h, w), (dy, dx), ks, N = COS_GEOMS[gname]
+    Ho, Wo = h * dy, w * dx
+    return ks, N, {"q": (B, heads, Ho, Wo, 64), "k": (B, heads, h, w, 64), "pv": (B, heads, h, w, ops.head_npad(N)), "v": (B, heads, h, w, Dv),
+                   "out": (B, 1, Ho, Wo, N), "norms": (B, 1, Ho, Wo, 1), "target": (B, 1, Ho, Wo, 1), "loss": (B, 1, Ho, Wo, 1),
+                   "labels": (B, 1, Ho, Wo, 1), "dlogits": (B, 1, Ho, Wo, ops.head_dlogits_channels(N)), "dscale": (B, 1, Ho, Wo, 1)}
+
+
+COS_DTYPES = {"q": torch.bfloat16, "k": torch.bfloat16, "pv": torch.bfloat16, "v": torch.bfloat16, "out": torch.float32, "norms": torch.float32,
+              "target": torch.int64, "loss": torch.float32, "labels": torch.uint8, "dlogits": torch.bfloat16, "dscale": torch.float32}
+COS_INPUTS, COS_OUTPUTS = ("q", "k", "pv", "v"), ("out", "norms")
+COS_CE_INPUTS, COS_CE_OUTPUTS = ("q", "k", "pv", "v", "target"), ("out", "norms", "loss", "labels", "dlogits", "dscale")
 
 
 def run_id(run):
@@ -413,6 +451,45 @@ def head_launch(a, sel, q, ce=False):
     with torch.cuda.device(q.device):
         rc = (lib.naf_xna_head_ce_fwd if ce else lib.naf_xna_head_fwd)(C.byref(a), ops._stream(q))
     _lib.check(rc, "naf_xna_head_ce_fwd" if ce else "naf_xna_head_fwd")
+
+
+def cos_args(q, k, pv, v, out, norms, n_out, ksz, logit_scale=1.0, path="fused", rope_tables=None):
+    """(naf_xna_cos_args, naf_xna_cos_select's answer).  ``out``: [B, Ho, Wo, N], ``norms``: [B, Ho, Wo] or None, by strides {b, y, x}."""
+    from naf_amd import _lib, ops
+    ky, kx = ops._ksize(ksz)
+    a = ops._fill_xna_cos(q, k, pv, v, out, norms, n_out, ky, kx, path, None, logit_scale, rope_tables)
+    return a, int(_lib.load().naf_xna_cos_select(C.byref(a)))
+
+
+def cos_ce_args(q, k, pv, v, out, norms, n_out, ksz, target, loss, labels, dlogits, dscale, ignore_index=COS_IGNORE, logit_scale=1.0, path="fused",
+                scale_ptr=None, rope_tables=None):
+    """(naf_xna_cos_ce_args, naf_xna_cos_ce_select's answer): ops.xna_cos_objective's filling with the caller's buffers, each of which may
+    be None.  ``scale_ptr``: a 1-element fp32 device tensor that replaces ``logit_scale``."""
+    from naf_amd import _lib, ops
+    ky, kx = ops._ksize(ksz)
+    a = _lib.XnaCosCEArgs()
+    a.cos = ops._fill_xna_cos(q, k, pv, v, out if out is not None else q, norms, n_out, ky, kx, path, None, logit_scale, rope_tables)
+    if out is None:
+        a.cos.out, a.cos.o_stride = None, ops.I64x3(0, 0, 0)
+    a.ignore_index = int(ignore_index)
+    a.dlogits_channels = int(dlogits.shape[-1]) if dlogits is not None else ops.head_dlogits_channels(n_out)
+    if scale_ptr is not None:
+        a.logit_scale_ptr = scale_ptr.data_ptr()
+    for t, ptr, st in ((target, "target", "t_stride"), (loss, "loss", "loss_stride"), (labels, "labels", "labels_stride"),
+                       (dlogits, "dlogits", "dlogits_stride"), (dscale, "dscale", "dscale_stride")):
+        if t is not None:
+            setattr(a, ptr, t.data_ptr())
+            setattr(a, st, ops._strides3(t))
+    return a, int(_lib.load().naf_xna_cos_ce_select(C.byref(a)))
+
+
+def cos_launch(a, sel, q, ce=False):
+    from naf_amd import _lib, ops
+    assert sel == _lib.XNA_HEAD_FUSED, "only layouts the host checks accept are launched"
+    lib = _lib.load()
+    with torch.cuda.device(q.device):
+        rc = (lib.naf_xna_cos_ce_fwd if ce else lib.naf_xna_cos_fwd)(C.byref(a), ops._stream(q))
+    _lib.check(rc, "naf_xna_cos_ce_fwd" if ce else "naf_xna_cos_fwd")
 
 
 def mse_args(q, k, v, target, dout, ksz):

@@ -1,14 +1,29 @@
-"""GPU tests (-m gpu) of the layout contract of the attention entries: naf_xna_fwd, naf_xna_head_fwd, naf_xna_head_ce_fwd, naf_xna_mse_fwd
-and naf_xna_bwd take every operand as a pointer plus four element strides; the kernels must honour each stride of each operand on its
-own, write nothing but their outputs and let nothing that lies next to an input reach a result.  tests/layout_contract.py describes the
-families, the arenas and the sentinels; tests/test_layout_contract_cpu.py holds the host side (what the eligibility checks answer for
-every case and family here) and shows that the technique reports two planted defects.
+"""GPU tests (-m gpu) of the layout contract of the attention entries: naf_xna_fwd, naf_xna_head_fwd, naf_xna_head_ce_fwd, naf_xna_cos_fwd,
+naf_xna_cos_ce_fwd, naf_xna_mse_fwd and naf_xna_bwd take every operand as a pointer plus four element strides; the kernels must honour
+each stride of each operand on its own, write nothing but their outputs and let nothing that lies next to an input reach a result.
+tests/layout_contract.py describes the families, the arenas and the sentinels; tests/test_layout_contract_cpu.py holds the host side
+(what the eligibility checks answer for every case and family here) and shows that the technique reports three planted defects.
 
 Every case runs at B = 2 (no per-element bound test of the suite has a batch stride that is multiplied by anything but 0) on the
 geometries tests/input_statistics.py uses to reach each kernel, the kernel that runs is asserted -- naf_xna_select /
 naf_xna_bwd_supported / naf_xna_head_select on the very arguments of every launch, cell versus sliding from the profiler's kernel names
 as tests/test_gpu_input_statistics.py does -- and only layouts the host checks accept are launched.  The head runs on
 input_statistics.HEAD_GEOM (whole 16-pixel row tiles) and on 14-pixel cells, where its epilogues mask two lanes of every tile.
+
+The cosine head (naf_xna_cos_fwd, naf_xna_cos_ce_fwd) runs on layout_contract.COS_GEOMS: whole 16-pixel row tiles, 14-pixel cells and
+151 embeddings (ten channel tiles), with one, one and a half and two 64-channel value chunks per head and Dv != Npad everywhere, so
+that pv_lr's strides and v_lr's differ in every family; the value channels carry offsets of their own
+(test_layout_contract_cpu.py::test_cos_inputs_show_a_misplaced_read: a head, channel, row, column or image read from the wrong place
+leaves twice the bound).  q, k_lr, pv_lr, v_lr and the int64 target are input arenas; the cosines, the norm map, the loss map, the
+labels, dlogits and dscale are output arenas, each with strides of its own.  The canonical launch is held to the derived bounds of
+tests/cosine_reference.py / cosine_objective_reference.py (the objective's cosines and norms: bit for bit naf_xna_cos_fwd's), every
+other launch to the canonical bits -- the kernel has no atomics.  Beyond the launch set below: head stride 0 on k_lr, pv_lr and v_lr,
+batch stride 0 on the target, rotate-on-load on the 14-pixel cells (its canonical launch is bit for bit the launch on materialised
+queries), outputs handed over as NULL (the others keep their bits, the NULL ones' arenas are not written), and the logit scale as a
+device value.  The header's routing rules for the two entries: the element-wise operands (out, norms, loss, labels, dscale, target) in
+``odd_offset`` / ``odd_stride`` still run the fused kernel, bit-equal; q, k_lr, pv_lr, v_lr or dlogits there are refused with
+-NAF_ERR_UNSUPPORTED under AUTO and FUSED alike, and ops.xna_cos_forward / xna_cos_objective (path="auto") then return the
+composition inside cosine_reference.composed_bound.
 
 Launch set per case (layout_contract.launch_plans): (a) every operand in one family, for each of the eight vectorisable families; (b)
 each operand in turn in ``crop`` and the rest head-major; (c) q, k head-major and everything else channels-last, what the model hands
@@ -43,6 +58,8 @@ import torch.nn.functional as F
 from oracle import naf_oracle as O
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cosine_objective_reference as CQ  # noqa: E402
+import cosine_reference as CR  # noqa: E402
 import half_reference as HR  # noqa: E402
 import input_statistics as S  # noqa: E402
 import layout_contract as LC  # noqa: E402
@@ -426,6 +443,221 @@ def test_head_objective_layouts(dev, gname):
     assert not canon_e[1]
     compare_head("expanded", head_once(de, dict(dense, k="expanded", pv="expanded"), dev, F32, ce=td), canon_e, failures)
     assert not failures, "\n".join(failures)
+
+
+# ---- the cosine head ---------------------------------------------------------------------------------------------------------------
+_COS = {}
+
+
+def cos_data(dev, gname):
+    """Device operands of a COS_GEOMS geometry and the fp64 reference at the geometry's logit scale: once, shared, never modified."""
+    if gname not in _COS:
+        from naf_amd import ops
+        B, heads, Dv, lr, cell, ks, N = LC.COS_GEOMS[gname]
+        q, k, v, E = LC.cos_inputs(gname)
+        v5 = LC.to5(v, heads).to(dev)
+        d = {"q": LC.to5(q, heads).to(dev), "k": LC.to5(k, heads).to(dev), "v": v5, "pv": ops.project_cosine_values(E.to(dev), v5), "E": E.to(dev),
+             "geom": LC.COS_GEOMS[gname], "ls": LC.COS_SCALE[gname], "tables": None}
+        assert d["pv"].shape[4] == ops.head_npad(N) != Dv
+        _COS[gname] = (d, CR.reference(q, k, v, E, ks, heads, d["ls"]))
+    return _COS[gname]
+
+
+def cos_once(d, plan, dev, ce=None, null=(), scale_ptr=None):
+    """One launch of naf_xna_cos_fwd, or (``ce`` = the int64 device target [B, Ho, Wo]) of naf_xna_cos_ce_fwd, every operand in the family
+    ``plan`` gives it: ({output name: dense tensor}, problems).  ``null``: outputs handed over as NULL -- their arenas exist all the same
+    and must come back bit-unchanged.  ``scale_ptr``: the logit scale as a device value."""
+    from naf_amd import _lib, ops
+    B, heads, Dv, (h, w), (dy, dx), ks, N = d["geom"]
+    Ho, Wo = h * dy, w * dx
+    P = LC.Placed()
+    t = {o: P.add(o, LC.embed(d[o], plan[o])) for o in LC.COS_INPUTS}
+    if ce is not None:
+        t["target"] = LC.hw2(P.add("target", LC.embed(ce.view(B, 1, Ho, Wo, 1), plan["target"])))
+    channels = {"out": N, "dlogits": ops.head_dlogits_channels(N)}
+    outs = {}
+    for o in (LC.COS_CE_OUTPUTS if ce is not None else LC.COS_OUTPUTS):
+        view = P.add(o, LC.arena_for((B, 1, Ho, Wo, channels.get(o, 1)), LC.COS_DTYPES[o], plan[o], dev), output=True)
+        outs[o] = LC.hw3(view) if o in channels else LC.hw2(view)
+    P.snapshot()
+    given = {o: (None if o in null else v) for o, v in outs.items()}
+    if ce is None:
+        a, sel = LC.cos_args(t["q"], t["k"], t["pv"], t["v"], given["out"], given["norms"], N, ks, d["ls"], rope_tables=d["tables"])
+    else:
+        a, sel = LC.cos_ce_args(t["q"], t["k"], t["pv"], t["v"], given["out"], given["norms"], N, ks, t["target"], given["loss"], given["labels"],
+                                given["dlogits"], given["dscale"], LC.COS_IGNORE, d["ls"], scale_ptr=scale_ptr, rope_tables=d["tables"])
+    assert sel == _lib.XNA_HEAD_FUSED, f"{plan}: the cosine head's select gives {sel}"
+    LC.cos_launch(a, sel, t["q"], ce is not None)
+    torch.cuda.synchronize()
+    problems = P.problems() + [f"{o}: handed over as NULL and written all the same" for o in null if not LC.unchanged(P.arenas[o], P.before[o])]
+    return {n: o.contiguous() for n, o in outs.items() if n not in null}, problems
+
+
+def cos_stride0_sets(d, dense, dev, failures, ce=None, heads_too=True):
+    """``expanded`` on k, pv, v (and the target) with their images made equal, ``expanded_head`` on k, pv, v with their heads made equal:
+    each against a canonical launch of its own."""
+    names = ("k", "pv", "v")
+    de, plan = dict(d, **{o: equal_images(d[o]) for o in names}), dict(dense, **{o: "expanded" for o in names})
+    te = None
+    if ce is not None:
+        te, plan["target"] = equal_images(ce), "expanded"
+    canon_e = cos_once(de, dense, dev, te)
+    assert not canon_e[1] and all(finite(o) for o in canon_e[0].values()), canon_e[1]
+    compare_head("expanded", cos_once(de, plan, dev, te), canon_e, failures)
+    if heads_too:
+        dh = dict(d, **{o: equal_heads(d[o]) for o in names})
+        canon_h = cos_once(dh, dense, dev, ce)
+        assert not canon_h[1] and all(finite(o) for o in canon_h[0].values()), canon_h[1]
+        compare_head("expanded-head", cos_once(dh, dict(dense, **{o: "expanded_head" for o in names}), dev, ce), canon_h, failures)
+
+
+@pytest.mark.parametrize("gname", list(LC.COS_GEOMS))
+def test_cos_layouts(dev, gname):
+    """naf_xna_cos_fwd with q, k_lr, pv_lr, v_lr, the cosines and the norm map each in an arena with strides of its own (pv_lr and v_lr
+    have other last dims, so their strides differ in every family).  The canonical launch is held to the derived bounds of
+    tests/cosine_reference.py against the fp64 definition at B = 2; every other launch to its bits.  On the 14-pixel cells the same with
+    rotate-on-load, whose canonical launch is bit for bit the launch on materialised queries."""
+    from naf_amd import ops
+    d, r = cos_data(dev, gname)
+    B, heads, Dv, (h, w), (dy, dx), ks, N = d["geom"]
+    dense = {o: LC.CANONICAL for o in LC.COS_INPUTS + LC.COS_OUTPUTS}
+    canon = cos_once(d, dense, dev)
+    again = cos_once(d, dense, dev)
+    assert all(LC.same_bits(canon[0][n], again[0][n]) for n in canon[0]), "two canonical launches differ"
+    assert not canon[1] and finite(canon[0]["out"]) and finite(canon[0]["norms"]), canon[1]
+    record(f"cos      {gname + ' cosines, norms':<34s} kernel fused")
+    CR.check(canon[0]["out"].permute(0, 3, 1, 2).cpu(), r["cos"], CR.bound(r), f"cosines {gname} canonical, B = {B}")
+    CR.check(canon[0]["norms"].cpu(), r["norms"], CR.norms_bound(r), f"norms {gname} canonical, B = {B}")
+    failures = []
+    for label, plan in LC.launch_plans(LC.COS_INPUTS, LC.COS_OUTPUTS):
+        compare_head(label, cos_once(d, plan, dev), canon, failures)
+    cos_stride0_sets(d, dense, dev, failures)
+    compare_head("norms = NULL", cos_once(d, dense, dev, null=("norms",)), canon, failures)
+    if gname == "patch14":
+        # rotate-on-load: q is the un-rotated guidance, the keys and the materialised queries come from naf_rope_pool_fwd
+        x = S.bf16r(O.hash_normal((B, heads * 64, h * dy, w * dx), 310) * 4.0)
+        xd = x.to(dev).to(BF16).contiguous(memory_format=torch.channels_last)
+        ty, tx = ops.rope_tables(O.rope_periods(heads * 64, heads, 100.0).to(dev), h * dy, w * dx)
+        q_mat, k5 = ops.rope_pool(xd, ty, tx, heads, (h, w))
+        dr = dict(d, q=xd.permute(0, 2, 3, 1).unflatten(3, (heads, 64)).permute(0, 3, 1, 2, 4).contiguous(), k=k5.contiguous(), tables=(ty, tx))
+        canon_r = cos_once(dr, dense, dev)
+        assert not canon_r[1] and finite(canon_r[0]["out"]) and finite(canon_r[0]["norms"]), canon_r[1]
+        mat = cos_once(dict(dr, q=q_mat.contiguous(), tables=None), dense, dev)
+        assert all(LC.same_bits(canon_r[0][n], mat[0][n]) for n in mat[0]), "rotate-on-load differs from materialised queries"
+        record(f"cos      {gname + ' cosines, norms, rope':<34s} kernel fused")
+        for label, plan in LC.launch_plans(LC.COS_INPUTS, LC.COS_OUTPUTS):
+            compare_head(f"rope {label}", cos_once(dr, plan, dev), canon_r, failures)
+    assert not failures, "\n".join(failures)
+
+
+@pytest.mark.parametrize("gname", list(LC.COS_GEOMS))
+def test_cos_objective_layouts(dev, gname):
+    """naf_xna_cos_ce_fwd with the cosines, the norm map, the loss map, the labels, dlogits and dscale each in an arena with strides of its
+    own, and the int64 target in an input arena.  The canonical launch is anchored: its cosines and norms are bit for bit
+    naf_xna_cos_fwd's at the same scale; loss, labels, dlogits and dscale lie inside the derived bounds of
+    tests/cosine_objective_reference.py; pad channels and ignored pixels are exactly zero."""
+    d, r = cos_data(dev, gname)
+    B, heads, Dv, (h, w), (dy, dx), ks, N = d["geom"]
+    t = make_target(B, h * dy, w * dx, N, LC.COS_IGNORE, "oob")          # about a tenth ignored, image row 5 outside [0, N)
+    valid = valid_of(t, LC.COS_IGNORE, N)
+    assert bool(((t != LC.COS_IGNORE) & ~valid).any()) and bool(valid.any())
+    td = t.to(dev)
+    o = CQ.objective(r, t, LC.COS_IGNORE)
+    dense = {n: LC.CANONICAL for n in LC.COS_CE_INPUTS + LC.COS_CE_OUTPUTS}
+    canon = cos_once(d, dense, dev, td)
+    again = cos_once(d, dense, dev, td)
+    assert all(LC.same_bits(canon[0][n], again[0][n]) for n in canon[0]), "two canonical launches differ"
+    assert not canon[1], canon[1]
+    record(f"cos      {gname + ' objective':<34s} kernel fused (cosines, norms, loss map, labels, dlogits, dscale; logit scale {d['ls']:g})")
+    plain = cos_once(d, {n: LC.CANONICAL for n in LC.COS_INPUTS + LC.COS_OUTPUTS}, dev)
+    assert LC.same_bits(canon[0]["out"], plain[0]["out"]), "the objective's cosines are not naf_xna_cos_fwd's"
+    assert LC.same_bits(canon[0]["norms"], plain[0]["norms"]), "the objective's norms are not naf_xna_cos_fwd's"
+    loss, labels, g, ds = canon[0]["loss"].cpu(), canon[0]["labels"].cpu(), canon[0]["dlogits"].float().cpu(), canon[0]["dscale"].cpu()
+    CR.check(loss, o["loss"], CQ.loss_bound(r, o), f"loss {gname} canonical, B = {B}")
+    CQ.check_labels(labels, r, o, f"labels {gname} canonical, B = {B}")
+    CR.check(g[..., :N], o["g"], CQ.g_bound(r, o), f"dlogits {gname} canonical, B = {B}")
+    CR.check(ds, o["ds"], CQ.ds_bound(r, o), f"dscale {gname} canonical, B = {B}")
+    assert g.shape[-1] > N and float(g[..., N:].abs().max()) == 0.0
+    assert float(loss[~valid].abs().max()) == 0.0 and float(g[~valid].abs().max()) == 0.0 and float(ds[~valid].abs().max()) == 0.0
+    failures = []
+    for label, plan in LC.launch_plans(LC.COS_CE_INPUTS, LC.COS_CE_OUTPUTS):
+        compare_head(label, cos_once(d, plan, dev, td), canon, failures)
+    cos_stride0_sets(d, dense, dev, failures, td, heads_too=False)
+    compare_head("out = norms = NULL", cos_once(d, dense, dev, td, null=("out", "norms")), canon, failures)
+    compare_head("logit scale on the device", cos_once(d, dense, dev, td, scale_ptr=torch.tensor([d["ls"]], dtype=F32, device=dev)), canon, failures)
+    assert not failures, "\n".join(failures)
+
+
+def test_cos_element_wise_outputs_take_any_layout(dev):
+    """out, norms, loss, labels, dscale and the target in ``odd_offset`` (pointer + 4 elements) and ``odd_stride`` (x stride C + 4), on the
+    14-pixel cells: the header has them read and stored element by element, so both selects still answer FUSED (asserted in cos_once), the
+    results are the canonical launch's bits and the guard bands stay."""
+    gname = "patch14"
+    d, r = cos_data(dev, gname)
+    B, heads, Dv, (h, w), (dy, dx), ks, N = d["geom"]
+    td = make_target(B, h * dy, w * dx, N, LC.COS_IGNORE, "oob").to(dev)
+    failures = []
+    for ce, ins, outs in ((None, LC.COS_INPUTS, LC.COS_OUTPUTS), (td, LC.COS_CE_INPUTS, LC.COS_CE_OUTPUTS)):
+        dense = {n: LC.CANONICAL for n in ins + outs}
+        canon = cos_once(d, dense, dev, ce)
+        assert not canon[1], canon[1]
+        for fam in LC.ROUTING_FAMILIES:
+            plan = {n: (fam if n in ("out", "norms", "loss", "labels", "dscale", "target") else LC.CANONICAL) for n in ins + outs}
+            compare_head(f"{'objective' if ce is not None else 'cosines'} {fam}", cos_once(d, plan, dev, ce), canon, failures)
+            record(f"cos      {gname + (' objective ' if ce is not None else ' cosines ') + fam:<34s} kernel fused (element-wise operands in {fam})")
+    assert not failures, "\n".join(failures)
+
+
+def test_cos_refuses_layouts_that_are_not_vectorisable(dev):
+    """q, k_lr, pv_lr or v_lr (and dlogits, for the objective) in ``odd_offset`` / ``odd_stride``: both selects answer -NAF_ERR_UNSUPPORTED,
+    not INVALID, under AUTO and FUSED alike, and nothing is launched.  ops.xna_cos_forward / xna_cos_objective (path="auto") then compose:
+    the plain forward on the strided queries, normalised in torch, inside the composition's own derived bound."""
+    from naf_amd import ops
+    gname = "patch14"
+    d, r = cos_data(dev, gname)
+    B, heads, Dv, (h, w), (dy, dx), ks, N = d["geom"]
+    _, _, shapes = LC.cos_shapes(gname)
+    for fam in LC.ROUTING_FAMILIES:
+        for o in LC.COS_INPUTS + ("dlogits",):
+            t = {n: LC.arena_for(shapes[n], LC.COS_DTYPES[n], fam if n == o else LC.CANONICAL, dev, mask=False)[0] for n in shapes}
+            for p in ("auto", "fused"):
+                if o != "dlogits":
+                    assert LC.cos_args(t["q"], t["k"], t["pv"], t["v"], LC.hw3(t["out"]), LC.hw2(t["norms"]), N, ks, path=p)[1] == -2, (fam, o, p)
+                sel = LC.cos_ce_args(t["q"], t["k"], t["pv"], t["v"], LC.hw3(t["out"]), LC.hw2(t["norms"]), N, ks, LC.hw2(t["target"]), LC.hw2(t["loss"]),
+                                     LC.hw2(t["labels"]), LC.hw3(t["dlogits"]), LC.hw2(t["dscale"]), path=p)[1]
+                assert sel == -2, (fam, o, p, sel)
+    # the Python entries on such a q: a 5-D view whose pixel stride is no multiple of 8
+
+    class Spy:
+        def __init__(self):
+            self.names = []
+
+        def start(self, name):
+            self.names.append(name)
+
+        def stop(self, name):
+            pass
+
+    q = LC.embed(d["q"], "odd_stride")[0]
+    assert q.stride(3) % 8 != 0 and q.dim() == 5
+    t = make_target(B, h * dy, w * dx, N, LC.COS_IGNORE, "oob")
+    old, spy = ops.KERNEL_TIMER, Spy()
+    ops.KERNEL_TIMER = spy
+    try:
+        cos, nrm = ops.xna_cos_forward(q, d["k"], d["v"], d["E"], ks, logit_scale=d["ls"], return_norms=True, path="auto")
+        loss, labels, g, ds = ops.xna_cos_objective(q, d["k"], d["v"], d["E"], ks, target=t.to(dev), ignore_index=LC.COS_IGNORE, logit_scale=d["ls"],
+                                                    want_loss=True, want_labels=True, want_dlogits=True, want_dscale=True, path="auto")
+        torch.cuda.synchronize()
+    finally:
+        ops.KERNEL_TIMER = old
+    assert "xna_cos_composed" in spy.names and "xna_cos_ce_composed" in spy.names and "xna_cos" not in spy.names and "xna_cos_ce" not in spy.names, spy.names
+    cb, cnb = CR.composed_bound(r)
+    CR.check(cos.cpu(), r["cos"], cb, "composed cosines, q with an odd pixel stride")
+    CR.check(nrm.cpu(), r["norms"], cnb, "composed norms, q with an odd pixel stride")
+    o = CQ.objective(r, t, LC.COS_IGNORE)
+    CR.check(loss.cpu(), o["loss"], 2.0 * cb.amax(dim=1) + 1e-5 * (1.0 + o["lse"].abs() + o["zt"].abs()), "composed loss, q with an odd pixel stride")
+    assert labels.shape == ds.shape == loss.shape and g.shape[-1] == ops.head_dlogits_channels(N) and float(g[..., N:].float().abs().max()) == 0.0
+    assert float(g.float().cpu()[~o["valid"]].abs().max()) == 0.0 and float(ds.cpu()[~o["valid"]].abs().max()) == 0.0
 
 
 # ---- the regression objective ------------------------------------------------------------------------------------------------------

@@ -189,8 +189,9 @@ def test_strided_keys_and_values_give_the_dense_result(dev, family):
         k5, v5 = k5[:1].expand(B, -1, -1, -1, -1).contiguous(), v5[:1].expand(B, -1, -1, -1, -1).contiguous()
     pd = PR.make_points(B, *c["out"], 21).to(dev, torch.int32)
     want = ops.xna_points(q5, k5, v5, pd, c["ksz"], want_probs=True)
-    # (the queries differ between the images: they stay head-major where the family is the stride-0 one)
-    placed = [LC.embed(q5, "head_major" if family == "expanded" else family), LC.embed(k5, family), LC.embed(v5, family)]
+    # q is a placed operand too (naf_xna_points takes q_stride[4]).  The queries differ between the images, so where the family is the
+    # stride-0 one they sit in the crop: a batch stride of their own next to keys and values that have none
+    placed = [LC.embed(q5, "crop" if family == "expanded" else family), LC.embed(k5, family), LC.embed(v5, family)]
     before = [a.clone() for _, a, _ in placed]
     if family == "expanded":
         assert placed[1][0].stride(0) == 0 and placed[2][0].stride(0) == 0

@@ -4,16 +4,20 @@
    family claims, the margins hold, everything else of the arena is the sentinel.
 2. The contract as a table.  Host pointers that nothing dereferences (the precedent is
    tests/test_head_cpu.py::test_select_refuses_misaligned_and_null): for every case of tests/test_gpu_layout_contract.py and every
-   family, what naf_xna_select, naf_xna_bwd_supported, naf_xna_head_select / naf_xna_head_ce_select and naf_xna_mse_supported answer.
+   family, what naf_xna_select, naf_xna_bwd_supported, naf_xna_head_select / naf_xna_head_ce_select, naf_xna_cos_select /
+   naf_xna_cos_ce_select and naf_xna_mse_supported answer.
    The vectorisable families get the kernel of the dense layout.  ``odd_offset`` / ``odd_stride`` on one operand get, under AUTO, a
    kernel whose eligibility test (restated in layout_contract.*_admits, with the source lines) admits that layout -- the dense layout's
    kernel where it still does -- and -NAF_ERR_UNSUPPORTED where the dense layout's kernel is insisted on and does not.
-3. Teeth: two defects emulated in torch on an arena -- a writer that stores all 16 lanes of a partial tile, a reader that takes
-   W * x_stride for the row stride -- and what ``untouched`` and the equality checks say about each; on the dense layouts the rest of the
-   suite uses, the second defect is invisible.
+3. Teeth: three defects emulated in torch on an arena -- a writer that stores all 16 lanes of a partial tile, a reader that takes
+   W * x_stride for the row stride, a writer of the cosine head's norm map that takes its strides from `out`'s -- and what ``untouched``
+   and the equality checks say about each; on the dense layouts the rest of the suite uses, the last two are invisible.  And the inputs
+   of the cosine cases: the fp64 definition on values (keys) read from the wrong image, head, channel, row or column leaves twice the
+   bound the canonical launch is held to.
 4. ops.xna_forward(out=...) refuses a wrong-shaped buffer before anything else happens.
 """
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -21,10 +25,12 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import cosine_reference as CR  # noqa: E402
 import input_statistics as S  # noqa: E402
 import layout_contract as LC  # noqa: E402
 import regress_reference as R  # noqa: E402
 
+INVALID = -1           # -NAF_ERR_INVALID
 UNSUPPORTED = -2       # -NAF_ERR_UNSUPPORTED
 
 
@@ -273,6 +279,86 @@ def test_head_select_table(lib, out_dtype, gname):
                     assert sel == (_lib.XNA_HEAD_FUSED if ok else UNSUPPORTED), (fam, o, sel)
 
 
+@pytest.mark.parametrize("gname", list(LC.COS_GEOMS))
+def test_cos_select_table(lib, gname):
+    """naf_xna_cos_select / naf_xna_cos_ce_select against layout_contract.cos_admits: q / k_lr / pv_lr / v_lr (and dlogits) that are not
+    vectorisable are -NAF_ERR_UNSUPPORTED under AUTO and FUSED alike; out, norms, target, loss, labels and dscale take any strides and any
+    alignment of their element size; an `out` row shorter than N and a dlogits row shorter than dlogits_channels are -NAF_ERR_INVALID."""
+    from naf_amd import _lib
+    ksz, N, shapes = LC.cos_shapes(gname)
+    B, heads, Dv, lr, cell, _, _ = LC.COS_GEOMS[gname]
+    assert Dv != shapes["pv"][4], "pv_lr and v_lr would have the same strides in every family"
+    keep = []
+
+    def select(plan, p, ce):
+        t = {}
+        for o in shapes:
+            t[o], arena = _fake(shapes[o], LC.COS_DTYPES[o], plan[o])
+            keep.append(arena)
+        if ce:
+            return t, LC.cos_ce_args(t["q"], t["k"], t["pv"], t["v"], LC.hw3(t["out"]), LC.hw2(t["norms"]), N, ksz, LC.hw2(t["target"]), LC.hw2(t["loss"]),
+                                     LC.hw2(t["labels"]), LC.hw3(t["dlogits"]), LC.hw2(t["dscale"]), path=p)[1]
+        return t, LC.cos_args(t["q"], t["k"], t["pv"], t["v"], LC.hw3(t["out"]), LC.hw2(t["norms"]), N, ksz, path=p)[1]
+
+    dense = {o: LC.CANONICAL for o in shapes}
+    for ce in (False, True):
+        ins, outs = (LC.COS_CE_INPUTS, LC.COS_CE_OUTPUTS) if ce else (LC.COS_INPUTS, LC.COS_OUTPUTS)
+        vector = LC.COS_INPUTS + (("dlogits",) if ce else ())          # the operands read / written in 16-byte chunks
+        for p in ("auto", "fused"):
+            assert select(dense, p, ce)[1] == _lib.XNA_HEAD_FUSED
+            for label, plan in LC.launch_plans(ins, outs, expandable=("k", "pv", "v") + (("target",) if ce else ()), head_expandable=("k", "pv", "v")):
+                assert select(dict(dense, **plan), p, ce)[1] == _lib.XNA_HEAD_FUSED, label
+            for fam in LC.FAMILIES:
+                for o in vector:
+                    t, sel = select(dict(dense, **{o: fam}), p, ce)
+                    ok = LC.cos_admits(t["q"], t["k"], t["pv"], t["v"], LC.hw3(t["dlogits"]) if ce else None)
+                    assert ok == (fam not in LC.ROUTING_FAMILIES), (fam, o)
+                    assert sel == (_lib.XNA_HEAD_FUSED if ok else UNSUPPORTED), (fam, o, p, sel)
+            for fam in LC.ROUTING_FAMILIES:                            # element by element: still the fused kernel's
+                for o in tuple(ins[4:]) + tuple(x for x in outs if x != "dlogits"):
+                    assert select(dict(dense, **{o: fam}), p, ce)[1] == _lib.XNA_HEAD_FUSED, (fam, o, p)
+            # rows too short for what is stored in them: arguments no kernel could serve
+            t, _ = select(dense, p, ce)
+            out, g = LC.hw3(t["out"]), LC.hw3(t["dlogits"])
+            short = out.as_strided(out.shape, (out.stride(0), out.stride(1), N - 1, 1), out.storage_offset())
+            gshort = g.as_strided(g.shape, (g.stride(0), g.stride(1), g.shape[3] - 8, 1), g.storage_offset())
+            if ce:
+                args = (LC.hw2(t["target"]), LC.hw2(t["loss"]), LC.hw2(t["labels"]))
+                assert LC.cos_ce_args(t["q"], t["k"], t["pv"], t["v"], short, None, N, ksz, *args, g, LC.hw2(t["dscale"]), path=p)[1] == INVALID
+                assert LC.cos_ce_args(t["q"], t["k"], t["pv"], t["v"], out, None, N, ksz, *args, gshort, LC.hw2(t["dscale"]), path=p)[1] == INVALID
+            else:
+                assert LC.cos_args(t["q"], t["k"], t["pv"], t["v"], short, None, N, ksz, path=p)[1] == INVALID
+
+
+@functools.lru_cache(maxsize=None)
+def _cos_reference(gname):
+    """Inputs of a cosine geometry, their fp64 reference and its bound: once, shared, never modified."""
+    B, heads, Dv, lr, cell, ks, N = LC.COS_GEOMS[gname]
+    q, k, v, E = LC.cos_inputs(gname)
+    r = CR.reference(q, k, v, E, ks, heads)
+    return (q, k, v, E), r, CR.bound(r)
+
+
+@pytest.mark.parametrize("gname", list(LC.COS_GEOMS))
+def test_cos_inputs_show_a_misplaced_read(gname):
+    """Teeth of the inputs test_gpu_layout_contract.py runs the cosine entries on: a kernel that read v_lr (or k_lr) from another image,
+    head, channel group, row or column would compute the definition on other inputs.  The fp64 reference of each such misread leaves
+    TWICE the derived bound of the true reference at every pixel (for at least one embedding) and at no less than 0.9 of all elements,
+    so no such misread can hide inside the bound the canonical launch is held to.  The per-channel offsets of the values do that."""
+    B, heads, Dv, (h, w), cell, ks, N = LC.COS_GEOMS[gname]
+    (q, k, v, E), r, bnd = _cos_reference(gname)
+    v5 = v.view(B, heads, Dv, h, w)
+    misreads = {"v of the other image": (k, v.flip(0)), "v of the next head": (k, v5.roll(-1, 1).reshape(v.shape)),
+                "v shifted by 8 channels inside a head": (k, v5.roll(-8, 2).reshape(v.shape)), "v shifted by one low-res row": (k, v.roll(-1, 2)),
+                "v shifted by one low-res column": (k, v.roll(-1, 3)), "k of the other image": (k.flip(0), v)}
+    assert float(r["norms"].min()) > 1.0
+    for what, (km, vm) in misreads.items():
+        off = (CR.reference(q, km, vm, E, ks, heads)["cos"] - r["cos"]).abs() > 2.0 * bnd
+        px, el = float(off.any(dim=1).double().mean()), float(off.double().mean())
+        print(f"{gname}: {what}: leaves twice the bound at {px:.3f} of the pixels, {el:.3f} of the elements")
+        assert px == 1.0 and el >= 0.9, (gname, what, px, el)
+
+
 def test_mse_supported_table(lib):
     B, heads, Dv, lr, out_sz, ks, kind = R.CASES[LC.MSE_CASE][:7]
     assert B == LC.B2
@@ -344,6 +430,42 @@ def test_a_reader_that_derives_the_row_stride_is_reported(family):
     assert LC.same_bits(got, x) == (not visible)
     if family in ("row_gap", "crop"):
         assert not bool(torch.isfinite(got.float()).all())
+
+
+def _norms_writer(view, arena, values, strides):
+    """The cosine kernel's store of the norm map emulated on the arena: pixel (b, y, x) of the [B, 1, H, W, 1] view goes to
+    start + b * s_b + y * s_y + x * s_x for ``strides`` = {b, y, x} (a correct kernel: the norm map's own)."""
+    B, _, H, W, _ = view.shape
+    sb, sy, sx = strides
+    start = view.storage_offset()
+    for b in range(B):
+        for y in range(H):
+            for x in range(W):
+                arena[start + b * sb + y * sy + x * sx] = values[b, y, x]
+
+
+@pytest.mark.parametrize("family", LC.VECTOR_FAMILIES)
+def test_a_norms_writer_that_takes_its_strides_from_out_is_reported(family):
+    """norms [B, Ho, Wo] addressed by `out`'s {b, y, x} strides (out is [B, Ho, Wo, N]; in pixels, i.e. divided by N, which is what the
+    norm map's strides ARE whenever both are dense, so no test on dense buffers sees it).  Where the two operands' gaps differ the
+    writer leaves the view: ``untouched`` says so, and the view keeps sentinels where nothing was stored."""
+    B, H, W, N = 2, 3, 14, 21
+    x = _dense((B, H, W), torch.float32)
+    out = LC.arena_for((B, 1, H, W, N), torch.float32, family, mask=False)[0]
+    os_ = tuple(int(s) // N for s in LC.hw3(out).stride()[:3])
+    view, arena, mask = LC.arena_for((B, 1, H, W, 1), torch.float32, family)
+    own = tuple(int(s) for s in LC.hw2(view).stride())
+    before = arena.clone()
+    _norms_writer(view, arena, x, own)
+    assert LC.same_bits(LC.hw2(view), x) and LC.untouched(arena, before, mask)
+    view2, arena2, mask2 = LC.arena_for((B, 1, H, W, 1), torch.float32, family)
+    _norms_writer(view2, arena2, x, os_)
+    visible = family in ("pixel_gap", "row_gap", "crop")
+    assert (os_ != own) == visible
+    assert LC.untouched(arena2, before, mask2) == (not visible)
+    assert LC.same_bits(LC.hw2(view2), x) == (not visible)
+    if visible:
+        assert LC.outside_writes(arena2, before, mask2) >= H and not bool(torch.isfinite(LC.hw2(view2)).all())
 
 
 # ---- 4. ops.xna_forward(out=...) ---------------------------------------------------------------------------------------------------
