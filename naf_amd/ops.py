@@ -185,15 +185,17 @@ def _fill_stem_conv0(image, weight, bias, y, stats_out) -> StemConv0Args:
 
 
 def stem_conv0(image: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, y: Optional[torch.Tensor],
-               stats_out: torch.Tensor) -> None:
+               stats_out: torch.Tensor, exact: bool = False) -> None:
     """Conv2d(3 -> 128, k in {1, 3}, reflect) + bias.  image [B,3,H,W] f32/bf16 (any strides); weight f32
     [128,3,k,k]; y: bf16 [B,H,W,128] view (128 channels contiguous) or None (statistics only);
-    stats_out: ``new_stats(B, device)`` (f64 [STATS_SLOTS,B,8,2], zeroed)."""
+    stats_out: ``new_stats(B, device)`` (f64 [STATS_SLOTS,B,8,2], zeroed).  ``exact=True`` sets ``NAF_CONV0_EXACT``: the 3x3
+    kernel of the default width then sums all six terms of the bf16 split (exact fp32 products) instead of three."""
     _gpu(image, "image")
     lib = _lib.load()
     if image.dtype not in _DT:
         image = image.float()
     a = _fill_stem_conv0(image, weight, bias, y, stats_out)
+    a.flags = _lib.CONV0_EXACT if exact else 0
     with torch.cuda.device(image.device), _Timed("stem_conv0"):
         rc = lib.naf_stem_conv0_fwd(C.byref(a), _stream(image))
     _lib.check(rc, "naf_stem_conv0_fwd")
