@@ -376,7 +376,17 @@ int naf_rope_tables(float* tab_y, float* tab_x, const float* periods, int32_t n_
  *   q      device bf16, logical [B, heads, Ho, Wo, Dh], strides q_stride = {b, head, y, x}, Dh contiguous
  *   k_lr   device bf16, logical [B, heads, h, w, Dh],   strides k_stride = {b, head, y, x}, Dh contiguous
  * Dh = Cq / heads, Dh % 4 == 0.  Pool window of low-res row i: [floor(i*Ho/h), ceil((i+1)*Ho/h)).
- * q may be NULL: keys only (the queries are then rotated on load by naf_xna_fwd, see rope_tab_y there). */
+ * q may be NULL: keys only (the queries are then rotated on load by naf_xna_fwd, see rope_tab_y there).
+ * Layouts.  Any strides of x, q and k_lr are honoured, each operand's on its own.  The VECTOR path (8 channels per 16-byte
+ * access) serves a call when ALL of these hold:
+ *   - Dh is a multiple of 32;
+ *   - x, q (where it is not NULL), tab_y and tab_x are 16-byte aligned;
+ *   - the four strides of q are multiples of 8 elements;
+ *   - where the channels of x are contiguous (x_stride[1] == 1), its strides {b, y, x} are multiples of 16 bytes (8 bf16 or 4
+ *     float elements); with any other channel stride x is loaded element by element inside the vector path.
+ * Every other call is served element by element: the same queries bit for bit, the keys up to the order of their fp32 sums, slower
+ * (and refused with NAF_ERR_UNSUPPORTED when Cq / 2 exceeds 256, the pair-chunks a pixel has threads for).  k_lr is stored element
+ * by element on both paths: no alignment. */
 typedef struct naf_rope_pool_args {
     const void* x;
     void* q;

@@ -358,6 +358,8 @@ int naf_launch_rope_pool(const naf_rope_pool_args* a, hipStream_t s) {
     const size_t esz = a->x_dtype == NAF_BF16 ? 2 : 4;
     bool vec = (p.Dh % 32 == 0);
     vec = vec && (reinterpret_cast<uintptr_t>(a->q) % 16 == 0) && (reinterpret_cast<uintptr_t>(a->x) % 16 == 0);
+    // the vector path reads its cos / sin in 16-byte pieces (Dh / 4 is a multiple of 8 floats, so only the bases matter)
+    vec = vec && (reinterpret_cast<uintptr_t>(a->tab_y) % 16 == 0) && (reinterpret_cast<uintptr_t>(a->tab_x) % 16 == 0);
     for (int i = 0; i < 4; ++i) vec = vec && (a->q == nullptr || a->q_stride[i] % 8 == 0);
     if (a->x_stride[1] == 1) {
         vec = vec && (a->x_stride[0] * esz % 16 == 0) && (a->x_stride[2] * esz % 16 == 0) && (a->x_stride[3] * esz % 16 == 0);

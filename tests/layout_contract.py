@@ -31,6 +31,8 @@ Families (D contiguous in all; C = heads * D):
   expanded_head memory [B, H, W, D], head stride 0: the `dout` that naf_xna_head_ce_fwd's dlogits is (read-only, heads equal)
   odd_offset    head-major, pointer + 4 elements            } not vectorisable (16-bit types): the routing tests only
   odd_stride    channels-last with x stride C + 4           }
+``planar`` places a [B, C, H, W] operand whose channel stride is free (the guidance of naf_rope_pool_fwd) in NCHW memory with a row gap and a
+plane gap.
 """
 import ctypes as C
 
@@ -147,6 +149,27 @@ def embed(dense5, family, fill=None, device=None):
     else:
         view.copy_(src)
     return view, arena, mask
+
+
+def planar(dense4, row_gap=3, plane_gap=40, device=None):
+    """A logical [B, C, H, W] tensor in PLANAR (NCHW) memory with x contiguous, rows ``row_gap`` and planes ``plane_gap`` elements apart:
+    (view, arena, inside_mask), sentinels in the gaps and in a margin of two rows + 16 elements on both sides.  For the operands whose
+    channel stride is free (the guidance of naf_rope_pool_fwd)."""
+    device = dense4.device if device is None else device
+    B, Cc, H, W = dense4.shape
+    sy = W + row_gap
+    sc = H * sy + plane_gap
+    sb = Cc * sc
+    lead = 2 * sy + 16
+    it = dense4.element_size()
+    while lead % max(32 // it, 1):
+        lead += 1
+    total = lead + B * sb + 2 * sy + 16
+    arena = torch.empty(total, dtype=dense4.dtype, device=device)
+    bits(arena).fill_(_SENTINEL[it])
+    view = arena.as_strided((B, Cc, H, W), (sb, sc, sy, 1), lead)
+    view.copy_(dense4.to(device))
+    return view, arena, view_mask(total, lead, (B, Cc, H, W), (sb, sc, sy), device)
 
 
 def banded(shape, dtype, device="cpu", inside=None, band=512):
