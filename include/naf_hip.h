@@ -1422,6 +1422,67 @@ typedef struct naf_xna_cos_ce_args {
 int naf_xna_cos_ce_select(const naf_xna_cos_ce_args* a);
 int naf_xna_cos_ce_fwd(const naf_xna_cos_ce_args* a, naf_stream_t stream);
 
+/* ---- mask pooling: the attention summed under K masks (added after the cosine entries; detect by symbol) ------------
+ * Masked average pooling of the upsampled features -- region embeddings for mask proposals, prototypes for few-shot segmentation --
+ * is linear in the values, and the attention's weights depend on the guidance only:
+ *     pooled[b, k, c] = sum_px M[b, k, px] * sum_j P_g(c)[px, j] * V[b, c, j] = sum_j A[b, g(c), k, j] * V[b, c, j]
+ *     A[b, g, k, j]   = sum_px M[b, k, px] * P_g[px, j]
+ * naf_xna_maskpool_fwd computes A on the low-res grid and mass[b, k] = sum_px M[b, k, px] without reading V; naf_maskpool_apply is the
+ * small contraction that follows.  The [B, C, Ho, Wo] tensor is never written.
+ *   q, k_lr   exactly as in naf_xna_head_args (bf16, strides {b, head, y, x}, last dim contiguous, Dq = 64), rope_tab_* as there
+ *   masks     device [B, K, Ho, Wo] of mask_dtype: NAF_MASK_BF16 (soft masks) or NAF_MASK_U8 (bytes: bool / uint8, read as their
+ *             integer value); element strides m_stride = {b, k, y, x} with x stride 1.  Cells a multiple of 8 pixels wide are read
+ *             with vector loads: the pointer must be 16-byte aligned and the b, k and y strides multiples of 8 elements
+ *             (-NAF_ERR_UNSUPPORTED otherwise: the caller copies); other cells (14, 15, 30 ... pixels) are read element by element
+ *   A         device float [B, heads, K, h, w] dense
+ *   mass      device float [B, K] dense
+ *   workspace device, naf_xna_maskpool_workspace_bytes(a) bytes, 16-byte aligned: per-cell partials
+ *             [B][h*w][heads][NSLOT][Kpad] fp32 (NSLOT = ky*kx, Kpad = K rounded up to 16) and per-cell masses [B][h*w][Kpad]
+ * Kernels (xna_pool_kernel.h): one workgroup per (batch, low-res cell) loops over the heads; scores and softmax are
+ * naf_xna_head_fwd's instruction for instruction, so the bf16 P is bit for bit that kernel's; P goes through LDS transposed and
+ * A_cell[slot, k] = sum_px P[px, slot] * M[k, px] runs on the matrix cores with the mask rows as operand fragments straight from
+ * memory.  A gather kernel then sums, for every key j, the partials of the cells whose clamped window holds j in ascending cell
+ * order.  No float atomics anywhere: two launches on the same inputs give the same bits.
+ * Served: what naf_xna_head_fwd serves (square odd window 3 .. 15, Dq = 64, integer ratio whose cell rows are row tiles, h, w >= window),
+ * 1 <= K <= 64 per launch (the caller chunks).  naf_xna_maskpool_select answers as naf_xna_head_select does: NAF_XNA_HEAD_FUSED,
+ * -NAF_ERR_INVALID for arguments no kernel could serve, -NAF_ERR_UNSUPPORTED (with naf_last_error) for a valid request outside the list.
+ * A pure host-side query.  Caller-owned memory and stream; capturable.  The struct must be zero-initialised (reserved fields). */
+enum naf_mask_dtype {
+    NAF_MASK_BF16 = 0,
+    NAF_MASK_U8 = 1
+};
+typedef struct naf_xna_maskpool_args {
+    const void* q;
+    const void* k_lr;
+    const void* masks;
+    float* A;
+    float* mass;
+    void* workspace;
+    size_t workspace_bytes;
+    const float* rope_tab_y;
+    const float* rope_tab_x;
+    int32_t B, heads, Ho, Wo, h, w, Dq, K, ky, kx;
+    int32_t mask_dtype; /* naf_mask_dtype */
+    int32_t path;       /* naf_xna_head_path */
+    float scale;
+    int32_t reserved;
+    int64_t q_stride[4];
+    int64_t k_stride[4];
+    int64_t m_stride[4];
+} naf_xna_maskpool_args;
+int naf_xna_maskpool_select(const naf_xna_maskpool_args* a);
+size_t naf_xna_maskpool_workspace_bytes(const naf_xna_maskpool_args* a);
+int naf_xna_maskpool_fwd(const naf_xna_maskpool_args* a, naf_stream_t stream);
+
+/* pooled[b, k, c] = sum_j A[b, c / (C / heads), k, j] * v[b, c, j]  (fp32 products and sums, one wave per output in a fixed order),
+ * divided by mass[b, k] when `mean` is non-zero; a mask of zero mass gives a row of exact zeros.
+ *   A      device float [B, heads, K, h*w] dense (naf_xna_maskpool_fwd's)
+ *   v      device bf16 [B, C, h*w], element strides v_stride = {b, c} with the grid contiguous (a dense [B, C, h, w] feature map)
+ *   mass   device float [B, K] dense (read only when mean != 0; may be NULL otherwise)
+ *   pooled device float [B, K, C] dense */
+int naf_maskpool_apply(const float* A, const void* v, const float* mass, float* pooled, int32_t B, int32_t heads, int32_t K, int32_t C,
+                       int32_t hw, const int64_t* v_stride, int32_t mean, naf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

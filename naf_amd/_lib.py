@@ -96,6 +96,21 @@ class XnaCosCEArgs(C.Structure):
     ]
 
 
+MASK_BF16, MASK_U8 = 0, 1     # naf_mask_dtype
+
+
+class XnaMaskPoolArgs(C.Structure):
+    """naf_xna_maskpool_args (added after the cosine entries, detected by symbol): the attention summed under K masks."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k_lr", C.c_void_p), ("masks", C.c_void_p), ("A", C.c_void_p), ("mass", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("rope_tab_y", C.c_void_p), ("rope_tab_x", C.c_void_p),
+        ("B", C.c_int32), ("heads", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("Dq", C.c_int32), ("K", C.c_int32), ("ky", C.c_int32), ("kx", C.c_int32),
+        ("mask_dtype", C.c_int32), ("path", C.c_int32), ("scale", C.c_float), ("reserved", C.c_int32),
+        ("q_stride", I64x4), ("k_stride", I64x4), ("m_stride", I64x4),
+    ]
+
+
 class XnaMSEArgs(C.Structure):
     """naf_xna_mse_args (added after the PCA entries, detected by symbol): naf_xna_args plus the regression target of the training objective."""
     _fields_ = [
@@ -398,6 +413,11 @@ SIGNATURES = {
     "naf_xna_cos_fwd": (C.c_int, [C.POINTER(XnaCosArgs), C.c_void_p]),
     "naf_xna_cos_ce_select": (C.c_int, [C.POINTER(XnaCosCEArgs)]),
     "naf_xna_cos_ce_fwd": (C.c_int, [C.POINTER(XnaCosCEArgs), C.c_void_p]),
+    "naf_xna_maskpool_select": (C.c_int, [C.POINTER(XnaMaskPoolArgs)]),
+    "naf_xna_maskpool_workspace_bytes": (C.c_size_t, [C.POINTER(XnaMaskPoolArgs)]),
+    "naf_xna_maskpool_fwd": (C.c_int, [C.POINTER(XnaMaskPoolArgs), C.c_void_p]),
+    "naf_maskpool_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.POINTER(C.c_int64), C.c_int32, C.c_void_p]),
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
     "naf_propagate_plan": (C.c_int, [C.POINTER(PropagateArgs), C.POINTER(C.c_int32)]),

@@ -45,6 +45,7 @@ INSTANCES = {
     "xna_union_mse_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_head_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_cos_inst.hip": [(k, None) for k in _WINDOWS],
+    "xna_pool_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_bwd_inst.hip": [(k, None) for k in _WINDOWS],
 }
 

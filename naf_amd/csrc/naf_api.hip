@@ -558,6 +558,51 @@ int naf_xna_cos_ce_fwd(const naf_xna_cos_ce_args* a, naf_stream_t stream) {
     return naf_launch_xna_cos_ce(a, xna_scale(a->cos.scale, a->cos.Dq), static_cast<hipStream_t>(stream));
 }
 
+// ---- mask pooling: the attention summed under K masks (after the cosine entries) ----
+static int xna_maskpool_validate(const naf_xna_maskpool_args* a) {
+    const char* who = "naf_xna_maskpool_fwd";
+    NAF_REQUIRE(a != nullptr, "%s: args is NULL", who);
+    NAF_REQUIRE(a->q && a->k_lr && a->masks && a->A && a->mass && a->workspace, "%s: NULL tensor pointer", who);
+    const int rc = xna_geometry_validate(who, a, 1);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(a->K >= 1, "%s: K must be at least 1, got %d", who, a->K);
+    NAF_REQUIRE(a->mask_dtype == NAF_MASK_BF16 || a->mask_dtype == NAF_MASK_U8, "%s: mask_dtype %d", who, a->mask_dtype);
+    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "%s: path %d", who, a->path);
+    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "%s: rope_tab_y and rope_tab_x must be given together", who);
+    NAF_REQUIRE(a->reserved == 0, "%s: reserved field must be zero", who);
+    return NAF_OK;
+}
+
+int naf_xna_maskpool_select(const naf_xna_maskpool_args* a) {
+    int rc = xna_maskpool_validate(a);
+    if (rc == NAF_OK) rc = naf_xna_maskpool_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
+}
+
+size_t naf_xna_maskpool_workspace_bytes(const naf_xna_maskpool_args* a) {
+    if (a == nullptr || a->B <= 0 || a->heads <= 0 || a->h <= 0 || a->w <= 0 || a->K <= 0 || a->ky <= 0 || a->kx <= 0) return 0;
+    return naf_xna_maskpool_ws(a, nullptr);
+}
+
+int naf_xna_maskpool_fwd(const naf_xna_maskpool_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_maskpool_select(a);
+    if (sel < 0) return -sel;
+    NAF_REQUIRE(a->workspace_bytes >= naf_xna_maskpool_ws(a, nullptr), "naf_xna_maskpool_fwd: workspace of %zu bytes, %zu needed", a->workspace_bytes,
+                naf_xna_maskpool_ws(a, nullptr));
+    NAF_REQUIRE(naf_aligned(a->workspace, 16), "naf_xna_maskpool_fwd: workspace must be 16-byte aligned");
+    return naf_launch_xna_maskpool(a, xna_scale(a->scale, a->Dq), static_cast<hipStream_t>(stream));
+}
+
+int naf_maskpool_apply(const float* A, const void* v, const float* mass, float* pooled, int32_t B, int32_t heads, int32_t K, int32_t C, int32_t hw,
+                       const int64_t* v_stride, int32_t mean, naf_stream_t stream) {
+    const char* who = "naf_maskpool_apply";
+    NAF_REQUIRE(A && v && pooled && v_stride && (mass || !mean), "%s: NULL pointer", who);
+    NAF_REQUIRE(B > 0 && heads > 0 && K > 0 && C > 0 && hw > 0, "%s: non-positive size", who);
+    NAF_REQUIRE(C % heads == 0, "%s: %d channels not divisible by %d heads", who, C, heads);
+    NAF_REQUIRE((int64_t)B * K * C <= 0x7fffffffLL, "%s: %lld outputs out of range", who, (long long)B * K * C);
+    return naf_launch_maskpool_apply(A, v, mass, pooled, B, heads, K, C, hw, v_stride, mean, static_cast<hipStream_t>(stream));
+}
+
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_bwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->dout && a->dq && a->dk_lr && a->dv_lr, "naf_xna_bwd: NULL tensor pointer");

@@ -83,7 +83,12 @@ int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s);  
 int naf_xna_cos_eligible(const naf_xna_cos_args* a);                              // xna_cos.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
 int naf_launch_xna_cos_ce(const naf_xna_cos_ce_args* a, float scale, hipStream_t s);   // xna_cos.hip: ... with the classification epilogue
 int naf_xna_cos_ce_eligible(const naf_xna_cos_ce_args* a);                            // xna_cos.hip: naf_xna_cos_eligible plus the dlogits layout
-int naf_tile_span(int L_out, int L_in, int k);                                   // xna_rows.hip: low-res columns under 16 consecutive queries
+int naf_launch_xna_maskpool(const naf_xna_maskpool_args* a, float scale, hipStream_t s);   // xna_pool.hip: mask pooling (cell kernel, gather, mass)
+int naf_xna_maskpool_eligible(const naf_xna_maskpool_args* a);                          // xna_pool.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
+size_t naf_xna_maskpool_ws(const naf_xna_maskpool_args* a, size_t* mass_offset);        // xna_pool.hip: workspace bytes, offset of the per-cell masses
+int naf_launch_maskpool_apply(const float* A, const void* v, const float* mass, float* pooled, int B, int heads, int K, int C, int hw,
+                              const int64_t* v_stride, int mean, hipStream_t s);        // xna_pool.hip
+int naf_tile_span(int L_out, int L_in, int k);                                  // xna_rows.hip: low-res columns under 16 consecutive queries
 // `sg` (0.4.3): the gradient of the scores (naf_xna_bwd_scores); nullptr = the plain backward, the same launches as before
 int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, const naf_xna_bwd_scores_args* sg = nullptr);   // xna_bwd.hip
 int naf_xna_bwd_eligible(const naf_xna_bwd_args* a);                             // xna_bwd.hip

@@ -1093,7 +1093,8 @@ class NAF(nn.Module):
 
     def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
                 reduction="mean", predict=False, confusion=None, regress=None, regress_path="auto", cosine=False, logit_scale=1.0,
-                return_norms=False, cosine_path="auto", loss=None, **kwargs):
+                return_norms=False, cosine_path="auto", loss=None, masks=None, mask_reduce="mean", mask_path="auto",
+                return_attention=False, **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -1199,7 +1200,34 @@ class NAF(nn.Module):
         gradient).  ``"fused"`` insists (NafHipError with the reason); ``"composed"`` is the A/B arm.  ``image`` may be a ``Guidance``.
         ValueError, before any device work: ``loss`` other than None / "ce"; ``loss`` without ``cosine=True``, without ``target``, with
         ``return_norms`` or with ``confusion``; a float ``logit_scale <= 0`` with ``predict``.  Not offered: a gradient for the upsampler
-        through the fused route, class weights, label smoothing, soft targets, fp16 / fp32 features on the fused route."""
+        through the fused route, class weights, label smoothing, soft targets, fp16 / fp32 features on the fused route.
+
+        ``masks``, ``mask_reduce``, ``mask_path``, ``return_attention`` (keyword only): MASKED AVERAGE POOLING -- region embeddings for mask
+        proposals, prototypes for few-shot and reference-guided segmentation ("scribble a mask, see what looks like it":
+        ``E = naf(image, feats, size, masks=M)``, then ``naf(image, feats, size, head=E[b], cosine=True)``).  ``masks`` is [B, K, Ho, Wo], dtype
+        bool, uint8, bfloat16, float16 or float32, on the features' device, without a gradient; the call returns fp32 [B, K, C]:
+            ``einsum("bkhw,bchw->bkc", masks.float(), naf(image, features, size).float())``
+        divided by ``mass[b, k] = masks[b, k].sum()`` for ``mask_reduce="mean"``, undivided for ``"sum"``.  A mask of zero mass gives a row of
+        exact zeros, never NaN (the convention of the cosine head for a zero feature).  ``return_attention=True`` returns ``(pooled, A,
+        mass)`` with ``A`` fp32 [B, heads, K, h, w], the attention summed under each mask on the low-res grid, and ``mass`` fp32 [B, K].
+        ``mask_path="auto"`` takes ``A`` and ``mass`` from the mask-pooling kernel (``ops.xna_mask_pool``: it never reads the features, and the
+        [B, C, Ho, Wo] tensor and its fp32 copy never exist) and contracts them with the features on the low-res grid
+        (``ops.mask_pool_apply``) where ``naf_xna_maskpool_select`` grants the geometry (those of ``head=``) and the features are bf16;
+        everything else is the expression above in torch ops on the plain forward: non-integer ratios, ratio 1, fp16 / fp32 features, or a
+        call that wants a gradient for the upsampler or the features (``forward_train``).  ``"fused"`` insists (NafHipError with the
+        library's reason); ``"composed"`` is the A/B arm.  float16 / float32 masks are rounded once to bfloat16 on the fused route; more than
+        64 masks run in chunks of 64.  ``image`` may be a ``Guidance``.  ValueError, before any device work: ``masks`` together with ``head``,
+        ``target``, ``predict``, ``confusion``, ``regress``, ``return_weights`` or ``cosine``; a wrong shape or device; ``mask_reduce`` outside
+        the two values.  Not offered: integer label maps (pass ``labels[:, None] == torch.arange(K, device=labels.device)[None, :, None, None]``),
+        a gradient through the fused route, ``capture()`` of this call."""
+        if masks is not None:
+            if (head is not None or target is not None or predict or (confusion is not None and confusion is not False) or regress is not None
+                    or return_weights or cosine or loss is not None):
+                raise ValueError("naf(..., masks=...) pools the features themselves: it does not combine with head / target / predict / confusion / "
+                                 "regress / return_weights / cosine")
+            return self._forward_masks(image, features, output_size, masks, mask_reduce, mask_path, bool(return_attention))
+        if return_attention:
+            raise ValueError("naf(..., return_attention=True) goes with masks=...")
         if loss is not None:
             if loss != "ce":
                 raise ValueError(f"loss must be None or 'ce', got {loss!r}")
@@ -1233,6 +1261,64 @@ class NAF(nn.Module):
             return self.forward_train(image, features, output_size, amp="auto", return_weights=return_weights)
         with torch.no_grad():
             return self._forward_inference(image, features, output_size, return_weights)
+
+    def _forward_masks(self, image, features, output_size, masks, reduce, path, return_attention):
+        """``forward(..., masks=M)``: see ``forward``.  Every refusal comes before anything touches the device.  On the composed route
+        ``A`` of ``return_attention`` comes from the materialised scores (``return_weights=True``, ``ops.mask_attention_from_scores``),
+        without a gradient."""
+        if reduce not in ops._MASK_REDUCE:
+            raise ValueError(f"mask_reduce must be one of {ops._MASK_REDUCE}, got {reduce!r}")
+        if path not in ops._HEAD_PATHS:
+            raise ValueError(f"mask_path must be one of {ops._HEAD_PATHS}, got {path!r}")
+        if not isinstance(features, torch.Tensor) or features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(getattr(features, 'shape', ()))}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, C = features.shape[0], features.shape[1]
+        ops.check_masks("naf(..., masks=...)", masks, (B, None, ho, wo), features.device)
+        if not (image.is_cuda and features.is_cuda):
+            raise _rocm_only(image=image, features=features)
+        if isinstance(image, Guidance):
+            self._check_guidance_call(image, features, False, None, None)
+        K = int(masks.shape[1])
+        heads, ksz, enc = self.upsampler.num_heads, self.upsampler.kernel_size, self.image_encoder
+        lr = features.shape[-2:]
+        reason = None       # why the fused kernel does not take the call
+        if B == 0:
+            reason = "an empty batch"
+        elif self._wants_grad(image, features):
+            reason = "the fused mask-pooling kernel is inference-only and the call wants a gradient for the upsampler or its inputs"
+        elif features.dtype != torch.bfloat16:
+            reason = f"the fused mask-pooling route reads bfloat16 features, got {features.dtype}"
+        elif C % heads or enc.out_channels % heads:
+            reason = f"feature channels {C} / guidance channels {enc.out_channels} not divisible by {heads} heads"
+        else:
+            probe = torch.empty((B, ho, wo, heads, enc.out_channels // heads), dtype=torch.bfloat16, device="meta").permute(0, 3, 1, 2, 4)
+            if ops.xna_mask_pool_select(probe, lr, min(K, ops.MASK_POOL_CHUNK), ksz) != "fused":
+                reason = _lib_last_error() or "naf_xna_maskpool_select refuses the geometry"
+        if path == "fused" and reason is not None:
+            raise ops._lib.NafHipError(f"naf(..., masks=..., mask_path='fused'): {reason}")
+        if path == "composed" or reason is not None:
+            with ops._Timed("mask_pool_composed"):
+                A = None
+                if B == 0:
+                    f = torch.empty((0, C, ho, wo), dtype=features.dtype, device=features.device)
+                    A = torch.empty((0, heads, K, *lr), dtype=torch.float32, device=features.device)
+                elif return_attention:
+                    f, scores = self.forward(image, features, output_size, return_weights=True)
+                    with torch.no_grad():
+                        A = ops.mask_attention_from_scores(scores, masks, lr, ksz)
+                else:
+                    f = self.forward(image, features, output_size)
+                pooled, mass = ops.mask_pool_from_features(f, masks, reduce, return_mass=True)
+            return (pooled, A, mass) if return_attention else pooled
+        with torch.no_grad():
+            kc = min(K, ops.MASK_POOL_CHUNK)
+            fusable = lambda q5, tabs: ops.xna_mask_pool_select(q5, lr, kc, ksz, rope_tables=tabs) == "fused"
+            q5, k5, tabs = self.guidance_qk(image, lr, (ho, wo), fusable=fusable)
+            with ops._Timed("attention"):
+                A, mass = ops.xna_mask_pool(q5, k5, masks, ksz, scale=self.upsampler.scale, rope_tables=tabs)
+                pooled = ops.mask_pool_apply(A, features, mass, reduce)
+        return (pooled, A, mass) if return_attention else pooled
 
     def _wants_grad(self, *inputs) -> bool:
         """This call wants a gradient for the upsampler or its ``inputs`` (image or ``Guidance``, features): gradient mode with an input

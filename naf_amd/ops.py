@@ -1311,6 +1311,195 @@ def xna_head_forward(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, b
         return o.to(out_dtype).contiguous().permute(0, 3, 1, 2)
 
 
+# ---- mask pooling: the attention summed under K masks (region embeddings, prototypes) --------------------------------------------
+MASK_POOL_CHUNK = 64          # masks per launch of naf_xna_maskpool_fwd
+_MASK_DTYPES = (torch.bool, torch.uint8, torch.bfloat16, torch.float16, torch.float32)
+_MASK_REDUCE = ("mean", "sum")
+
+
+def check_masks(who: str, masks, shape, device) -> None:
+    """What every mask-pooling entry asks of ``masks``: a [B, K, Ho, Wo] = ``shape`` tensor (K >= 1; ``shape[1]`` None: any K) of dtype bool, uint8,
+    bfloat16, float16 or float32 on ``device`` that carries no gradient.  TypeError / ValueError; nothing touches the device."""
+    if not isinstance(masks, torch.Tensor):
+        raise TypeError(f"{who}: masks must be a tensor, got {type(masks).__name__}")
+    if masks.dtype not in _MASK_DTYPES:
+        raise TypeError(f"{who}: masks must be bool, uint8, bfloat16, float16 or float32, got {masks.dtype}")
+    want = tuple(shape)
+    if masks.dim() != 4 or masks.shape[1] < 1 or any(s is not None and int(m) != int(s) for m, s in zip(masks.shape, want)):
+        raise ValueError(f"{who}: masks must be [B, K, Ho, Wo] = ({want[0]}, {'K >= 1' if want[1] is None else want[1]}, {want[2]}, {want[3]}), "
+                         f"got {tuple(masks.shape)}")
+    if masks.device != device:
+        raise ValueError(f"{who}: masks on {masks.device}, the features on {device}")
+    if masks.requires_grad:
+        raise ValueError(f"{who}: masks carry no gradient (detach them)")
+
+
+def _mask_operand(masks: torch.Tensor, dx: int) -> Tuple[torch.Tensor, int]:
+    """The tensor the kernel reads for ``masks`` and its naf_mask_dtype: bool / uint8 as bytes, bfloat16 as it is, float16 / float32 cast once
+    to bfloat16 (a rounding of the mask, documented); a copy where the kernel's vector loads (cells a multiple of 8 pixels wide) would
+    not be aligned."""
+    if masks.dtype == torch.bool:
+        m, dt = masks.view(torch.uint8), _lib.MASK_U8
+    elif masks.dtype == torch.uint8:
+        m, dt = masks, _lib.MASK_U8
+    else:
+        m, dt = masks.to(torch.bfloat16), _lib.MASK_BF16
+    if m.stride(3) != 1 or (dx % 8 == 0 and (m.data_ptr() % 16 or any(m.stride(i) % 8 for i in range(3)))):
+        m = m.contiguous()
+    return m, dt
+
+
+def xna_mask_pool_select(q: torch.Tensor, lr_size, n_masks: int, kernel_size, *, rope_tables=None) -> str:
+    """Which route mask pooling takes for these shapes: "fused" (``naf_xna_maskpool_select`` grants the kernel for ``n_masks`` masks per launch,
+    at most ``MASK_POOL_CHUNK``) or "composed" (the caller pools the plain forward).  ``q``: the 5-D [B, heads, Ho, Wo, Dq] bf16 queries --
+    with ``rope_tables`` the un-rotated guidance.  A host-side query: nothing is launched or read, CPU / meta tensors do.  Invalid
+    arguments raise ValueError; the library's reason for "composed" is in ``naf_last_error``."""
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1:
+        return "composed"
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    _, heads, Ho, Wo, Dq = q.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    a = _lib.XnaMaskPoolArgs()
+    a.q = a.k_lr = a.masks = a.A = a.mass = a.workspace = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    _fill_geometry(a, q, None, h, w, ky, kx, None)
+    a.K, a.path, a.mask_dtype = int(n_masks), _lib.XNA_HEAD_AUTO, _lib.MASK_BF16
+    a.k_stride = _dense5(h, w, heads, Dq)
+    a.m_stride = I64x4(int(n_masks) * Ho * Wo, Ho * Wo, Wo, 1)
+    sel = lib.naf_xna_maskpool_select(C.byref(a))
+    if sel == -1:
+        _lib.check(1, "naf_xna_maskpool_select")
+    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
+
+
+def xna_mask_pool(q: torch.Tensor, k_lr: torch.Tensor, masks: torch.Tensor, kernel_size, *, scale: Optional[float] = None, rope_tables=None):
+    """The attention of ``xna_forward`` summed under K masks, without values (``naf_xna_maskpool_fwd``):
+
+        ``A[b, g, k, j] = sum_px masks[b, k, px] * P_g[px, j]``  fp32 [B, heads, K, h, w],  ``mass[b, k] = masks[b, k].sum()``  fp32 [B, K]
+
+    with ``P_g`` the bf16-rounded softmax weights of head ``g`` -- bit for bit those of ``xna_head_forward``.  q [B, heads, Ho, Wo, Dq] bf16,
+    k_lr [B, heads, h, w, Dq] bf16 (5-D strided views, last dim contiguous), masks [B, K, Ho, Wo] bool / uint8 (read as bytes), bfloat16,
+    or float16 / float32 (cast once to bfloat16 on the host: a rounding of the mask).  K above ``MASK_POOL_CHUNK`` runs in chunks of at
+    most that many masks, concatenated.  No float atomics: two calls give the same bits.  Raises NafHipError where the kernel does not
+    serve the geometry (``xna_mask_pool_select``); there is no composed arm at this level.  ``rope_tables``: as in ``xna_forward``."""
+    who = "xna_mask_pool"
+    _check_operands(who, ((q, "q", _BF16), (k_lr, "k_lr", _BF16)))
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w = int(k_lr.shape[2]), int(k_lr.shape[3])
+    if tuple(k_lr.shape) != (B, heads, h, w, Dq):
+        raise ValueError(f"{who}: k_lr shape {tuple(k_lr.shape)} does not match q {tuple(q.shape)}")
+    check_masks(who, masks, (B, None, Ho, Wo), q.device)
+    lib = _lib.load()
+    dev = q.device
+    K = int(masks.shape[1])
+    A = torch.empty((B, heads, K, h, w), dtype=torch.float32, device=dev)
+    mass = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if B == 0:
+        return A, mass
+    rope_ptrs = None if rope_tables is None else _rope_table_ptrs(who, rope_tables, Ho, Wo, Dq)
+    ws = None
+    for k0 in range(0, K, MASK_POOL_CHUNK):
+        kc = min(MASK_POOL_CHUNK, K - k0)
+        m, mdt = _mask_operand(masks[:, k0:k0 + kc], Wo // w if w and Wo % w == 0 else 1)
+        whole = kc == K
+        Ac = A if whole else torch.empty((B, heads, kc, h, w), dtype=torch.float32, device=dev)
+        mc = mass if whole else torch.empty((B, kc), dtype=torch.float32, device=dev)
+        a = _lib.XnaMaskPoolArgs()
+        a.q, a.k_lr, a.masks, a.A, a.mass = q.data_ptr(), k_lr.data_ptr(), m.data_ptr(), Ac.data_ptr(), mc.data_ptr()
+        if rope_ptrs is not None:
+            a.rope_tab_y, a.rope_tab_x = rope_ptrs
+        _fill_geometry(a, q, k_lr, h, w, ky, kx, scale)
+        a.K, a.mask_dtype, a.path = kc, mdt, _lib.XNA_HEAD_FUSED
+        a.m_stride = _strides4(m, (0, 1, 2, 3))
+        need = int(lib.naf_xna_maskpool_workspace_bytes(C.byref(a)))
+        if ws is None or ws.numel() < need:
+            ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+        sel = lib.naf_xna_maskpool_select(C.byref(a))
+        if sel != _lib.XNA_HEAD_FUSED:
+            _lib.check(-sel, "naf_xna_maskpool_select")
+        with torch.cuda.device(dev), _Timed("xna_mask_pool"):
+            rc = lib.naf_xna_maskpool_fwd(C.byref(a), _stream(q))
+        _lib.check(rc, "naf_xna_maskpool_fwd")
+        if not whole:
+            A[:, :, k0:k0 + kc] = Ac
+            mass[:, k0:k0 + kc] = mc
+    return A, mass
+
+
+def mask_pool_apply(A: torch.Tensor, v_lr: torch.Tensor, mass: Optional[torch.Tensor], reduce: str = "mean") -> torch.Tensor:
+    """``pooled[b, k, c] = sum_j A[b, g(c), k, j] * v_lr[b, c, j]`` in fp32 (``naf_maskpool_apply``), divided by ``mass[b, k]`` for
+    ``reduce="mean"`` (a mask of zero mass: a row of exact zeros), undivided for ``"sum"``.  A fp32 [B, heads, K, h, w] dense and mass fp32
+    [B, K] from ``xna_mask_pool``, v_lr the bf16 feature map [B, C, h, w] (head g owns channels [g*C/heads, (g+1)*C/heads)).  Returns
+    fp32 [B, K, C]."""
+    who = "mask_pool_apply"
+    if reduce not in _MASK_REDUCE:
+        raise ValueError(f"{who}: reduce must be one of {_MASK_REDUCE}, got {reduce!r}")
+    for t, n in ((A, "A"), (v_lr, "v_lr")) + (((mass, "mass"),) if mass is not None else ()):
+        _gpu(t, n)
+    if A.dim() != 5 or A.dtype != torch.float32 or not A.is_contiguous():
+        raise ValueError(f"{who}: A must be a dense float32 [B, heads, K, h, w] tensor")
+    B, heads, K, h, w = A.shape
+    if v_lr.dim() != 4 or v_lr.dtype != torch.bfloat16 or v_lr.shape[0] != B or tuple(v_lr.shape[2:]) != (h, w) or v_lr.shape[1] % heads:
+        raise ValueError(f"{who}: v_lr must be bfloat16 [B, C, h, w] = ({B}, multiple of {heads}, {h}, {w}), got {tuple(v_lr.shape)} {v_lr.dtype}")
+    if reduce == "mean" and (mass is None or mass.dtype != torch.float32 or tuple(mass.shape) != (B, K) or not mass.is_contiguous()):
+        raise ValueError(f"{who}: reduce='mean' needs mass as a dense float32 [{B}, {K}] tensor")
+    if v_lr.stride(3) != 1 or v_lr.stride(2) != w:
+        v_lr = v_lr.contiguous()
+    Cc = int(v_lr.shape[1])
+    pooled = torch.empty((B, K, Cc), dtype=torch.float32, device=A.device)
+    if pooled.numel() == 0:
+        return pooled
+    lib = _lib.load()
+    vs = (C.c_int64 * 2)(int(v_lr.stride(0)), int(v_lr.stride(1)))
+    with torch.cuda.device(A.device), _Timed("mask_pool_apply"):
+        rc = lib.naf_maskpool_apply(A.data_ptr(), v_lr.data_ptr(), mass.data_ptr() if reduce == "mean" else None, pooled.data_ptr(),
+                                    B, heads, K, Cc, h * w, vs, 1 if reduce == "mean" else 0, _stream(A))
+    _lib.check(rc, "naf_maskpool_apply")
+    return pooled
+
+
+def mask_pool_from_features(f: torch.Tensor, masks: torch.Tensor, reduce: str = "mean", return_mass: bool = False):
+    """Mask pooling as torch ops on a materialised feature map [B, C, Ho, Wo] (any device, CPU included): the composed arm and the
+    definition -- ``einsum("bkhw,bchw->bkc", masks.float(), f.float())``, divided by ``mass = masks.float().sum((2, 3))`` for "mean"
+    with exact zeros where the mass is zero."""
+    if reduce not in _MASK_REDUCE:
+        raise ValueError(f"mask pooling: mask_reduce must be one of {_MASK_REDUCE}, got {reduce!r}")
+    m = masks.float()
+    pooled = torch.einsum("bkhw,bchw->bkc", m, f.float())
+    mass = m.sum(dim=(2, 3))
+    if reduce == "mean":
+        live = (mass != 0)[..., None]
+        pooled = torch.where(live, pooled / torch.where(live, mass[..., None], torch.ones_like(mass[..., None])), torch.zeros_like(pooled))
+    return (pooled, mass) if return_mass else pooled
+
+
+def mask_attention_from_scores(scores: torch.Tensor, masks: torch.Tensor, lr_size, kernel_size) -> torch.Tensor:
+    """``A[b, g, k, j] = sum_px masks[b, k, px] * softmax(scores)[b, g, px, slot of j]`` as torch ops (any device, CPU included), fp32
+    [B, heads, K, h, w]: what ``xna_mask_pool`` computes, from materialised scores [B, heads, Ho, Wo, ky*kx] (``return_weights=True``) and the
+    index tables -- any geometry, repeated keys included.  The composed arm of ``return_attention``; rows are processed in chunks so that
+    the dense [pixels, keys] weights of a chunk stay below 256 MiB."""
+    B, heads, Ho, Wo, kk = scores.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    ky, kx = _ksize(kernel_size)
+    dev = scores.device
+    iy, ix = axis_index_table(Ho, h, ky).to(dev).long(), axis_index_table(Wo, w, kx).to(dev).long()
+    K = masks.shape[1]
+    m = masks.float()
+    A = torch.zeros((B, heads, K, h * w), dtype=torch.float32, device=dev)
+    rows = max(1, min(Ho, (64 << 20) // max(1, B * heads * Wo * h * w)))
+    for r0 in range(0, Ho, rows):
+        r1 = min(r0 + rows, Ho)
+        key = (iy[r0:r1, None, :, None] * w + ix[None, :, None, :]).reshape(1, 1, (r1 - r0) * Wo, kk)
+        P = torch.softmax(scores[:, :, r0:r1].float(), dim=-1).reshape(B, heads, (r1 - r0) * Wo, kk)
+        dense = torch.zeros((B, heads, (r1 - r0) * Wo, h * w), dtype=torch.float32, device=dev).scatter_add_(3, key.expand_as(P), P)
+        A += torch.einsum("bkp,bgpj->bgkj", m[:, :, r0:r1].reshape(B, K, -1), dense)
+    return A.view(B, heads, K, h, w)
+
+
 # ---- ... and a cosine head: scaled cosines between the upsampled feature and N embeddings (open vocabulary, heat maps) -----------
 def normalize_embeddings(embeddings: torch.Tensor) -> torch.Tensor:
     """``F.normalize(E.float(), dim=1)`` (eps 1e-12) of an [N, C] or [N, C, 1, 1] embedding matrix: the rows the cosine head projects with."""
