@@ -1483,6 +1483,44 @@ int naf_xna_maskpool_fwd(const naf_xna_maskpool_args* a, naf_stream_t stream);
 int naf_maskpool_apply(const float* A, const void* v, const float* mass, float* pooled, int32_t B, int32_t heads, int32_t K, int32_t C,
                        int32_t hw, const int64_t* v_stride, int32_t mean, naf_stream_t stream);
 
+/* ---- peak search on the scaled cosines (added after the mask-pooling entries; detect by symbol) ------------
+ * "Where is the best match": with cos the [B, N, Ho, Wo] result of naf_xna_cos_fwd, an integer ratio dy = Ho / h, dx = Wo / w, and cell
+ * (cy, cx) the pixel block [cy*dy, (cy+1)*dy) x [cx*dx, (cx+1)*dx),
+ *     peak[b, cy, cx, n]  = max of cos[b, n] over the cell              (fp32: the bits of an element of cos)
+ *     where[b, cy, cx, n] = the lowest flat index y * Wo + x (output coordinates) among the cell's pixels that attain it   (int32)
+ * from the epilogue of the cosine kernel: the N-channel map need not exist.  A pixel whose feature is zero has cosine exactly 0 and takes
+ * part like any other.  Non-finite inputs are out of contract.
+ *   cos           naf_xna_cos_args as for naf_xna_cos_fwd, except that `out` may be NULL; when given it receives the scaled cosines, bit for
+ *                 bit what naf_xna_cos_fwd stores; norms as there
+ *   peak          device float [B, h, w, N], element strides peak_stride {b, cy, cx}, channel axis contiguous
+ *   where         device int32 [B, h, w, N], element strides where_stride {b, cy, cx}, channel axis contiguous
+ * No atomics, nothing crosses a workgroup: every output is deterministic, bit for bit.  The comparator on (value, flat index) -- greater
+ * value, or equal value and lower index -- is a total order, so the result does not depend on the order of the reduction.
+ * Served: what naf_xna_cos_fwd serves (profiles/cosine_peaks.txt holds the compiler's figures of every instantiation), Ho * Wo < 2^31.
+ * naf_xna_cos_peaks_select answers as naf_xna_cos_select does and additionally refuses: a NULL peak / where, an x stride below N, a
+ * pointer that is not 4-byte aligned, Ho * Wo >= 2^31, non-zero reserved fields (all -NAF_ERR_INVALID).  The struct must be
+ * zero-initialised.  Caller-owned memory and stream; capturable; no workspace. */
+typedef struct naf_xna_cos_peaks_args {
+    naf_xna_cos_args cos; /* cos.out may be NULL */
+    float* peak;
+    int32_t* where;
+    int64_t peak_stride[3];
+    int64_t where_stride[3];
+    int64_t reserved[2]; /* must be 0 */
+} naf_xna_cos_peaks_args;
+int naf_xna_cos_peaks_select(const naf_xna_cos_peaks_args* a);
+int naf_xna_cos_peaks_fwd(const naf_xna_cos_peaks_args* a, naf_stream_t stream);
+
+/* The k best cells of every (b, n): the n_cells candidates (peak, where) ordered by value descending, then by flat index ascending; the
+ * first k are returned.  One candidate per low-res cell -- a non-maximum suppression at the cell grid, not the k best pixels; k = 1 is
+ * the global maximum of cos[b, n] with the lowest flat index among ties.  One wave per (b, n), k selection passes in a fixed order.
+ *   peak / where  device float / int32 [B, n_cells, N] by the element strides peak_stride / where_stride {b, cell}, channel axis
+ *                 contiguous (naf_xna_cos_peaks_fwd's outputs with a cell stride: x stride, and y stride = w * x stride)
+ *   values / index   device float / int32 [B, N, k] dense
+ * 1 <= k <= min(n_cells, 64); indices must be non-negative (Ho * Wo < 2^31).  No workspace; capturable. */
+int naf_peaks_topk(const float* peak, const int32_t* where, float* values, int32_t* index, int32_t B, int32_t N, int32_t n_cells, int32_t k,
+                   const int64_t peak_stride[2], const int64_t where_stride[2], naf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

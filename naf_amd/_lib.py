@@ -96,6 +96,14 @@ class XnaCosCEArgs(C.Structure):
     ]
 
 
+class XnaCosPeaksArgs(C.Structure):
+    """naf_xna_cos_peaks_args (added after the mask-pooling entries, detected by symbol): naf_xna_cos_args plus the cell peaks."""
+    _fields_ = [
+        ("cos", XnaCosArgs), ("peak", C.c_void_p), ("where", C.c_void_p), ("peak_stride", I64x3), ("where_stride", I64x3),
+        ("reserved", C.c_int64 * 2),
+    ]
+
+
 MASK_BF16, MASK_U8 = 0, 1     # naf_mask_dtype
 
 
@@ -418,6 +426,10 @@ SIGNATURES = {
     "naf_xna_maskpool_fwd": (C.c_int, [C.POINTER(XnaMaskPoolArgs), C.c_void_p]),
     "naf_maskpool_apply": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                      C.POINTER(C.c_int64), C.c_int32, C.c_void_p]),
+    "naf_xna_cos_peaks_select": (C.c_int, [C.POINTER(XnaCosPeaksArgs)]),
+    "naf_xna_cos_peaks_fwd": (C.c_int, [C.POINTER(XnaCosPeaksArgs), C.c_void_p]),
+    "naf_peaks_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
     "naf_propagate_plan": (C.c_int, [C.POINTER(PropagateArgs), C.POINTER(C.c_int32)]),

@@ -603,6 +603,44 @@ int naf_maskpool_apply(const float* A, const void* v, const float* mass, float* 
     return naf_launch_maskpool_apply(A, v, mass, pooled, B, heads, K, C, hw, v_stride, mean, static_cast<hipStream_t>(stream));
 }
 
+// ---- peak search on the scaled cosines (after the mask-pooling entries) ----
+static int xna_cos_peaks_validate(const naf_xna_cos_peaks_args* c) {
+    const char* who = "naf_xna_cos_peaks";
+    NAF_REQUIRE(c != nullptr, "%s: args is NULL", who);
+    const int rc = xna_cos_validate(&c->cos, false);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(c->peak != nullptr && c->where != nullptr, "%s: peak / where is NULL", who);
+    NAF_REQUIRE(reinterpret_cast<uintptr_t>(c->peak) % 4 == 0 && reinterpret_cast<uintptr_t>(c->where) % 4 == 0, "%s: peak / where not 4-byte aligned", who);
+    NAF_REQUIRE(c->peak_stride[2] >= c->cos.N && c->where_stride[2] >= c->cos.N, "%s: peak / where x stride (%lld / %lld) smaller than N %d", who,
+                (long long)c->peak_stride[2], (long long)c->where_stride[2], c->cos.N);
+    NAF_REQUIRE((int64_t)c->cos.Ho * c->cos.Wo <= 0x7fffffffLL, "%s: %d x %d output pixels do not fit an int32 flat index", who, c->cos.Ho, c->cos.Wo);
+    NAF_REQUIRE(c->reserved[0] == 0 && c->reserved[1] == 0, "%s: reserved fields must be 0", who);
+    return NAF_OK;
+}
+
+int naf_xna_cos_peaks_select(const naf_xna_cos_peaks_args* a) {
+    int rc = xna_cos_peaks_validate(a);
+    if (rc == NAF_OK) rc = naf_xna_cos_peaks_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
+}
+
+int naf_xna_cos_peaks_fwd(const naf_xna_cos_peaks_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_cos_peaks_select(a);
+    if (sel < 0) return -sel;
+    return naf_launch_xna_cos_peaks(a, xna_scale(a->cos.scale, a->cos.Dq), static_cast<hipStream_t>(stream));
+}
+
+int naf_peaks_topk(const float* peak, const int32_t* where, float* values, int32_t* index, int32_t B, int32_t N, int32_t n_cells, int32_t k,
+                   const int64_t peak_stride[2], const int64_t where_stride[2], naf_stream_t stream) {
+    const char* who = "naf_peaks_topk";
+    NAF_REQUIRE(peak && where && values && index && peak_stride && where_stride, "%s: NULL pointer", who);
+    NAF_REQUIRE(B > 0 && N > 0 && n_cells > 0, "%s: non-positive size", who);
+    NAF_REQUIRE(k >= 1 && k <= 64 && k <= n_cells, "%s: k must be in 1 .. min(cells, 64) = %d, got %d", who, n_cells < 64 ? n_cells : 64, k);
+    NAF_REQUIRE((int64_t)B * N <= 0x7fffffffLL, "%s: %lld rows out of range", who, (long long)B * N);
+    NAF_REQUIRE(peak_stride[1] >= N && where_stride[1] >= N, "%s: cell stride smaller than N %d", who, N);
+    return naf_launch_peaks_topk(peak, where, values, index, B, N, n_cells, k, peak_stride, where_stride, static_cast<hipStream_t>(stream));
+}
+
 static int xna_bwd_validate(const naf_xna_bwd_args* a) {
     NAF_REQUIRE(a != nullptr, "naf_xna_bwd: args is NULL");
     NAF_REQUIRE(a->q && a->k_lr && a->v_lr && a->dout && a->dq && a->dk_lr && a->dv_lr, "naf_xna_bwd: NULL tensor pointer");

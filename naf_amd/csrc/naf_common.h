@@ -83,6 +83,10 @@ int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s);  
 int naf_xna_cos_eligible(const naf_xna_cos_args* a);                              // xna_cos.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
 int naf_launch_xna_cos_ce(const naf_xna_cos_ce_args* a, float scale, hipStream_t s);   // xna_cos.hip: ... with the classification epilogue
 int naf_xna_cos_ce_eligible(const naf_xna_cos_ce_args* a);                            // xna_cos.hip: naf_xna_cos_eligible plus the dlogits layout
+int naf_launch_xna_cos_peaks(const naf_xna_cos_peaks_args* a, float scale, hipStream_t s);   // xna_cos.hip: ... with the peak epilogue
+int naf_xna_cos_peaks_eligible(const naf_xna_cos_peaks_args* a);                             // xna_cos.hip: naf_xna_cos_eligible plus the peak instantiation
+int naf_launch_peaks_topk(const float* peak, const int32_t* where, float* values, int32_t* index, int B, int N, int n_cells, int k,
+                          const int64_t* peak_stride, const int64_t* where_stride, hipStream_t s);   // peaks_topk.hip
 int naf_launch_xna_maskpool(const naf_xna_maskpool_args* a, float scale, hipStream_t s);   // xna_pool.hip: mask pooling (cell kernel, gather, mass)
 int naf_xna_maskpool_eligible(const naf_xna_maskpool_args* a);                          // xna_pool.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
 size_t naf_xna_maskpool_ws(const naf_xna_maskpool_args* a, size_t* mass_offset);        // xna_pool.hip: workspace bytes, offset of the per-cell masses

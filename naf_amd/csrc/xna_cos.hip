@@ -52,6 +52,17 @@ int naf_xna_cos_ce_eligible(const naf_xna_cos_ce_args* c) {
     return NAF_OK;
 }
 
+// What the peak epilogue asks beyond naf_xna_cos_eligible (the request is validated: naf_api.hip).
+int naf_xna_cos_peaks_eligible(const naf_xna_cos_peaks_args* c) {
+    const int rc = naf_xna_cos_eligible(&c->cos);
+    if (rc != NAF_OK) return rc;
+    if (!xna_cos_peak_served(c->cos.ky, xna_head_nct((c->cos.N + 15) & ~15))) {
+        naf_set_error("naf_xna_cos_peaks: no fused kernel for window %d with N = %d (registers: the instantiation would spill)", c->cos.ky, c->cos.N);
+        return NAF_ERR_UNSUPPORTED;
+    }
+    return NAF_OK;
+}
+
 // `who` names the entry in the messages.
 static int cos_fill(const naf_xna_cos_args* a, float scale, const char* who, XnaCosParams& p, XnaCosEpilogue& e) {
     const int rc = xna_headsum_fill(p, a, scale, who);
@@ -101,5 +112,24 @@ int naf_launch_xna_cos_ce(const naf_xna_cos_ce_args* c, float scale, hipStream_t
 #undef NAF_X
     }
     naf_set_error("naf_xna_cos_ce_fwd: kernel size %d has no instantiation", c->cos.ky);
+    return NAF_ERR_UNSUPPORTED;
+}
+
+int naf_launch_xna_cos_peaks(const naf_xna_cos_peaks_args* c, float scale, hipStream_t s) {
+    XnaCosParams p;
+    XnaCosPeakEpilogue x;
+    const int rc = cos_fill(&c->cos, scale, "naf_xna_cos_peaks_fwd", p, x.cos);
+    if (rc != NAF_OK) return rc;
+    x.peak = c->peak;
+    x.where = c->where;
+    for (int i = 0; i < 3; ++i) {
+        x.ps[i] = c->peak_stride[i]; x.is[i] = c->where_stride[i];
+    }
+    switch (c->cos.ky) {
+#define NAF_X(K) case K: return xna_cos_launch_ks<K>(p, x, s);
+        NAF_FOR_WINDOWS(NAF_X)
+#undef NAF_X
+    }
+    naf_set_error("naf_xna_cos_peaks_fwd: kernel size %d has no instantiation", c->cos.ky);
     return NAF_ERR_UNSUPPORTED;
 }

@@ -40,6 +40,21 @@
 //   past the NCT*16 accumulator channels.  s is the struct's float, or one fp32 device value behind scale_ptr, read once per round of the
 //   epilogue.  Every output is optional (NULL: a wave-uniform branch); vector stores only, no atomics, nothing crosses a workgroup.
 //   Tiles per wave and which pairs exist: xna_cos_ce_tpw / xna_cos_ce_served (profiles/cosine_objective.txt).
+//
+// Peak epilogue (Epi = XnaCosPeakEpilogue, naf_xna_cos_peaks_fwd): the maximum of every channel over the PIXELS of the cell and where it
+// is, so that the N-channel map need not exist.  z = logit_scale * (acc * inv) is the cosine epilogue's expression (nothing is
+// contracted), so a peak has the bits naf_xna_cos_fwd stores; `out` stays optional and receives exactly those.  The pixel is on
+// col = lane & 15, so the reduction runs across the 16 lanes of a row (naf_cols_max: DPP, no LDS), the direction naf_rows_max does not
+// cover.  The comparator on (value, flat index y * Wo + x) is "greater value, or equal value and lower index": a total order, so the
+// shape of the reduction cannot change the result.  Stages:
+//   1. per live tile and channel: the row's maximum, then the lowest col that holds it (a ballot; a lower col is a lower index).  Lanes
+//      past a partial last tile repeat the row's last pixel: they hold that pixel's value and can only tie with it, at a higher col.
+//   2. lane col = r of a row owns channel ct*16 + grp*4 + r: it compare-updates the wave's own LDS array [wave][channel] of pairs (the
+//      same lane reads and writes a slot: no race, no barrier).  The array lies past xna_cos_lds_for: K / PV / V are restaged every
+//      round.  Tiles past the cell never get here; a wave without a live tile leaves (-inf, INT_MAX), which loses to everything.
+//   3. after the last round: a barrier, thread n < N merges the eight waves' pairs and stores peak / where [b, cy, cx, n].
+//   Vector stores only, no atomics, nothing crosses a workgroup.  Tiles per wave and which pairs exist: xna_cos_peak_tpw /
+//   xna_cos_peak_served (profiles/cosine_peaks.txt).
 #pragma once
 #include "xna_head_kernel.h"
 
@@ -79,8 +94,17 @@ struct XnaCosCEEpilogue {
     int64_t ts[3], ls[3], bs[3], gs[3], ds[3];   // {b, y, x} element strides of target / loss / labels / dlogits / dscale
     int32_t gc;                // channels of a dlogits row the kernel writes (multiple of 8, >= npad)
 };
+// ... and with the peak epilogue: XnaCosEpilogue first as well
+struct XnaCosPeakEpilogue {
+    XnaCosEpilogue cos;
+    float* peak;               // [B, h, w, N] by ps: the cell's maximum
+    int32_t* where;            // [B, h, w, N] by is: its flat index y * Wo + x
+    int64_t ps[3], is[3];      // {b, cy, cx} element strides, channels contiguous
+};
 template <typename T> struct XnaCosIsCE { static constexpr bool value = false; };
 template <> struct XnaCosIsCE<XnaCosCEEpilogue> { static constexpr bool value = true; };
+template <typename T> struct XnaCosIsPeak { static constexpr bool value = false; };
+template <> struct XnaCosIsPeak<XnaCosPeakEpilogue> { static constexpr bool value = true; };
 constexpr size_t XNA_COS_ARG_OFFSET = (sizeof(XnaCosParams) + alignof(XnaCosEpilogue) - 1) / alignof(XnaCosEpilogue) * alignof(XnaCosEpilogue);
 
 constexpr int XNA_COS_DVC = 64;   // value channels staged at a time
@@ -110,11 +134,33 @@ constexpr bool xna_cos_ce_served(int ks, int nct) { return xna_cos_fits(ks, nct)
 constexpr bool xna_cos_ce_served(int ks, int nct) { return xna_cos_served(ks, nct); }
 #endif
 
+// the peak epilogue's instantiations, from the compiler's figures as above (profiles/cosine_peaks.txt; tools/cosine_peaks_time.py
+// --resources).  Its per-wave pairs [8 waves][NCT * 16 channels] x 8 bytes follow the staged windows in LDS.
+constexpr int xna_cos_peak_tpw(int ks, int nct) { return xna_cos_ce_tpw(ks, nct); }
+constexpr size_t xna_cos_peak_lds(int nct) { return (size_t)XNA_HEAD_NW * nct * 16 * 8; }
+#ifdef NAF_XNA_COS_ALL
+constexpr bool xna_cos_peak_served(int ks, int nct) { return xna_cos_fits(ks, nct); }
+#else
+constexpr bool xna_cos_peak_served(int ks, int nct) { return xna_cos_served(ks, nct); }
+#endif
+
+// max over the 16 lanes of a row (col = lane & 15), every lane gets it: two quad permutes, then the mirrors of 8 and of 16 lanes (DPP)
+__device__ __forceinline__ float naf_cols_max(float v) {
+    int b = __float_as_int(v);
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0xB1, 0xf, 0xf, false)));    // quad_perm [1, 0, 3, 2]
+    b = __float_as_int(v);
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x4E, 0xf, 0xf, false)));    // quad_perm [2, 3, 0, 1]
+    b = __float_as_int(v);
+    v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x141, 0xf, 0xf, false)));   // row_half_mirror
+    b = __float_as_int(v);
+    return fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x140, 0xf, 0xf, false)));   // row_mirror
+}
+
 template <int KS, int NCT, typename Epi = XnaCosEpilogue>
 __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosParams p, const Epi epi) {
-    constexpr bool CE = XnaCosIsCE<Epi>::value;
+    constexpr bool CE = XnaCosIsCE<Epi>::value, PK = XnaCosIsPeak<Epi>::value;
     constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
-    constexpr int TPW = CE ? xna_cos_ce_tpw(KS, NCT) : xna_cos_tpw(KS, NCT);
+    constexpr int TPW = CE ? xna_cos_ce_tpw(KS, NCT) : PK ? xna_cos_peak_tpw(KS, NCT) : xna_cos_tpw(KS, NCT);
     using G = XnaGeom<KS, 1>;
     constexpr int NSLOT = G::NSLOT, MT = G::MT, KST = G::KST, KROW = G::KROW;
     constexpr int DVT = NCT * 16, VROW = XnaVRow<DVT>::VROW, VCH = DVT / 8;
@@ -168,6 +214,16 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosP
         a[4] = hi[0]; a[5] = hi[1]; a[6] = hi[2]; a[7] = hi[3];
         return a;
     };
+
+    // peak epilogue: the wave's running (value, flat index) per channel; lane (col < 4, grp) owns channels ct*16 + grp*4 + col
+    u32x2_t* Pk = reinterpret_cast<u32x2_t*>(smem + xna_cos_lds_for(KS, NCT)) + wave * DVT;
+    if constexpr (PK) {
+        static_assert(xna_cos_lds_for(KS, NCT) % 8 == 0 && xna_cos_lds_for(KS, NCT) + xna_cos_peak_lds(NCT) <= 160 * 1024, "the peak pairs do not fit the LDS");
+        if (col < 4) {
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) Pk[ct * 16 + grp * 4 + col] = u32x2_t{__float_as_uint(-INFINITY), 0x7fffffffu};
+        }
+    }
 
     for (int t0 = 0; t0 < ntile; t0 += NW * TPW) {
         // this wave's tiles of the round: t0 + u * NW + wave (wave-uniform); a tile past the cell is computed on clamped
@@ -471,6 +527,46 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosP
                     if (xc->dscale != nullptr && egrp == 0 && inpx) xc->dscale[b * xc->ds[0] + gy * xc->ds[1] + gx * xc->ds[2]] = dsl;
                 }
             }
+        } else if constexpr (PK) {
+            // ---- peak epilogue (see the header comment): the cell's maximum of every channel and its flat index ----
+#pragma clang fp contract(off)
+            const float ls = x->logit_scale;
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u]) continue;   // wave-uniform: a tile past the cell takes no part; the lane reductions below run on whole waves
+                const float nrm = sqrtf(naf_rows_sum(ssq[u]));
+                const float inv = 1.0f / fmaxf(nrm, 1e-12f);
+                const bool inpx = tx0v[u] + ecol < p.dx;   // lanes past a partial last tile hold the row's last pixel again, store nothing
+                float* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)min(tx0v[u] + ecol, p.dx - 1) * p.os[2];
+                const bool st = p.out != nullptr && inpx;
+                if (x->norms != nullptr && egrp == 0 && inpx)
+                    x->norms[b * x->ns[0] + (int64_t)(cy * p.dy + tyv[u]) * x->ns[1] + (int64_t)(cx * p.dx + tx0v[u] + ecol) * x->ns[2]] = nrm;
+                const int base = (cy * p.dy + tyv[u]) * p.Wo + cx * p.dx + tx0v[u];   // flat index of the tile's col 0 (host: Ho * Wo < 2^31)
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) {
+                    if (ct * 16 >= p.N) continue;   // wave-uniform: channels that are never stored
+                    float bv = 0.f;
+                    int bi = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float z = ls * (acc[u][ct][r] * inv);
+                        if (st && ct * 16 + egrp * 4 + r < p.N) op[ct * 16 + egrp * 4 + r] = z;
+                        const float m = naf_cols_max(z);
+                        // the lowest col of the row that holds the maximum: a repeated last pixel ties only with itself, at a higher col
+                        const uint32_t hit = (uint32_t)(__builtin_amdgcn_ballot_w64(z == m) >> (egrp * 16)) & 0xffffu;
+                        if (ecol == r) {
+                            bv = m;
+                            bi = base + __builtin_ctz(hit | 0x10000u);
+                        }
+                    }
+                    if (ecol < 4) {
+                        u32x2_t* slot = Pk + ct * 16 + egrp * 4 + ecol;
+                        const u32x2_t old = *slot;
+                        const float ov = __uint_as_float(old[0]);
+                        if (bv > ov || (bv == ov && bi < (int)old[1])) *slot = u32x2_t{__float_as_uint(bv), (uint32_t)bi};
+                    }
+                }
+            }
         } else {
 #pragma unroll
             for (int u = 0; u < TPW; ++u) {
@@ -492,16 +588,39 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_cos_kernel(const XnaCosP
             }
         }
     }
+    if constexpr (PK) {
+        // ---- the eight waves' pairs of a channel, merged in wave order by the same comparator; one store per (cell, channel < N) ----
+        __syncthreads();
+        const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(ka));
+        const XnaCosPeakEpilogue __attribute__((address_space(4)))* xp = reinterpret_cast<const XnaCosPeakEpilogue __attribute__((address_space(4)))*>(ka + XNA_COS_ARG_OFFSET);
+        if (tid < DVT && tid < p.N) {
+            const u32x2_t* all = reinterpret_cast<const u32x2_t*>(smem + xna_cos_lds_for(KS, NCT));
+            float bv = __uint_as_float(all[tid][0]);
+            int bi = (int)all[tid][1];
+#pragma unroll
+            for (int wv = 1; wv < NW; ++wv) {
+                const u32x2_t o = all[wv * DVT + tid];
+                const float ov = __uint_as_float(o[0]);
+                if (ov > bv || (ov == bv && (int)o[1] < bi)) {
+                    bv = ov;
+                    bi = (int)o[1];
+                }
+            }
+            xp->peak[b * xp->ps[0] + (int64_t)cy * xp->ps[1] + (int64_t)cx * xp->ps[2] + tid] = bv;
+            xp->where[b * xp->is[0] + (int64_t)cy * xp->is[1] + (int64_t)cx * xp->is[2] + tid] = bi;
+        }
+    }
 }
 
 template <int KS, int NCT, typename Epi>
 static int xna_cos_launch_one(const XnaCosParams& p, const Epi& epi, hipStream_t s) {
-    constexpr bool CE = XnaCosIsCE<Epi>::value;
-    if constexpr (!(CE ? xna_cos_ce_served(KS, NCT) : xna_cos_served(KS, NCT))) {
-        naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", CE ? "naf_xna_cos_ce_fwd" : "naf_xna_cos_fwd", KS, NCT);
+    constexpr bool CE = XnaCosIsCE<Epi>::value, PK = XnaCosIsPeak<Epi>::value;
+    if constexpr (!(CE ? xna_cos_ce_served(KS, NCT) : PK ? xna_cos_peak_served(KS, NCT) : xna_cos_served(KS, NCT))) {
+        naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", CE ? "naf_xna_cos_ce_fwd" : PK ? "naf_xna_cos_peaks_fwd" : "naf_xna_cos_fwd", KS, NCT);
         return NAF_ERR_UNSUPPORTED;
     } else {
-        constexpr size_t lds = xna_cos_lds_for(KS, NCT);
+        constexpr size_t lds = xna_cos_lds_for(KS, NCT) + (PK ? xna_cos_peak_lds(NCT) : 0);
         auto kern = xna_cos_kernel<KS, NCT, Epi>;
         if (lds > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -511,7 +630,7 @@ static int xna_cos_launch_one(const XnaCosParams& p, const Epi& epi, hipStream_t
             }
         }
         hipLaunchKernelGGL(kern, dim3(p.nblocks), dim3(XNA_HEAD_NW * 64), lds, s, p, epi);
-        return naf_check_launch(CE ? "xna_cos_kernel (classification epilogue)" : "xna_cos_kernel");
+        return naf_check_launch(CE ? "xna_cos_kernel (classification epilogue)" : PK ? "xna_cos_kernel (peak epilogue)" : "xna_cos_kernel");
     }
 }
 
@@ -523,11 +642,13 @@ int xna_cos_launch_ks(const XnaCosParams& p, const Epi& epi, hipStream_t s) {
     if (nct == 4) return xna_cos_launch_one<KS, 4, Epi>(p, epi, s);
     if (nct == 10) return xna_cos_launch_one<KS, 10, Epi>(p, epi, s);
     if (nct == 16) return xna_cos_launch_one<KS, 16, Epi>(p, epi, s);
-    naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", XnaCosIsCE<Epi>::value ? "naf_xna_cos_ce_fwd" : "naf_xna_cos_fwd", KS, nct);
+    naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d",
+                  XnaCosIsCE<Epi>::value ? "naf_xna_cos_ce_fwd" : XnaCosIsPeak<Epi>::value ? "naf_xna_cos_peaks_fwd" : "naf_xna_cos_fwd", KS, nct);
     return NAF_ERR_UNSUPPORTED;
 }
 
-// xna_cos_inst.hip (-DNAF_KS=<KS>) defines the two, xna_cos.hip declares them (extern) and dispatches on the window.
+// xna_cos_inst.hip (-DNAF_KS=<KS>) defines the three, xna_cos.hip declares them (extern) and dispatches on the window.
 #define NAF_XNA_COS_WINDOW(LINKAGE, KS)                                                                                    \
     LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosEpilogue&, hipStream_t);                   \
-    LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosCEEpilogue&, hipStream_t);
+    LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosCEEpilogue&, hipStream_t);     \
+    LINKAGE template int xna_cos_launch_ks<KS>(const XnaCosParams&, const XnaCosPeakEpilogue&, hipStream_t);

@@ -711,6 +711,16 @@ def _cosine_head(head, channels: int) -> torch.Tensor:
     return weight
 
 
+Peaks = collections.namedtuple("Peaks", ["scores", "y", "x", "cell_scores", "cell_index"])
+Peaks.__doc__ = """Result of ``NAF.locate``: ``scores`` [B, N, k] fp32, the k best cells' maxima of the scaled cosine in descending order (ties: the
+lower flat index first); ``y``, ``x`` [B, N, k] int64, their pixels in output coordinates; ``cell_scores`` [B, N, h, w] fp32 and ``cell_index``
+[B, N, h, w] int32, every low-res cell's maximum and its flat index ``y * Wo + x``."""
+
+Match = collections.namedtuple("Match", ["scores", "y", "x", "distance"])
+Match.__doc__ = """Result of ``NAF.match``: per source point its k best locations in the destination image, ``scores`` [P, k] fp32, ``y``, ``x`` [P, k]
+int64; ``distance`` [P] fp32 with ``mutual=True`` (the pixel distance between the point and where its best match leads back to), else None."""
+
+
 def _lib_last_error() -> str:
     return ops._lib.last_error()
 
@@ -1431,6 +1441,106 @@ class NAF(nn.Module):
             win_y = torch.where(ok, iy[py.clamp(0, ho - 1)], -1)
             win_x = torch.where(ok, ix[px.clamp(0, wo - 1)], -1)
         return PointQuery(out, logits, probs, win_y, win_x)
+
+    def locate(self, image, features, output_size, embeddings, *, topk=1, logit_scale=1.0, path="auto") -> Peaks:
+        """Where in the upsampled map each of N vectors matches best: ``naf.locate(image_or_guidance, feats, (Ho, Wo), E, topk=k)``.
+
+        With ``cos`` what ``naf(image, feats, size, head=E, cosine=True, logit_scale=s)`` returns, every low-res cell (the ``Ho / h`` x
+        ``Wo / w`` block of pixels it is upsampled to; the ratio must be an integer, ValueError otherwise) yields the maximum of ``cos[b, n]``
+        over its pixels and the lowest flat index ``y * Wo + x`` among the pixels that attain it; the ``topk`` best cells per (b, n), by value
+        descending, then by index ascending, are returned as a ``Peaks``.  One candidate per cell: a non-maximum suppression at the cell
+        grid, not the k best pixels; ``topk=1`` is the global maximum with the lowest flat index among ties.  A pixel whose feature is zero
+        has cosine 0 and takes part like any other.  ``embeddings`` takes the forms ``cosine=True`` takes; ``image`` may be a ``Guidance``.
+        Inference only: runs under ``no_grad`` whatever the mode.  ``path="auto"``: the peak epilogue of the cosine kernel
+        (``ops.xna_cos_peaks``: the [B, N, Ho, Wo] map is never allocated; more than 256 vectors run in chunks of 256) wherever
+        ``naf_xna_cos_peaks_select`` grants it, else the composition (the cosine call, then torch reductions with the same tie rule): fp16 /
+        fp32 features, windows 13 / 15 with more than 64 vectors.  ``"fused"`` insists (NafHipError with the library's reason),
+        ``"composed"`` is the A/B arm.  1 <= topk <= min(h * w, 64).  Every refusal comes before any device work."""
+        if path not in ("auto", "fused", "composed"):
+            raise ValueError(f"locate: path must be 'auto', 'fused' or 'composed', got {path!r}")
+        if not isinstance(features, torch.Tensor) or features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(getattr(features, 'shape', ()))}")
+        weight = _cosine_head(embeddings, features.shape[1])
+        if not math.isfinite(float(logit_scale)):
+            raise ValueError(f"logit_scale must be finite, got {logit_scale}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, C, N = features.shape[0], features.shape[1], weight.shape[0]
+        h, w = int(features.shape[-2]), int(features.shape[-1])
+        if ho % h or wo % w:
+            raise ValueError(f"locate: {ho}x{wo} pixels over {h}x{w} cells is not an integer ratio: there are no cells")
+        if ho * wo >= 2 ** 31:
+            raise ValueError(f"locate: {ho}x{wo} pixels do not fit an int32 flat index")
+        k = int(topk)
+        if k != topk or not 1 <= k <= min(h * w, 64):
+            raise ValueError(f"locate: topk must be an integer in 1 .. min(h * w, 64) = {min(h * w, 64)}, got {topk!r}")
+        if not (image.is_cuda and features.is_cuda and weight.is_cuda):
+            raise _rocm_only(image=image, features=features, embeddings=weight)
+        if isinstance(image, Guidance):
+            image.check(self)
+        dev = features.device
+        if B == 0 or N == 0:
+            z = lambda *sh, dt=torch.float32: torch.empty(sh, dtype=dt, device=dev)
+            return Peaks(z(B, N, k), z(B, N, k, dt=torch.int64), z(B, N, k, dt=torch.int64), z(B, N, h, w), z(B, N, h, w, dt=torch.int32))
+        heads, ksz, enc = self.upsampler.num_heads, self.upsampler.kernel_size, self.image_encoder
+        chunks = sorted({min(N, 256), N % 256 or min(N, 256)})      # the sizes ops.xna_cos_peaks launches
+        with torch.no_grad():
+            reason = None       # why the fused kernel does not take the call
+            if features.dtype != torch.bfloat16:
+                reason = f"the fused kernel reads bfloat16 features, got {features.dtype}"
+            elif C % heads or enc.out_channels % heads:
+                reason = f"feature channels {C} / guidance channels {enc.out_channels} not divisible by {heads} heads"
+            else:
+                probe = torch.empty((B, ho, wo, heads, enc.out_channels // heads), dtype=torch.bfloat16, device="meta").permute(0, 3, 1, 2, 4)
+                for n in chunks:
+                    if reason is None and ops.xna_cos_peaks_select(probe, (h, w), C // heads, n, ksz) != "fused":
+                        reason = _lib_last_error() or f"naf_xna_cos_peaks_select refuses {n} embeddings"
+            if path == "fused" and reason is not None:
+                raise ops._lib.NafHipError(f"naf.locate(..., path='fused'): {reason}")
+            if path == "composed" or reason is not None:
+                with ops._Timed("locate_composed"):
+                    cos = self.forward(image, features, (ho, wo), head=weight, cosine=True, logit_scale=logit_scale)
+                    peak, where = ops.peaks_from_cosines(cos, (h, w))
+                    del cos
+            else:
+                fusable = lambda q5, tabs: all(ops.xna_cos_peaks_select(q5, (h, w), C // heads, n, ksz, rope_tables=tabs) == "fused" for n in chunks)
+                q5, k5, tabs = self.guidance_qk(image, (h, w), (ho, wo), fusable=fusable)
+                v5 = ops.pack_values(features).view(B, h, w, heads, C // heads).permute(0, 3, 1, 2, 4)
+                with ops._Timed("attention"):
+                    peak, where, _ = ops.xna_cos_peaks(q5, k5, v5, weight, ksz, logit_scale=logit_scale, path="fused", scale=self.upsampler.scale,
+                                                       rope_tables=tabs)
+            scores, index = ops.peaks_topk(peak, where, k)
+            index = index.long()
+            return Peaks(scores, index // wo, index % wo, peak, where)
+
+    def match(self, src, src_features, points, dst, dst_features, output_size, *, topk=1, mutual=False) -> Match:
+        """Keypoint transfer: find the pixels of ``points`` of one image in another.  ``src`` and ``dst`` are ``Guidance`` objects of the same
+        batch size, ``points`` as for ``query`` ([P, 3] of (b, y, x), [P, 2] for a batch of 1; inside the grid -- a point outside has a NaN
+        vector and no match).  The call is ``query(src, points, features=src_features, output_size=output_size).features`` followed by
+        ``locate(dst, dst_features, output_size, those, topk=topk)``, read for every point in the destination image of the point's batch
+        index.  ``mutual=True`` also goes the way back -- ``query`` at the best locations in ``dst``, ``locate`` in ``src`` -- and reports
+        the round-trip pixel distance per point, the usual cycle-consistency filter (0 is not guaranteed for a perfect match: another
+        pixel may tie within the arithmetic's error).  Returns a ``Match``.  Pure host glue over the two calls."""
+        if not isinstance(src, Guidance) or not isinstance(dst, Guidance):
+            raise TypeError(f"match: src and dst must be Guidance objects (naf.guide(image)), got {type(src).__name__} / {type(dst).__name__}")
+        if src.shape[0] != dst.shape[0]:
+            raise ValueError(f"match: src holds {src.shape[0]} images, dst {dst.shape[0]}")
+        with torch.no_grad():
+            vec = self.query(src, points, features=src_features, output_size=output_size, weights=None).features
+            dev = vec.device
+            pts = points.to(device=dev, dtype=torch.int64)
+            bidx = pts[:, 0] if pts.shape[1] == 3 else torch.zeros(pts.shape[0], dtype=torch.int64, device=dev)
+            bsel = bidx.clamp(0, dst.shape[0] - 1)
+            rows = torch.arange(pts.shape[0], device=dev)
+            there = self.locate(dst, dst_features, output_size, vec, topk=topk)
+            scores, y, x = there.scores[bsel, rows], there.y[bsel, rows], there.x[bsel, rows]
+            distance = None
+            if mutual:
+                found = torch.stack([bsel, y[:, 0], x[:, 0]], dim=1)
+                back = self.locate(src, src_features, output_size, self.query(dst, found, features=dst_features, output_size=output_size,
+                                                                              weights=None).features, topk=1)
+                by, bx = back.y[bsel, rows, 0], back.x[bsel, rows, 0]
+                distance = ((by - pts[:, -2]).float().square() + (bx - pts[:, -1]).float().square()).sqrt()
+        return Match(scores, y, x, distance)
 
     def _forward_regress(self, image, features, output_size, regress, regress_path):
         """``forward(..., regress=regress)``: see ``forward``."""

@@ -1625,6 +1625,132 @@ def xna_cos_forward(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, emb
         return cosine_from_features(f, e_hat, logit_scale, return_norms)
 
 
+# ---- ... and the peak search: where in the upsampled map each embedding matches best, without the N-channel map ------------------
+def peaks_from_cosines(cos: torch.Tensor, lr_size) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The definition in torch ops: for cos [B, N, Ho, Wo] fp32 and an integer ratio, ``peak`` [B, N, h, w] = the maximum over each cell's
+    pixels and ``where`` [B, N, h, w] int32 = the lowest flat index ``y * Wo + x`` among the cell's pixels that attain it
+    (``where(cos == peak, index, big).amin``: torch's argmax promises no tie rule on the device)."""
+    B, N, Ho, Wo = cos.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    if Ho % h or Wo % w:
+        raise ValueError(f"peak search: {Ho}x{Wo} pixels over {h}x{w} cells is not an integer ratio: there are no cells")
+    dy, dx = Ho // h, Wo // w
+    c = cos.reshape(B, N, h, dy, w, dx)
+    peak = c.amax(dim=(3, 5))
+    idx = torch.arange(Ho * Wo, dtype=torch.int32, device=cos.device).view(1, 1, h, dy, w, dx)
+    big = torch.full((), 2 ** 31 - 1, dtype=torch.int32, device=cos.device)
+    where = torch.where(c == peak[:, :, :, None, :, None], idx, big).amin(dim=(3, 5))
+    return peak, where
+
+
+def xna_cos_peaks_select(q: torch.Tensor, lr_size, Dv: int, n_out: int, kernel_size, *, value_dtype: torch.dtype = torch.bfloat16,
+                         rope_tables=None) -> str:
+    """Which route ``xna_cos_peaks(path="auto")`` takes for these shapes and at most 256 embeddings (more run in chunks of 256): "fused"
+    (``naf_xna_cos_peaks_select`` grants the peak epilogue of the cosine kernel) or "composed" (``xna_cos_forward``, then the definition in
+    torch ops).  The conventions of ``xna_cos_select``: a host-side query, nothing is launched or read, invalid arguments raise ValueError."""
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1 or value_dtype != torch.bfloat16 or not 1 <= int(n_out) <= 256 or int(Dv) < 1:
+        return "composed"
+    outer = _lib.XnaCosPeaksArgs()
+    h, w, n = int(lr_size[0]), int(lr_size[1]), int(n_out)
+    outer.peak = outer.where = q.data_ptr() or 16
+    outer.peak_stride = outer.where_stride = I64x3(h * w * n, w * n, n)
+    return _head_route(outer.cos, "naf_xna_cos_peaks_select", q, lr_size, n_out, kernel_size, rope_tables, Dv=int(Dv), outer=outer)
+
+
+def xna_cos_peaks(q: torch.Tensor, k_lr: torch.Tensor, v_lr: torch.Tensor, embeddings: torch.Tensor, kernel_size, *,
+                  logit_scale: float = 1.0, want_cos: bool = False, path: str = "auto", scale: Optional[float] = None, rope_tables=None):
+    """Cell peaks of the scaled cosines: with ``cos`` what ``xna_cos_forward`` returns for the same operands, ``peak[b, n, cy, cx]`` is the
+    maximum of ``cos[b, n]`` over the pixels of low-res cell (cy, cx) -- the bits of an element of ``cos`` -- and ``where[b, n, cy, cx]``
+    the lowest flat index ``y * Wo + x`` among the cell's pixels that attain it.  Needs an integer ratio (ValueError otherwise: there are
+    no cells).  Returns ``(peak [B, N, h, w] fp32, where [B, N, h, w] int32, cos or None)``: the first two are logical views of dense
+    channels-last [B, h, w, N] buffers; ``want_cos`` also returns the cosines (then the map is written).  Inference only.
+    ``path="auto"``: the kernel (``naf_xna_cos_peaks_fwd``: the maximum over the cell's pixels is taken in the epilogue of the cosine
+    kernel, the [B, N, Ho, Wo] map never exists) where ``naf_xna_cos_peaks_select`` grants it, else the composition ``xna_cos_forward`` +
+    ``peaks_from_cosines`` (fp16 / fp32 values, windows 13 / 15 with more than 64 embeddings).  More than 256 embeddings run in chunks of
+    256.  ``"fused"`` insists and raises NafHipError with the library's reason; ``"composed"`` insists on the composition."""
+    e_hat, (B, heads, Ho, Wo, Dq, h, w, Dv) = _check_cos_operands("xna_cos_peaks", q, k_lr, v_lr, embeddings, path)
+    ky, kx = _ksize(kernel_size)
+    N = e_hat.shape[0]
+    if not math.isfinite(float(logit_scale)):
+        raise ValueError(f"xna_cos_peaks: logit_scale must be finite, got {logit_scale}")
+    if Ho % h or Wo % w:
+        raise ValueError(f"xna_cos_peaks: {Ho}x{Wo} pixels over {h}x{w} cells is not an integer ratio: there are no cells")
+    if Ho * Wo >= 2 ** 31:
+        raise ValueError(f"xna_cos_peaks: {Ho}x{Wo} pixels do not fit an int32 flat index")
+    if N > 256:
+        parts = [xna_cos_peaks(q, k_lr, v_lr, embeddings[n0:n0 + 256], kernel_size, logit_scale=logit_scale, want_cos=want_cos, path=path, scale=scale,
+                               rope_tables=rope_tables) for n0 in range(0, N, 256)]
+        return (torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1),
+                torch.cat([p[2] for p in parts], dim=1) if want_cos else None)
+    lib = _lib.load()
+    dev = q.device
+    with torch.no_grad():
+        if path != "composed" and (path == "fused" or v_lr.dtype == torch.bfloat16):
+            if v_lr.dtype != torch.bfloat16:
+                raise _lib.NafHipError(f"xna_cos_peaks: the fused kernel needs bfloat16 values, got {v_lr.dtype}")
+            pv = torch.einsum("ngd,bghwd->bghwn", e_hat.reshape(N, heads, Dv), v_lr.float())
+            pad = head_npad(N) - N
+            pv5 = (torch.nn.functional.pad(pv, (0, pad)) if pad else pv).to(torch.bfloat16)
+            out = torch.empty((B, Ho, Wo, N), dtype=torch.float32, device=dev) if want_cos else None
+            peak = torch.empty((B, h, w, N), dtype=torch.float32, device=dev)
+            where = torch.empty((B, h, w, N), dtype=torch.int32, device=dev)
+            a = _lib.XnaCosPeaksArgs()
+            a.cos = _fill_xna_cos(q, k_lr, pv5, v_lr, out if want_cos else peak, None, N, ky, kx, path, scale, logit_scale, rope_tables)
+            if not want_cos:
+                a.cos.out = None
+            a.peak, a.where = peak.data_ptr(), where.data_ptr()
+            a.peak_stride, a.where_stride = _strides3(peak), _strides3(where)
+            sel = lib.naf_xna_cos_peaks_select(C.byref(a))
+            if sel == _lib.XNA_HEAD_FUSED:
+                with torch.cuda.device(dev), _Timed("xna_cos_peaks"):
+                    rc = lib.naf_xna_cos_peaks_fwd(C.byref(a), _stream(q))
+                _lib.check(rc, "naf_xna_cos_peaks_fwd")
+                return peak.permute(0, 3, 1, 2), where.permute(0, 3, 1, 2), (out.permute(0, 3, 1, 2) if want_cos else None)
+            if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
+                _lib.check(-sel, "naf_xna_cos_peaks_select")
+            del out, peak, where, pv5, pv
+        with _Timed("xna_cos_peaks_composed"):
+            cos = xna_cos_forward(q, k_lr, v_lr, e_hat, (ky, kx), logit_scale=logit_scale, path="auto", scale=scale, rope_tables=rope_tables)
+            peak, where = peaks_from_cosines(cos, (h, w))
+            # channels-last, as the kernel's
+            peak = peak.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+            where = where.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
+        return peak, where, (cos if want_cos else None)
+
+
+def peaks_topk(peak: torch.Tensor, where: torch.Tensor, k: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The ``k`` best cells of every (b, n): the ``h * w`` candidates ``(peak, where)`` ordered by value descending, then by flat index
+    ascending (``naf_peaks_topk``: torch promises no tie rule on the device).  One candidate per low-res cell -- a non-maximum suppression
+    at the cell grid, not the k best pixels; ``k = 1`` is the global maximum of the cosine map with the lowest flat index among ties.
+    ``peak`` fp32 and ``where`` int32, both [B, N, h, w] (``xna_cos_peaks``'s; any strides, channels-last ones are read in place);
+    1 <= k <= min(h * w, 64).  Returns ``(values [B, N, k] fp32, index [B, N, k] int32)``."""
+    _gpu(peak, "peak")
+    _gpu(where, "where")
+    if peak.dim() != 4 or peak.shape != where.shape or peak.dtype != torch.float32 or where.dtype != torch.int32:
+        raise ValueError(f"peaks_topk: peak must be fp32 and where int32, both [B, N, h, w]; got {tuple(peak.shape)} {peak.dtype} / {tuple(where.shape)} {where.dtype}")
+    B, N, h, w = peak.shape
+    k = int(k)
+    if not 1 <= k <= min(h * w, 64):
+        raise ValueError(f"peaks_topk: k must be in 1 .. min(h * w, 64) = {min(h * w, 64)}, got {k}")
+    values = torch.empty((B, N, k), dtype=torch.float32, device=peak.device)
+    index = torch.empty((B, N, k), dtype=torch.int32, device=peak.device)
+    if B == 0 or N == 0:
+        return values, index
+
+    def cells(t):   # [B, N, h, w] -> a view [B, h * w, N] with the channel axis contiguous, or a copy that is
+        t = t.permute(0, 2, 3, 1)
+        if t.stride(3) != 1 or t.stride(1) != w * t.stride(2):
+            t = t.contiguous()
+        return t, (C.c_int64 * 2)(t.stride(0), t.stride(2))
+    pk, ps = cells(peak)
+    wh, ws = cells(where)
+    lib = _lib.load()
+    with torch.cuda.device(peak.device), _Timed("peaks_topk"):
+        rc = lib.naf_peaks_topk(pk.data_ptr(), wh.data_ptr(), values.data_ptr(), index.data_ptr(), B, N, h * w, k, ps, ws, _stream(peak))
+    _lib.check(rc, "naf_peaks_topk")
+    return values, index
+
+
 def head_dlogits_channels(n_out: int) -> int:
     """Channels of a ``dlogits`` row for ``n_out`` classes: the value width the cell backward serves that holds Npad (``_BWD_DV``)."""
     npad = head_npad(n_out)
