@@ -1521,6 +1521,54 @@ int naf_xna_cos_peaks_fwd(const naf_xna_cos_peaks_args* a, naf_stream_t stream);
 int naf_peaks_topk(const float* peak, const int32_t* where, float* values, int32_t* index, int32_t B, int32_t N, int32_t n_cells, int32_t k,
                    const int64_t peak_stride[2], const int64_t where_stride[2], naf_stream_t stream);
 
+/* ---- k-means step: assign and accumulate in one launch (added after the peak-search entries; detect by symbol) ------------
+ * One Lloyd iteration over the upsampled features f(px) without writing them.  Both halves are entries above:
+ *     label(px)     = argmin_k |f(px) - c_k|^2 = argmax_k (c_k . f(px) - |c_k|^2 / 2)      a linear head with a bias and an argmax
+ *     A[b, g, k, j] = sum_px [label(px) = k] * P_g[px, j],   mass[b, k] = #{px: label(px) = k}   mask pooling under one-hot masks
+ * followed by naf_maskpool_apply(A, v_lr, ..., mean = 0) / mass on the low-res grid.  naf_xna_kmeans_fwd runs both in one cell kernel:
+ * per round of 256 pixels it runs naf_xna_head_ce_fwd's head loop and argmax, keeps the 256 labels in LDS, and runs
+ * naf_xna_maskpool_fwd's head loop with the mask operand built in registers from those labels.  No label map, no one-hot tensor.
+ *   q, k_lr   exactly as in naf_xna_head_args (bf16, strides {b, head, y, x}, last dim contiguous, Dq = 64), rope_tab_* as there
+ *   pv_lr     device bf16 [B, heads, h, w, Kpad] (Kpad = K rounded up to 16), as naf_xna_head_args.pv_lr: the centroids projected on the
+ *             low-res features, PV_g[j, k] = c_k[g] . V_g[j]; channels K .. Kpad-1 are read and must be finite
+ *   bias      device float [B, K]: row b starts bias_stride_b elements after row b-1 (0: one row for all images); or NULL
+ *   labels    device uint8 [B, Ho, Wo] (labels_stride {b, y, x}), or NULL: the label map is an optional output
+ *   A, mass   device float [B, heads, K, h, w] and [B, K], dense, as naf_xna_maskpool_args
+ *   workspace device, naf_xna_kmeans_workspace_bytes(a) bytes, 16-byte aligned (naf_xna_maskpool_fwd's per-cell partials)
+ * Two bit-identities define the entry (tests/test_gpu_kmeans.py):
+ *   (1) labels are, bit for bit, what naf_xna_head_ce_fwd stores for image b with (pv_lr[b], bias[b]): the lowest index among equal maxima;
+ *   (2) A and mass are, bit for bit, what naf_xna_maskpool_fwd returns for the NAF_MASK_U8 masks [label == k]; mass is an exact count.
+ * A pixel counts in at most one cluster.  No float atomics anywhere: two launches on the same inputs give the same bits.
+ * Served: exactly what naf_xna_maskpool_fwd serves, 1 <= K <= 64, pv_lr laid out as naf_xna_head_fwd asks.  naf_xna_kmeans_select answers
+ * as naf_xna_head_select does: NAF_XNA_HEAD_FUSED, -NAF_ERR_INVALID for arguments no kernel could serve, -NAF_ERR_UNSUPPORTED (with
+ * naf_last_error) for a valid request outside the list -- the caller then composes the two entries above.  A pure host-side query.
+ * Caller-owned memory and stream; capturable.  The struct must be zero-initialised (reserved fields). */
+typedef struct naf_xna_kmeans_args {
+    const void* q;
+    const void* k_lr;
+    const void* pv_lr;
+    const float* bias;
+    uint8_t* labels;
+    float* A;
+    float* mass;
+    void* workspace;
+    size_t workspace_bytes;
+    const float* rope_tab_y;
+    const float* rope_tab_x;
+    int32_t B, heads, Ho, Wo, h, w, Dq, K, ky, kx;
+    int32_t path; /* naf_xna_head_path */
+    float scale;
+    int64_t bias_stride_b;
+    int64_t q_stride[4];
+    int64_t k_stride[4];
+    int64_t pv_stride[4];
+    int64_t labels_stride[3];
+    int64_t reserved[2]; /* must be 0 */
+} naf_xna_kmeans_args;
+int naf_xna_kmeans_select(const naf_xna_kmeans_args* a);
+size_t naf_xna_kmeans_workspace_bytes(const naf_xna_kmeans_args* a);
+int naf_xna_kmeans_fwd(const naf_xna_kmeans_args* a, naf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

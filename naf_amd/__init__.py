@@ -10,7 +10,7 @@ attention filtering forward, behind the reference's own API (valeoai/NAF: src/mo
 
 Kernels live in naf_amd/csrc (HIP, C ABI in include/naf_hip.h); build with ``python -m naf_amd.build``.
 """
-from .model import NAF, CrossAttention, GraphedForward, Guidance, ImageEncoder, Match, Peaks, PointQuery, RoPE  # noqa: F401
+from .model import NAF, CrossAttention, GraphedForward, Guidance, ImageEncoder, KMeans, Match, Peaks, PointQuery, RoPE  # noqa: F401
 from .ops import ConfusionMetrics, FrameFeatures, confusion_metrics, pack_frame, propagate_labels  # noqa: F401
 from .ops import DenoisingLoss, denoising_loss, denoising_metrics  # noqa: F401
 from .ops import DavisJF, davis_jf, davis_statistics  # noqa: F401
@@ -18,7 +18,7 @@ from .ops import VideoTracker, labels_to_masks, masks_to_labels, nearest_index_t
 from .ops import PrepView, davis_frame_views, lr_image_size, prepare_views, probing_views, training_views  # noqa: F401
 from .feature_pca import FeaturePCA, pca  # noqa: F401
 
-__all__ = ["NAF", "CrossAttention", "GraphedForward", "Guidance", "PointQuery", "Peaks", "Match", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics",
+__all__ = ["NAF", "CrossAttention", "GraphedForward", "Guidance", "PointQuery", "Peaks", "Match", "KMeans", "ImageEncoder", "RoPE", "ConfusionMetrics", "confusion_metrics",
            "FrameFeatures", "pack_frame", "propagate_labels", "DenoisingLoss", "denoising_loss", "denoising_metrics",
            "FeaturePCA", "pca", "DavisJF", "davis_jf", "davis_statistics",
            "VideoTracker", "labels_to_masks", "masks_to_labels", "nearest_index_table",

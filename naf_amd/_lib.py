@@ -119,6 +119,19 @@ class XnaMaskPoolArgs(C.Structure):
     ]
 
 
+class XnaKmeansArgs(C.Structure):
+    """naf_xna_kmeans_args (added after the peak-search entries, detected by symbol): one k-means step, assign and accumulate in one launch."""
+    _fields_ = [
+        ("q", C.c_void_p), ("k_lr", C.c_void_p), ("pv_lr", C.c_void_p), ("bias", C.c_void_p), ("labels", C.c_void_p),
+        ("A", C.c_void_p), ("mass", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("rope_tab_y", C.c_void_p), ("rope_tab_x", C.c_void_p),
+        ("B", C.c_int32), ("heads", C.c_int32), ("Ho", C.c_int32), ("Wo", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+        ("Dq", C.c_int32), ("K", C.c_int32), ("ky", C.c_int32), ("kx", C.c_int32),
+        ("path", C.c_int32), ("scale", C.c_float), ("bias_stride_b", C.c_int64),
+        ("q_stride", I64x4), ("k_stride", I64x4), ("pv_stride", I64x4), ("labels_stride", I64x3), ("reserved", C.c_int64 * 2),
+    ]
+
+
 class XnaMSEArgs(C.Structure):
     """naf_xna_mse_args (added after the PCA entries, detected by symbol): naf_xna_args plus the regression target of the training objective."""
     _fields_ = [
@@ -430,6 +443,9 @@ SIGNATURES = {
     "naf_xna_cos_peaks_fwd": (C.c_int, [C.POINTER(XnaCosPeaksArgs), C.c_void_p]),
     "naf_peaks_topk": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_void_p]),
+    "naf_xna_kmeans_select": (C.c_int, [C.POINTER(XnaKmeansArgs)]),
+    "naf_xna_kmeans_workspace_bytes": (C.c_size_t, [C.POINTER(XnaKmeansArgs)]),
+    "naf_xna_kmeans_fwd": (C.c_int, [C.POINTER(XnaKmeansArgs), C.c_void_p]),
     "naf_propagate_select": (C.c_int, [C.POINTER(PropagateArgs)]),
     "naf_propagate_fwd": (C.c_int, [C.POINTER(PropagateArgs), C.c_void_p]),
     "naf_propagate_plan": (C.c_int, [C.POINTER(PropagateArgs), C.POINTER(C.c_int32)]),

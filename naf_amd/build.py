@@ -46,6 +46,7 @@ INSTANCES = {
     "xna_head_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_cos_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_pool_inst.hip": [(k, None) for k in _WINDOWS],
+    "xna_kmeans_inst.hip": [(k, None) for k in _WINDOWS],
     "xna_bwd_inst.hip": [(k, None) for k in _WINDOWS],
 }
 

@@ -603,6 +603,46 @@ int naf_maskpool_apply(const float* A, const void* v, const float* mass, float* 
     return naf_launch_maskpool_apply(A, v, mass, pooled, B, heads, K, C, hw, v_stride, mean, static_cast<hipStream_t>(stream));
 }
 
+// ---- k-means step: the head kernel's argmax and mask pooling under its labels in one launch (after the peak-search entries) ----
+static int xna_kmeans_validate(const naf_xna_kmeans_args* a) {
+    const char* who = "naf_xna_kmeans_fwd";
+    NAF_REQUIRE(a != nullptr, "%s: args is NULL", who);
+    NAF_REQUIRE(a->q && a->k_lr && a->pv_lr && a->A && a->mass && a->workspace, "%s: NULL tensor pointer", who);
+    const int rc = xna_geometry_validate(who, a, 1);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(a->K >= 1, "%s: K must be at least 1, got %d", who, a->K);
+    NAF_REQUIRE(a->path == NAF_XNA_HEAD_AUTO || a->path == NAF_XNA_HEAD_FUSED, "%s: path %d", who, a->path);
+    NAF_REQUIRE((a->rope_tab_y == nullptr) == (a->rope_tab_x == nullptr), "%s: rope_tab_y and rope_tab_x must be given together", who);
+    NAF_REQUIRE(a->pv_stride[3] >= ((a->K + 15) & ~15), "%s: pv_lr rows must hold K rounded up to 16 channels (x stride %lld, K %d)", who,
+                (long long)a->pv_stride[3], a->K);
+    NAF_REQUIRE(a->bias == nullptr || a->bias_stride_b == 0 || a->bias_stride_b >= a->K, "%s: bias_stride_b %lld is neither 0 nor at least K %d", who,
+                (long long)a->bias_stride_b, a->K);
+    NAF_REQUIRE(a->bias == nullptr || naf_aligned(a->bias, 4), "%s: bias not 4-byte aligned", who);
+    NAF_REQUIRE(a->labels == nullptr || a->labels_stride[2] >= 1, "%s: labels x stride %lld", who, (long long)a->labels_stride[2]);
+    NAF_REQUIRE(a->reserved[0] == 0 && a->reserved[1] == 0, "%s: reserved fields must be zero", who);
+    return NAF_OK;
+}
+
+int naf_xna_kmeans_select(const naf_xna_kmeans_args* a) {
+    int rc = xna_kmeans_validate(a);
+    if (rc == NAF_OK) rc = naf_xna_kmeans_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
+}
+
+size_t naf_xna_kmeans_workspace_bytes(const naf_xna_kmeans_args* a) {
+    if (a == nullptr || a->B <= 0 || a->heads <= 0 || a->h <= 0 || a->w <= 0 || a->K <= 0 || a->ky <= 0 || a->kx <= 0) return 0;
+    return naf_xna_pool_ws(a->B, a->heads, a->h, a->w, a->ky * a->kx, a->K, nullptr);
+}
+
+int naf_xna_kmeans_fwd(const naf_xna_kmeans_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_kmeans_select(a);
+    if (sel < 0) return -sel;
+    const size_t need = naf_xna_kmeans_workspace_bytes(a);
+    NAF_REQUIRE(a->workspace_bytes >= need, "naf_xna_kmeans_fwd: workspace of %zu bytes, %zu needed", a->workspace_bytes, need);
+    NAF_REQUIRE(naf_aligned(a->workspace, 16), "naf_xna_kmeans_fwd: workspace must be 16-byte aligned");
+    return naf_launch_xna_kmeans(a, xna_scale(a->scale, a->Dq), static_cast<hipStream_t>(stream));
+}
+
 // ---- peak search on the scaled cosines (after the mask-pooling entries) ----
 static int xna_cos_peaks_validate(const naf_xna_cos_peaks_args* c) {
     const char* who = "naf_xna_cos_peaks";

@@ -92,6 +92,10 @@ int naf_xna_maskpool_eligible(const naf_xna_maskpool_args* a);                  
 size_t naf_xna_maskpool_ws(const naf_xna_maskpool_args* a, size_t* mass_offset);        // xna_pool.hip: workspace bytes, offset of the per-cell masses
 int naf_launch_maskpool_apply(const float* A, const void* v, const float* mass, float* pooled, int B, int heads, int K, int C, int hw,
                               const int64_t* v_stride, int mean, hipStream_t s);        // xna_pool.hip
+size_t naf_xna_pool_ws(int B, int heads, int h, int w, int nslot, int K, size_t* mass_offset);   // xna_pool.hip: the per-cell partials of both pooling families
+int naf_launch_xna_pool_mass(const float* pmass, float* mass, int B, int K, int kpad, int cells, hipStream_t s);   // xna_pool.hip: mass[b, k] from the per-cell masses
+int naf_launch_xna_kmeans(const naf_xna_kmeans_args* a, float scale, hipStream_t s);   // xna_kmeans.hip: k-means step (cell kernel, gather, mass)
+int naf_xna_kmeans_eligible(const naf_xna_kmeans_args* a);                          // xna_kmeans.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
 int naf_tile_span(int L_out, int L_in, int k);                                  // xna_rows.hip: low-res columns under 16 consecutive queries
 // `sg` (0.4.3): the gradient of the scores (naf_xna_bwd_scores); nullptr = the plain backward, the same launches as before
 int naf_launch_xna_bwd(const naf_xna_bwd_args* a, float scale, hipStream_t s, const naf_xna_bwd_scores_args* sg = nullptr);   // xna_bwd.hip

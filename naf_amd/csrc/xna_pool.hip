@@ -33,11 +33,15 @@ int naf_xna_maskpool_eligible(const naf_xna_maskpool_args* a) {
     return NAF_OK;
 }
 
-size_t naf_xna_maskpool_ws(const naf_xna_maskpool_args* a, size_t* mass_offset) {
-    const size_t kpad = (size_t)((a->K + 15) & ~15), cells = (size_t)a->B * (size_t)a->h * (size_t)a->w;
-    const size_t part = cells * (size_t)a->heads * (size_t)(a->ky * a->kx) * kpad * sizeof(float);
+// (shared with the k-means step, xna_kmeans.hip, whose cell kernel writes the same partials)
+size_t naf_xna_pool_ws(int B, int heads, int h, int w, int nslot, int K, size_t* mass_offset) {
+    const size_t kpad = (size_t)((K + 15) & ~15), cells = (size_t)B * (size_t)h * (size_t)w;
+    const size_t part = cells * (size_t)heads * (size_t)nslot * kpad * sizeof(float);
     if (mass_offset != nullptr) *mass_offset = part;
     return part + cells * kpad * sizeof(float);
+}
+size_t naf_xna_maskpool_ws(const naf_xna_maskpool_args* a, size_t* mass_offset) {
+    return naf_xna_pool_ws(a->B, a->heads, a->h, a->w, a->ky * a->kx, a->K, mass_offset);
 }
 
 // mass[b, k] = sum over the cells of pmass[b][cell][k]: one workgroup per (b, k), thread t adds cells t, t + 256, ... in ascending
@@ -54,6 +58,11 @@ __global__ __launch_bounds__(256) void xna_pool_mass_kernel(const float* __restr
         __syncthreads();
     }
     if (threadIdx.x == 0) mass[blockIdx.x] = red[0];
+}
+
+int naf_launch_xna_pool_mass(const float* pmass, float* mass, int B, int K, int kpad, int cells, hipStream_t s) {
+    hipLaunchKernelGGL(xna_pool_mass_kernel, dim3((unsigned)(B * K)), dim3(256), 0, s, pmass, mass, K, kpad, cells);
+    return naf_check_launch("xna_pool_mass_kernel");
 }
 
 int naf_launch_xna_maskpool(const naf_xna_maskpool_args* a, float scale, hipStream_t s) {
@@ -80,8 +89,7 @@ int naf_launch_xna_maskpool(const naf_xna_maskpool_args* a, float scale, hipStre
         default: naf_set_error("naf_xna_maskpool_fwd: kernel size %d has no instantiation", a->ky);
     }
     if (rc != NAF_OK) return rc;
-    hipLaunchKernelGGL(xna_pool_mass_kernel, dim3((unsigned)(a->B * a->K)), dim3(256), 0, s, p.pmass, a->mass, a->K, p.kpad, a->h * a->w);
-    return naf_check_launch("xna_pool_mass_kernel");
+    return naf_launch_xna_pool_mass(p.pmass, a->mass, a->B, a->K, p.kpad, a->h * a->w, s);
 }
 
 // pooled[b, k, c] = sum_j A[b, g(c), k, j] * v[b, c, j]: one wave per output, lane l takes j = l, l + 64, ... in ascending order

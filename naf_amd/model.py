@@ -721,6 +721,24 @@ Match.__doc__ = """Result of ``NAF.match``: per source point its k best location
 int64; ``distance`` [P] fp32 with ``mutual=True`` (the pixel distance between the point and where its best match leads back to), else None."""
 
 
+class KMeans(collections.namedtuple("KMeans", ["labels", "centroids", "counts", "shift"])):
+    """Result of ``NAF.kmeans``: ``labels`` int64 [B, Ho, Wo], every pixel's cluster under the returned centroids; ``centroids`` fp32 [B, K, C]
+    ([K, C] with ``per_image=False``); ``counts`` fp32 [B, K], the pixels per cluster (exact integers); ``shift`` fp32 [iters, B], the largest
+    centroid movement ``max_k |c_new - c|`` of every iteration: the caller's convergence record."""
+    __slots__ = ()
+
+    def head(self, b: int = 0):
+        """``(weight [K, C], bias [K])`` of image ``b``'s centroids as a linear head: ``naf(g, feats, size, head=r.head(), predict=True)``
+        labels the pixels of other images by their nearest centroid (``argmax_k c_k . f - |c_k|^2 / 2``); on the clustered batch itself
+        row ``b`` of that call is ``labels[b]``, bit for bit (``NAF.kmeans`` makes its final assignment this way)."""
+        return _kmeans_head(self.centroids if self.centroids.dim() == 2 else self.centroids[b])
+
+
+def _kmeans_head(c: torch.Tensor):
+    """Centroids [K, C] as a linear head: ``argmax_k c_k . f - |c_k|^2 / 2`` is the nearest centroid."""
+    return c, -0.5 * (c * c).sum(dim=1)
+
+
 def _lib_last_error() -> str:
     return ops._lib.last_error()
 
@@ -1541,6 +1559,157 @@ class NAF(nn.Module):
                 by, bx = back.y[bsel, rows, 0], back.x[bsel, rows, 0]
                 distance = ((by - pts[:, -2]).float().square() + (bx - pts[:, -1]).float().square()).sqrt()
         return Match(scores, y, x, distance)
+
+    # ---- k-means on the upsampled features ---------------------------------------------------------------------------------------
+    def kmeans_path(self, features, output_size, k: int) -> str:
+        """The route ``kmeans(..., path="auto")`` takes for these features, output size and cluster count: "fused" or "composed".  A
+        host-side query (``ops.xna_kmeans_select``); the reason for "composed" is the second element of ``_kmeans_reason``."""
+        return "composed" if self._kmeans_reason(features, (int(output_size[0]), int(output_size[1])), int(k)) is not None else "fused"
+
+    def _kmeans_reason(self, features, size, K: int):
+        """Why the one-launch step does not take the call, or None."""
+        heads, ksz, enc = self.upsampler.num_heads, self.upsampler.kernel_size, self.image_encoder
+        B, C = features.shape[0], features.shape[1]
+        if K > ops.KMEANS_FUSED_MAX:
+            return f"the fused k-means step takes at most {ops.KMEANS_FUSED_MAX} clusters, got {K}"
+        if features.dtype != torch.bfloat16:
+            return f"the fused k-means route reads bfloat16 features, got {features.dtype}"
+        if C % heads or enc.out_channels % heads:
+            return f"feature channels {C} / guidance channels {enc.out_channels} not divisible by {heads} heads"
+        probe = torch.empty((max(B, 1), size[0], size[1], heads, enc.out_channels // heads), dtype=torch.bfloat16, device="meta").permute(0, 3, 1, 2, 4)
+        if ops.xna_kmeans_select(probe, features.shape[-2:], K, ksz) != "fused":
+            return _lib_last_error() or "naf_xna_kmeans_select refuses the geometry"
+        return None
+
+    def kmeans(self, image, features, output_size, k, *, iters=10, init="points", generator=None, per_image=True, path="auto") -> KMeans:
+        """K-means (Lloyd) over the upsampled features of one call, without writing them: ``r = naf.kmeans(image_or_guidance, feats, (Ho, Wo), k)``
+        returns ``KMeans(labels, centroids, counts, shift)`` -- an unsupervised segmentation, the companion picture of the PCA view.
+
+        One iteration is, with ``c`` the centroids [B, K, C] fp32,
+
+            pv5, bias, _ = ops.project_kmeans_values(c, feats, heads)               # centred: argmax_k c_k . f - |c_k|^2 / 2
+            labels       = the head kernel's argmax of (pv5[b], bias[b]) per image  # the lowest index among equal maxima
+            A, mass      = ops.xna_mask_pool(q, k, labels == arange(K))             # the attention summed under the one-hot masks
+            sums         = ops.mask_pool_apply(A, feats, None, "sum")
+            c_new        = where(mass > 0, sums / mass, c)                          # an empty cluster keeps its centroid
+            shift[i]     = max_k |c_new - c|
+
+        which is also the ``path="composed"`` arm.  ``path="auto"`` runs labels and accumulation of an iteration in ONE launch
+        (``ops.xna_kmeans_step``; no label map, no one-hot tensor) where ``naf_xna_kmeans_select`` grants the geometry, k <= 64 and the
+        features are bf16 -- bit for bit the same labels, centroids, counts and shift -- and the composition otherwise: 64 < k <= 256,
+        fp16 / fp32 features, geometries the head route composes (those materialise the feature map).  ``"fused"`` insists (NafHipError
+        with the library's reason).  After ``iters`` updates one more labels-only launch per image assigns the pixels to the final
+        centroids through ``r.head(b)`` -- the centroids as a plain linear head, the call ``naf(g, feats, size, head=r.head(b),
+        predict=True)`` makes, so that call returns ``r.labels[b]`` bit for bit: the returned ``labels``; ``counts`` are their masses.  ``iters`` is fixed: there is no tolerance and no early stop (it would
+        synchronise with the host); ``shift`` is the record to read afterwards.  ``init="points"`` draws k distinct pixels per image with
+        ``torch.randperm`` on the host from ``generator`` (default: a fixed seed) and takes their features (``query``); ``init`` may also
+        be a tensor [K, C] or [B, K, C].  ``per_image=False`` shares one set of centroids: sums and masses are added over the batch before
+        the division.  The image is encoded once for all iterations; a ``Guidance`` is accepted.  Inference only (``no_grad``).
+        k > 256, k < 1 and iters < 0 raise ValueError before any device work.
+        Not offered: a gradient, cosine / spherical k-means, k-means++ seeding, ``capture()``."""
+        who = "kmeans"
+        if path not in ("auto", "fused", "composed"):
+            raise ValueError(f"{who}: path must be 'auto', 'fused' or 'composed', got {path!r}")
+        K, iters_ = int(k), int(iters)
+        if K != k or K < 1 or K > ops.KMEANS_MAX:
+            raise ValueError(f"{who}: k must be an integer in 1 .. {ops.KMEANS_MAX}, got {k!r}")
+        if iters_ != iters or iters_ < 0:
+            raise ValueError(f"{who}: iters must be a non-negative integer, got {iters!r}")
+        if not isinstance(features, torch.Tensor) or features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
+            raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(getattr(features, 'shape', ()))}")
+        ho, wo = int(output_size[0]), int(output_size[1])
+        B, C = int(features.shape[0]), int(features.shape[1])
+        heads, ksz = self.upsampler.num_heads, self.upsampler.kernel_size
+        if B < 1:
+            raise ValueError(f"{who}: an empty batch has nothing to cluster")
+        if C % heads:
+            raise ValueError(f"feature channels {C} not divisible by {heads} heads")
+        if isinstance(init, torch.Tensor):
+            if tuple(init.shape) not in ((K, C), (B, K, C)) or not init.is_floating_point():
+                raise ValueError(f"{who}: init must be 'points' or a floating-point tensor [K, C] = ({K}, {C}) or [B, K, C], got {tuple(init.shape)} {init.dtype}")
+            if not per_image and init.dim() == 3:
+                raise ValueError(f"{who}: per_image=False shares one set of centroids: init must be [K, C]")
+        elif init != "points":
+            raise ValueError(f"{who}: init must be 'points' or a tensor, got {init!r}")
+        elif K > ho * wo:
+            raise ValueError(f"{who}: cannot draw {K} distinct pixels from {ho}x{wo}")
+        if features.dtype not in (torch.bfloat16, torch.float16, torch.float32):
+            raise TypeError(f"{who}: features must be bfloat16, float16 or float32, got {features.dtype}")
+        if not (image.is_cuda and features.is_cuda) or (isinstance(init, torch.Tensor) and not init.is_cuda):
+            raise _rocm_only(image=image, features=features, **({"init": init} if isinstance(init, torch.Tensor) else {}))
+        reason = self._kmeans_reason(features, (ho, wo), K)
+        if path == "fused" and reason is not None:
+            raise ops._lib.NafHipError(f"naf.kmeans(..., path='fused'): {reason}")
+        fused = path != "composed" and reason is None
+        dev, lr = features.device, tuple(features.shape[-2:])
+        with torch.no_grad():
+            g = image if isinstance(image, Guidance) else self.guide(image)
+            g.check(self)
+            if isinstance(init, torch.Tensor):
+                c = init.to(device=dev, dtype=torch.float32)
+                c = (c[None].expand(B, K, C) if c.dim() == 2 else c).contiguous()
+            else:
+                gen = generator if generator is not None else torch.Generator().manual_seed(0)
+                nb = B if per_image else 1
+                flat = torch.stack([torch.randperm(ho * wo, generator=gen)[:K] for _ in range(nb)])          # host
+                pts = torch.stack([torch.arange(nb)[:, None].expand(nb, K), flat // wo, flat % wo], dim=2).reshape(nb * K, 3)
+                c = self.query(g, pts, features=features, output_size=(ho, wo), weights=None).features.reshape(nb, K, C)
+                c = c.expand(B, K, C).contiguous()
+            # can the (un-rotated guidance, tables) form serve every launch of the route?
+            if fused:
+                fusable = lambda q5, tabs: ops.xna_kmeans_select(q5, lr, K, ksz, rope_tables=tabs) == "fused" and \
+                    ops.xna_head_select(q5[:1], lr, K, ksz, rope_tables=tabs) == "fused"
+            else:
+                fusable = lambda q5, tabs: ops.xna_head_select(q5[:1], lr, K, ksz, rope_tables=tabs) == "fused" and \
+                    ops.xna_mask_pool_select(q5, lr, min(K, ops.MASK_POOL_CHUNK), ksz, rope_tables=tabs) == "fused"
+            q5, k5, tabs = self.guidance_qk(g, lr, (ho, wo), fusable=fusable)
+            pooled_ok = fused or ops.xna_mask_pool_select(q5, lr, min(K, ops.MASK_POOL_CHUNK), ksz, rope_tables=tabs) == "fused"
+            fmap = None if pooled_ok else self.forward(g, features, (ho, wo)).float()      # geometries the head route composes
+            scale = self.upsampler.scale
+            arange = torch.arange(K, device=dev)
+
+            def assign(pv5, bias):
+                """The head kernel's labels per image (each image has its own bias row)."""
+                return torch.cat([ops.xna_head_objective(q5[b:b + 1], k5[b:b + 1], pv5[b:b + 1], bias[b], ksz, n_out=K, want_labels=True,
+                                                         scale=scale, rope_tables=tabs)[1] for b in range(B)])
+
+            def sums_of(A):
+                if features.dtype == torch.bfloat16:
+                    return ops.mask_pool_apply(A, features, None, "sum")
+                return torch.einsum("bgkj,bgdj->bkgd", A.flatten(3), features.float().reshape(B, heads, C // heads, -1)).reshape(B, K, C)
+
+            shift = torch.empty((iters_, B), dtype=torch.float32, device=dev)
+            for it in range(iters_):
+                pv5, bias, _ = ops.project_kmeans_values(c, features, heads)
+                with ops._Timed("attention"):
+                    if fused:
+                        _, A, mass = ops.xna_kmeans_step(q5, k5, pv5, bias, ksz, scale=scale, rope_tables=tabs)
+                        sums = sums_of(A)
+                    else:
+                        onehot = assign(pv5, bias)[:, None] == arange[None, :, None, None]
+                        if pooled_ok:
+                            A, mass = ops.xna_mask_pool(q5, k5, onehot, ksz, scale=scale, rope_tables=tabs)
+                            sums = sums_of(A)
+                        else:
+                            sums, mass = ops.mask_pool_from_features(fmap, onehot, "sum", return_mass=True)
+                        del onehot
+                if not per_image:
+                    sums, mass = sums.sum(dim=0, keepdim=True).expand(B, K, C), mass.sum(dim=0, keepdim=True).expand(B, K)
+                c_new = torch.where(mass[..., None] > 0, sums / mass[..., None], c)
+                shift[it] = (c_new - c).norm(dim=2).amax(dim=1)
+                c = c_new
+            # the final assignment is the call ``KMeans.head`` documents -- the centroids as a plain linear head on the features as they
+            # are -- so that ``naf(g, feats, size, head=r.head(b), predict=True)[b]`` IS ``r.labels[b]``, bit for bit
+            cents = c if per_image else c[:1]
+            labels = []
+            for b in range(cents.shape[0]):
+                pvh, bh = ops.project_head_values(*_kmeans_head(cents[b]), features, heads)
+                sl = slice(b, b + 1) if per_image else slice(None)
+                labels.append(ops.xna_head_objective(q5[sl], k5[sl], pvh[sl], bh, ksz, n_out=K, want_labels=True, scale=scale, rope_tables=tabs)[1])
+            labels = torch.cat(labels)
+            counts = torch.zeros((B, 256), dtype=torch.float32, device=dev)
+            counts.scatter_add_(1, labels.reshape(B, -1).long(), torch.ones((B, ho * wo), dtype=torch.float32, device=dev))
+            return KMeans(labels.long(), c if per_image else c[0].clone(), counts[:, :K].contiguous(), shift)
 
     def _forward_regress(self, image, features, output_size, regress, regress_path):
         """``forward(..., regress=regress)``: see ``forward``."""

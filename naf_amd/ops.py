@@ -1501,6 +1501,131 @@ def mask_attention_from_scores(scores: torch.Tensor, masks: torch.Tensor, lr_siz
 
 
 # ---- ... and a cosine head: scaled cosines between the upsampled feature and N embeddings (open vocabulary, heat maps) -----------
+# ---- k-means on the upsampled features: one Lloyd step, assign and accumulate in one launch ---------------------------------------
+KMEANS_FUSED_MAX = 64         # clusters naf_xna_kmeans_fwd takes (one launch; above it the step is composed)
+KMEANS_MAX = 256              # clusters the composed step takes (the head kernel's uint8 label map)
+
+
+def project_kmeans_values(centroids: torch.Tensor, features: torch.Tensor, heads: int):
+    """The low-res half of the k-means assignment ``argmin_k |f - c_k|^2 = argmax_k (c_k . f - |c_k|^2 / 2)``: a linear head whose weight
+    rows are the centroids and whose bias is minus half their squared norm.
+
+    centroids [K, C] or [B, K, C], features [B, C, h, w] -> ``(pv5, bias, mean)``: pv5 bf16 [B, heads, h, w, Kpad] (Kpad = K rounded up to
+    16, zero pad channels) as ``project_head_values`` lays it out, bias fp32 [B, K], mean fp32 [B, C].  The per-channel mean ``mu`` of the
+    low-res features is subtracted from the features AND the centroids before projecting, and ``bias = -|c - mu|^2 / 2``: the attention
+    weights of a head sum to one, so ``(c - mu) . (f - mu) - |c - mu|^2 / 2`` differs from ``c . f - |c|^2 / 2`` by a term without k and
+    the argmax is the same, while the magnitudes that are rounded to bf16 shrink.  Pure torch, works on CPU tensors."""
+    who = "project_kmeans_values"
+    if features.dim() != 4:
+        raise ValueError(f"{who}: features must be [B, C, h, w], got {tuple(features.shape)}")
+    B, Cc, h, w = features.shape
+    if centroids.dim() == 2:
+        centroids = centroids[None].expand(B, -1, -1)
+    if centroids.dim() != 3 or centroids.shape[0] != B or centroids.shape[2] != Cc or centroids.shape[1] < 1:
+        raise ValueError(f"{who}: centroids must be [K, C] or [B, K, C] = ([{B},] K >= 1, {Cc}), got {tuple(centroids.shape)}")
+    if heads <= 0 or Cc % heads:
+        raise ValueError(f"{who}: feature channels {Cc} not divisible by {heads} heads")
+    K, Dv = int(centroids.shape[1]), Cc // heads
+    f = features.float()
+    mean = f.mean(dim=(2, 3))
+    cc = centroids.float() - mean[:, None, :]
+    fc = f - mean[:, :, None, None]
+    pv = torch.einsum("bkgd,bgdhw->bghwk", cc.reshape(B, K, heads, Dv), fc.reshape(B, heads, Dv, h, w))
+    pad = head_npad(K) - K
+    if pad:
+        pv = torch.nn.functional.pad(pv, (0, pad))
+    bias = -0.5 * (cc * cc).sum(dim=2)
+    return pv.to(torch.bfloat16), bias.contiguous(), mean
+
+
+def xna_kmeans_select(q: torch.Tensor, lr_size, k: int, kernel_size, *, rope_tables=None) -> str:
+    """Which route a k-means step takes for these shapes: "fused" (``naf_xna_kmeans_select`` grants the one-launch kernel for ``k`` clusters)
+    or "composed" (head-kernel labels, then mask pooling under their one-hot masks).  ``q``: the 5-D [B, heads, Ho, Wo, Dq] bf16 queries
+    -- with ``rope_tables`` the un-rotated guidance.  A host-side query: nothing is launched or read, CPU / meta tensors do.  Invalid
+    arguments raise ValueError; the library's reason for "composed" is in ``naf_last_error``."""
+    if q.dtype != torch.bfloat16 or q.dim() != 5 or q.stride(4) != 1:
+        return "composed"
+    lib = _lib.load()
+    ky, kx = _ksize(kernel_size)
+    _, heads, Ho, Wo, Dq = q.shape
+    h, w = int(lr_size[0]), int(lr_size[1])
+    kpad = head_npad(max(int(k), 1))
+    a = _lib.XnaKmeansArgs()
+    a.q = a.k_lr = a.pv_lr = a.A = a.mass = a.workspace = q.data_ptr() or 16      # shape / alignment query only: nothing is dereferenced
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = rope_tables[0].data_ptr(), rope_tables[1].data_ptr()
+    _fill_geometry(a, q, None, h, w, ky, kx, None)
+    a.K, a.path = int(k), _lib.XNA_HEAD_AUTO
+    a.k_stride = _dense5(h, w, heads, Dq)
+    a.pv_stride = I64x4(heads * h * w * kpad, h * w * kpad, w * kpad, kpad)
+    sel = lib.naf_xna_kmeans_select(C.byref(a))
+    if sel == -1:
+        _lib.check(1, "naf_xna_kmeans_select")
+    return "fused" if sel == _lib.XNA_HEAD_FUSED else "composed"
+
+
+def xna_kmeans_step(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, bias: Optional[torch.Tensor], kernel_size, *,
+                    k: Optional[int] = None, want_labels: bool = False, scale: Optional[float] = None, rope_tables=None):
+    """One k-means step on the attention of ``xna_forward`` in one launch (``naf_xna_kmeans_fwd``): every pixel is labelled
+    ``argmax_k (bias[b, k] + sum over heads and window of P . pv_lr)`` -- the lowest index among equal maxima -- and the attention is summed
+    under those labels:
+
+        ``A[b, g, k, j] = sum_px [label(px) = k] * P_g[px, j]``  fp32 [B, heads, K, h, w],  ``mass[b, k]``  fp32 [B, K], an exact count
+
+    q [B, heads, Ho, Wo, Dq] and k_lr [B, heads, h, w, Dq] bf16 as for ``xna_mask_pool``, pv_lr bf16 [B, heads, h, w, Kpad] and bias fp32
+    [B, K] (a row per image; any row stride) from ``project_kmeans_values``; bias None needs ``k``.  Returns ``(labels, A, mass)``, labels
+    uint8 [B, Ho, Wo] or None (``want_labels``).  Two identities, bit for bit: the labels are ``xna_head_objective(want_labels=True)``'s per
+    image, and (A, mass) are ``xna_mask_pool``'s for the bool masks ``labels == k``.  No float atomics: two calls give the same bits.
+    Raises NafHipError where the kernel does not serve the request (``xna_kmeans_select``; K above ``KMEANS_FUSED_MAX``): the composition
+    of those two operators is the caller's other arm."""
+    who = "xna_kmeans_step"
+    _check_operands(who, ((q, "q", _BF16), (k_lr, "k_lr", _BF16), (pv_lr, "pv_lr", _BF16)))
+    ky, kx = _ksize(kernel_size)
+    B, heads, Ho, Wo, Dq = q.shape
+    h, w, kpad = (int(s) for s in pv_lr.shape[2:])
+    if tuple(k_lr.shape) != (B, heads, h, w, Dq) or tuple(pv_lr.shape[:2]) != (B, heads):
+        raise ValueError(f"{who}: k_lr {tuple(k_lr.shape)} / pv_lr {tuple(pv_lr.shape)} do not match q {tuple(q.shape)}")
+    if bias is not None:
+        _gpu(bias, "bias")
+        if bias.dtype != torch.float32 or bias.dim() != 2 or bias.shape[0] != B or bias.stride(1) != 1 or (k is not None and int(k) != bias.shape[1]):
+            raise ValueError(f"{who}: bias must be a float32 [B, K] = ({B}, {'K' if k is None else int(k)}) tensor with contiguous rows")
+        K = int(bias.shape[1])
+    elif k is None:
+        raise ValueError(f"{who}: without a bias the number of clusters k must be given")
+    else:
+        K = int(k)
+    if K < 1 or kpad != head_npad(K):
+        raise ValueError(f"{who}: pv_lr holds {kpad} channels, K = {K} needs {head_npad(max(K, 1))}")
+    lib = _lib.load()
+    dev = q.device
+    A = torch.empty((B, heads, K, h, w), dtype=torch.float32, device=dev)
+    mass = torch.empty((B, K), dtype=torch.float32, device=dev)
+    labels = torch.empty((B, Ho, Wo), dtype=torch.uint8, device=dev) if want_labels else None
+    if B == 0:
+        return labels, A, mass
+    a = _lib.XnaKmeansArgs()
+    a.q, a.k_lr, a.pv_lr, a.A, a.mass = q.data_ptr(), k_lr.data_ptr(), pv_lr.data_ptr(), A.data_ptr(), mass.data_ptr()
+    if bias is not None:
+        a.bias, a.bias_stride_b = bias.data_ptr(), (int(bias.stride(0)) if B > 1 else K)
+    if labels is not None:
+        a.labels, a.labels_stride = labels.data_ptr(), _strides3(labels)
+    if rope_tables is not None:
+        a.rope_tab_y, a.rope_tab_x = _rope_table_ptrs(who, rope_tables, Ho, Wo, Dq)
+    _fill_geometry(a, q, k_lr, h, w, ky, kx, scale)
+    a.K, a.path = K, _lib.XNA_HEAD_FUSED
+    a.pv_stride = _strides4(pv_lr, (0, 1, 2, 3))
+    need = int(lib.naf_xna_kmeans_workspace_bytes(C.byref(a)))
+    ws = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
+    sel = lib.naf_xna_kmeans_select(C.byref(a))
+    if sel != _lib.XNA_HEAD_FUSED:
+        _lib.check(-sel, "naf_xna_kmeans_select")
+    with torch.cuda.device(dev), _Timed("xna_kmeans_step"):
+        rc = lib.naf_xna_kmeans_fwd(C.byref(a), _stream(q))
+    _lib.check(rc, "naf_xna_kmeans_fwd")
+    return labels, A, mass
+
+
 def normalize_embeddings(embeddings: torch.Tensor) -> torch.Tensor:
     """``F.normalize(E.float(), dim=1)`` (eps 1e-12) of an [N, C] or [N, C, 1, 1] embedding matrix: the rows the cosine head projects with."""
     if embeddings.dim() == 4 and tuple(embeddings.shape[2:]) == (1, 1):
