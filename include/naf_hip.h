@@ -77,7 +77,10 @@ extern "C" {
  * after those naf_xna_cos_select / naf_xna_cos_fwd -- the attention with a cosine head folded in: scaled cosines between the upsampled feature
  * and N embeddings, and the feature's norm (naf_xna_cos_args); and after those naf_xna_cos_ce_select / naf_xna_cos_ce_fwd -- that
  * attention with a cross-entropy on the scaled cosines in its epilogue: loss, labels, the gradient for the embeddings' projection and
- * for the scale (naf_xna_cos_ce_args, which embeds naf_xna_cos_args unchanged). */
+ * for the scale (naf_xna_cos_ce_args, which embeds naf_xna_cos_args unchanged); and, the same way, naf_xna_head_reg_select /
+ * naf_xna_head_reg_workspace_bytes / naf_xna_head_reg_fwd -- the attention with a linear head and a dense regression objective in its
+ * epilogue: L1 / MSE / smooth-L1 loss map, its gradient, and the error statistics of depth evaluation (naf_xna_head_reg_args, which embeds
+ * naf_xna_head_args unchanged). */
 /* The copy count is part of the ABI and the export names are DERIVED from it (round 6): a library built with another value
  * (-DNAF_STATS_SLOTS=8) exports naf_stem_conv0_fwd_s8, ..., so that a host holding [16][B][8][2] buffers cannot resolve them. */
 #ifndef NAF_STATS_SLOTS
@@ -669,6 +672,77 @@ typedef struct naf_xna_head_cm_args {
 } naf_xna_head_cm_args;
 int naf_xna_head_cm_select(const naf_xna_head_cm_args* a);
 int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream);
+
+/* ---- ... or a dense regression objective in the epilogue (added after the k-means entries; detect by symbol) ------------
+ * The other dense probing protocol the upsampler literature reports with the same linear probe: a 1x1 Conv2d(C, N) trained on a dense
+ * target (N = 1 depth; N = 2, 3 flow, normals, colour) under a validity mask and, for depth, scored with RMSE, abs-rel and delta < 1.25^k.
+ * A pixel's N logits z are in the registers of four lanes when naf_xna_head_fwd's kernel is done, so this entry computes, per pixel and
+ * in fp32, with r[n] = z[n] - target[n] (the bias added exactly as naf_xna_head_fwd adds it),
+ *     loss[px]       = sum_n l(r[n]), 0 where the pixel is not valid
+ *     dlogits[px, n] = l'(r[n]),      0 where the pixel is not valid and for the pad channels n >= N
+ *     NAF_HEAD_REG_L1         l = |r|                                                   l' = sign(r)   (0 at r = 0)
+ *     NAF_HEAD_REG_MSE        l = r * r                                                 l' = 2 r, formed as (bf16)(2.f * r)
+ *     NAF_HEAD_REG_SMOOTH_L1  l = |r| < beta ? 0.5 r r / beta : |r| - 0.5 beta          l' = |r| < beta ? r / beta : sign(r)     (torch's, beta > 0)
+ * and stores only what is asked for; the [B, Ho, Wo, N] logits need not exist.
+ *   head      naf_xna_head_args as for naf_xna_head_fwd, except that `out` may be NULL; when given it receives the logits, fp32
+ *             (out_dtype must be NAF_F32), bit for bit what naf_xna_head_fwd stores.  1 <= N <= 32 here
+ *   target    device float [B, N, Ho, Wo] read at ELEMENT strides t_stride {b, n, y, x}: any layout (NCHW, channels-last, a view).  NULL when
+ *             only the logits are wanted.  Target and mask are only read as values; no address is formed from them
+ *   valid     device uint8 [B, Ho, Wo] (valid_stride {b, y, x}), or NULL = every pixel valid: a pixel is valid when its byte is not 0, for
+ *             all N channels alike
+ *   loss      device float [B, Ho, Wo] (loss_stride), or NULL.  A lane adds its channels in ascending order, the pixel's four lanes add in a
+ *             two-level tree: N - 1 additions.  The caller reduces the map (sum, or sum / (valid pixels * N))
+ *   dlogits   device bf16 [B, Ho, Wo, dlogits_channels] (dlogits_stride {b, y, x}, channel axis contiguous), or NULL: rounded once to bf16,
+ *             NOT divided by anything; EVERY one of the dlogits_channels channels is written, so the buffer needs no clearing: it is the
+ *             `dout` of naf_xna_bwd for all heads at once (head stride 0), as naf_xna_head_ce_args' is
+ *   errors    device double[NAF_HEAD_REG_STATS], 8-byte aligned, or NULL; N == 1 only.  The call ADDS to it (the library never clears it), so
+ *             one accumulator passed for every batch of a validation set ends up as the set's sums without a host synchronisation.  With
+ *             p = min(max(z, clamp_lo), clamp_hi) (clamp_lo > 0; both bounds are the floats given) a pixel is COUNTED when it is valid,
+ *             target > 0 and target and z are finite; over the counted pixels, with d = ln p - ln target:
+ *               [0] n   [1] sum |p - t|   [2] sum (p - t)^2   [3] sum |p - t| / t   [4] sum (p - t)^2 / t   [5] sum d   [6] sum d^2
+ *               [7], [8], [9] number of pixels with max(p / t, t / p) < 1.25, 1.25^2, 1.25^3
+ *             The clamp applies to these statistics only.
+ *   workspace device, naf_xna_head_reg_workspace_bytes(a) bytes (0 without errors), 8-byte aligned; contents need no initialisation
+ * Summation of the statistics: no floating-point atomics.  Per round of its workgroup (xna_head_kernel.h) a lane adds at most two pixels'
+ * terms in fp32, the 16 lanes of a row add theirs in a four-level tree, and from there on every addition is fp64: the wave's sums over
+ * the rounds, the eight waves in wave order, one row of ten fp64 partials per workgroup in `workspace`, and a one-workgroup finishing
+ * kernel launched by the same call on the same stream that adds the rows in a fixed order and adds the ten totals to `errors`.  The
+ * LONGEST FP32 ADDITION CHAIN between a pixel's term and the fp64 sums is 6 (this interface promises at most 64); counts are exact.
+ * Two runs give the same bits.  No cross-workgroup dependency, no spin-wait.
+ * naf_xna_head_reg_select answers as naf_xna_head_ce_select does (NAF_XNA_HEAD_FUSED, -NAF_ERR_INVALID, -NAF_ERR_UNSUPPORTED, with
+ * naf_last_error) and additionally refuses, -NAF_ERR_INVALID: nothing asked for (out, loss, dlogits and errors all NULL); a NULL target with
+ * loss, dlogits or errors; errors with N != 1; errors that is not 8-byte aligned; beta <= 0 with NAF_HEAD_REG_SMOOTH_L1; clamp_lo <= 0 or
+ * clamp_hi < clamp_lo with errors; an unknown kind; non-zero reserved fields; dlogits_channels as for naf_xna_head_ce_args;
+ * -NAF_ERR_UNSUPPORTED: N > 32 (the caller composes naf_xna_head_fwd's fp32 logits with the loss); a dlogits that is not 16-byte
+ * aligned, whose strides are not multiples of 8 elements, or whose channel count is not a value width naf_xna_bwd serves (32, 64, 96,
+ * 128, 192, 256).  A pure host-side query: pointers are checked, never read.  naf_xna_head_reg_fwd additionally refuses
+ * (-NAF_ERR_INVALID) a NULL, misaligned or too small workspace when errors is given.  Served geometries: exactly naf_xna_head_fwd's.
+ * The struct must be zero-initialised by the caller (reserved fields are checked).  Caller-owned memory, workspace and stream; nothing
+ * is allocated or kept; capturable. */
+#define NAF_HEAD_REG_STATS 10
+enum naf_head_reg_kind { NAF_HEAD_REG_L1 = 0, NAF_HEAD_REG_MSE = 1, NAF_HEAD_REG_SMOOTH_L1 = 2 };
+typedef struct naf_xna_head_reg_args {
+    naf_xna_head_args head; /* head.out may be NULL */
+    const float* target;
+    const uint8_t* valid;
+    float* loss;
+    void* dlogits;
+    double* errors;
+    void* workspace;
+    size_t workspace_bytes;
+    int32_t dlogits_channels;
+    int32_t kind; /* naf_head_reg_kind */
+    float beta;
+    float clamp_lo, clamp_hi;
+    int32_t reserved[3]; /* must be 0 */
+    int64_t t_stride[4]; /* {b, n, y, x} */
+    int64_t valid_stride[3];
+    int64_t loss_stride[3];
+    int64_t dlogits_stride[3];
+} naf_xna_head_reg_args;
+int naf_xna_head_reg_select(const naf_xna_head_reg_args* a);
+size_t naf_xna_head_reg_workspace_bytes(const naf_xna_head_reg_args* a);
+int naf_xna_head_reg_fwd(const naf_xna_head_reg_args* a, naf_stream_t stream);
 
 /* ---- label propagation: windowed top-k affinity over a queue of context frames (added after the confusion entries; detect by symbol) ----
  * Replaces label_propagation (evaluation/eval_video_seg.py:499-561) after feature extraction: the reference materialises

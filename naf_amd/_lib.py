@@ -74,6 +74,22 @@ class XnaHeadCMArgs(C.Structure):
     _fields_ = [("ce", XnaHeadCEArgs), ("confusion", C.c_void_p), ("cm_stride", C.c_int64), ("reserved", C.c_int64 * 2)]
 
 
+HEAD_REG_STATS = 10                                   # NAF_HEAD_REG_STATS
+HEAD_REG_KINDS = {"l1": 0, "mse": 1, "smooth_l1": 2}  # naf_head_reg_kind
+
+
+class XnaHeadRegArgs(C.Structure):
+    """naf_xna_head_reg_args (added after the k-means entries, detected by symbol): naf_xna_head_args plus the regression epilogue's target,
+    mask, maps and error statistics.  ctypes zero-initialises it, as the header asks."""
+    _fields_ = [
+        ("head", XnaHeadArgs), ("target", C.c_void_p), ("valid", C.c_void_p), ("loss", C.c_void_p), ("dlogits", C.c_void_p),
+        ("errors", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+        ("dlogits_channels", C.c_int32), ("kind", C.c_int32), ("beta", C.c_float), ("clamp_lo", C.c_float), ("clamp_hi", C.c_float),
+        ("reserved", C.c_int32 * 3),
+        ("t_stride", I64x4), ("valid_stride", I64x3), ("loss_stride", I64x3), ("dlogits_stride", I64x3),
+    ]
+
+
 class XnaCosArgs(C.Structure):
     """naf_xna_cos_args (added after the image-preparation entries, detected by symbol): the attention with a cosine head folded in."""
     _fields_ = [
@@ -430,6 +446,9 @@ SIGNATURES = {
     "naf_xna_head_ce_fwd": (C.c_int, [C.POINTER(XnaHeadCEArgs), C.c_void_p]),
     "naf_xna_head_cm_select": (C.c_int, [C.POINTER(XnaHeadCMArgs)]),
     "naf_xna_head_cm_fwd": (C.c_int, [C.POINTER(XnaHeadCMArgs), C.c_void_p]),
+    "naf_xna_head_reg_select": (C.c_int, [C.POINTER(XnaHeadRegArgs)]),
+    "naf_xna_head_reg_workspace_bytes": (C.c_size_t, [C.POINTER(XnaHeadRegArgs)]),
+    "naf_xna_head_reg_fwd": (C.c_int, [C.POINTER(XnaHeadRegArgs), C.c_void_p]),
     "naf_xna_cos_select": (C.c_int, [C.POINTER(XnaCosArgs)]),
     "naf_xna_cos_fwd": (C.c_int, [C.POINTER(XnaCosArgs), C.c_void_p]),
     "naf_xna_cos_ce_select": (C.c_int, [C.POINTER(XnaCosCEArgs)]),

@@ -496,6 +496,57 @@ int naf_xna_head_cm_fwd(const naf_xna_head_cm_args* a, naf_stream_t stream) {
     return naf_launch_xna_head_cm(a, xna_scale(a->ce.head.scale, a->ce.head.Dq), static_cast<hipStream_t>(stream));
 }
 
+// ---- ... or a dense regression objective in that epilogue's place (L1 / MSE / smooth-L1 loss, its gradient, depth error statistics) ----
+static int xna_head_reg_validate(const naf_xna_head_reg_args* c) {
+    NAF_REQUIRE(c != nullptr, "naf_xna_head_reg: args is NULL");
+    const int rc = xna_head_validate(&c->head, false);
+    if (rc != NAF_OK) return rc;
+    NAF_REQUIRE(c->reserved[0] == 0 && c->reserved[1] == 0 && c->reserved[2] == 0, "naf_xna_head_reg: reserved fields must be 0");
+    NAF_REQUIRE(c->kind == NAF_HEAD_REG_L1 || c->kind == NAF_HEAD_REG_MSE || c->kind == NAF_HEAD_REG_SMOOTH_L1, "naf_xna_head_reg: unknown kind %d", c->kind);
+    NAF_REQUIRE(c->head.out || c->loss || c->dlogits || c->errors, "naf_xna_head_reg: nothing asked for (out, loss, dlogits and errors are all NULL)");
+    NAF_REQUIRE(c->head.out == nullptr || c->head.out_dtype == NAF_F32, "naf_xna_head_reg: the optional logits are stored as NAF_F32 (out_dtype %d)", c->head.out_dtype);
+    NAF_REQUIRE(c->target != nullptr || (c->loss == nullptr && c->dlogits == nullptr && c->errors == nullptr), "naf_xna_head_reg: loss, dlogits and errors need a target");
+    NAF_REQUIRE(c->kind != NAF_HEAD_REG_SMOOTH_L1 || c->beta > 0.f, "naf_xna_head_reg: NAF_HEAD_REG_SMOOTH_L1 needs beta > 0, got %g", (double)c->beta);
+    if (c->errors != nullptr) {
+        NAF_REQUIRE(c->head.N == 1, "naf_xna_head_reg: the error statistics are defined for N = 1 (got N = %d)", c->head.N);
+        NAF_REQUIRE(reinterpret_cast<uintptr_t>(c->errors) % 8 == 0, "naf_xna_head_reg: errors is not 8-byte aligned");
+        NAF_REQUIRE(c->clamp_lo > 0.f && c->clamp_hi >= c->clamp_lo, "naf_xna_head_reg: the error statistics need 0 < clamp_lo <= clamp_hi, got %g, %g",
+                    (double)c->clamp_lo, (double)c->clamp_hi);
+    }
+    if (c->dlogits != nullptr) {
+        const int npad = (c->head.N + 15) & ~15;
+        NAF_REQUIRE(c->dlogits_channels % 8 == 0, "naf_xna_head_reg: dlogits_channels must be a multiple of 8, got %d", c->dlogits_channels);
+        NAF_REQUIRE(c->dlogits_channels >= npad, "naf_xna_head_reg: dlogits_channels %d smaller than N rounded up to 16 (%d)", c->dlogits_channels, npad);
+        NAF_REQUIRE(c->dlogits_channels <= 256, "naf_xna_head_reg: dlogits_channels %d above 256", c->dlogits_channels);
+        NAF_REQUIRE(c->dlogits_stride[2] >= c->dlogits_channels, "naf_xna_head_reg: dlogits x stride %lld smaller than dlogits_channels %d",
+                    (long long)c->dlogits_stride[2], c->dlogits_channels);
+    }
+    return NAF_OK;
+}
+
+int naf_xna_head_reg_select(const naf_xna_head_reg_args* a) {
+    int rc = xna_head_reg_validate(a);
+    if (rc == NAF_OK) rc = naf_xna_head_reg_eligible(a);
+    return rc != NAF_OK ? -rc : NAF_XNA_HEAD_FUSED;
+}
+
+size_t naf_xna_head_reg_workspace_bytes(const naf_xna_head_reg_args* a) {
+    if (xna_head_reg_validate(a) != NAF_OK) return 0;
+    return naf_xna_head_reg_ws(a);
+}
+
+int naf_xna_head_reg_fwd(const naf_xna_head_reg_args* a, naf_stream_t stream) {
+    const int sel = naf_xna_head_reg_select(a);
+    if (sel < 0) return -sel;
+    if (a->errors != nullptr) {
+        const size_t need = naf_xna_head_reg_ws(a);
+        NAF_REQUIRE(a->workspace != nullptr && reinterpret_cast<uintptr_t>(a->workspace) % 8 == 0 && a->workspace_bytes >= need,
+                    "naf_xna_head_reg_fwd: workspace of %zu bytes given, %zu needed, 8-byte aligned (naf_xna_head_reg_workspace_bytes)",
+                    a->workspace ? a->workspace_bytes : (size_t)0, need);
+    }
+    return naf_launch_xna_head_reg(a, xna_scale(a->head.scale, a->head.Dq), static_cast<hipStream_t>(stream));
+}
+
 // ---- the cosine head: scaled cosines between the upsampled feature and N embeddings (after the image-preparation entries) ----
 // need_out = false: the classification entry (naf_xna_cos_ce_*), where `out` is optional
 static int xna_cos_validate(const naf_xna_cos_args* a, bool need_out = true) {

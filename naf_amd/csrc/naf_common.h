@@ -79,6 +79,9 @@ int naf_xna_head_eligible(const naf_xna_head_args* a);                          
 int naf_launch_xna_head_ce(const naf_xna_head_ce_args* a, float scale, hipStream_t s);   // xna_head.hip: the classification epilogue
 int naf_launch_xna_head_cm(const naf_xna_head_cm_args* a, float scale, hipStream_t s);   // xna_head.hip: ... with a confusion matrix
 int naf_xna_head_ce_eligible(const naf_xna_head_ce_args* a);                          // xna_head.hip: naf_xna_head_eligible plus the dlogits layout
+int naf_launch_xna_head_reg(const naf_xna_head_reg_args* a, float scale, hipStream_t s);   // xna_head.hip: the regression epilogue and its finishing kernel
+int naf_xna_head_reg_eligible(const naf_xna_head_reg_args* a);                          // xna_head.hip: naf_xna_head_eligible plus N <= 32 and the dlogits layout
+size_t naf_xna_head_reg_ws(const naf_xna_head_reg_args* a);                             // xna_head.hip: bytes of the statistics workspace (0 without errors)
 int naf_launch_xna_cos(const naf_xna_cos_args* a, float scale, hipStream_t s);     // xna_cos.hip: the cosine head
 int naf_xna_cos_eligible(const naf_xna_cos_args* a);                              // xna_cos.hip: NAF_OK, or NAF_ERR_UNSUPPORTED with the reason set
 int naf_launch_xna_cos_ce(const naf_xna_cos_ce_args* a, float scale, hipStream_t s);   // xna_cos.hip: ... with the classification epilogue

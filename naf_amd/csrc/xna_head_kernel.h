@@ -47,6 +47,24 @@
 // of a wave are added directly.  The adds are no-return 64-bit vector atomics; integer adds commute exactly, so the matrix does not
 // depend on the order.  t * cm_stride + label is the ONE address formed from the target, after t AND label have been checked to lie
 // in [0, N) (a pixel whose logits are NaN has no maximum and counts nothing).
+//
+// Regression epilogue (Extra = XnaHeadRegExtra, naf_xna_head_reg_fwd): a third epilogue, instantiated for N <= 32 only (NCT = 2); the
+// logits, XnaHeadCEExtra and XnaHeadCMExtra instantiations keep their code (`if constexpr`).  With z = acc + bias as above and a dense
+// fp32 target t [B, N, Ho, Wo] read at element strides, r[n] = z[n] - t[n]; a pixel is valid when there is no mask or its uint8 mask
+// value is not 0.  Target and mask are only read as values: no address is formed from them.
+//     loss[px] = sum_n l(r[n]) (0 where invalid),  l = |r| (L1), r*r (MSE), |r| < beta ? 0.5*r*r/beta : |r| - 0.5*beta (SMOOTH_L1)
+//     g[px, n] = sign(r) (L1), (bf16)(2.f * r) (MSE), |r| < beta ? r/beta : sign(r) (SMOOTH_L1); zeros for n >= N and invalid pixels
+//   A lane adds its channels in ascending order, the four lanes of the pixel add with naf_rows_sum; the grp = 0 lane stores the loss.  g is
+//   rounded once to bf16 and stored as 8-byte vectors by the owning lanes, every one of the gc channels written, as the CE dlogits is.
+//   Error statistics (N == 1, the evaluation of a depth probe): p = min(max(z, clamp_lo), clamp_hi), a pixel is counted when it is valid,
+//   t > 0 and t, z are finite; d = ln p - ln t; ten sums over the counted pixels: n, |p-t|, (p-t)^2, |p-t|/t, (p-t)^2/t, d, d^2 and the
+//   three counts max(p/t, t/p) < 1.25^k.  No float atomics.  Channel 0 of a pixel is in its grp = 0 lane: per round that lane adds its
+//   (at most TPW = 2) pixels in fp32, the 16 lanes of the row add in a four-level DPP tree (naf_cols_sum), and lane 0 adds the wave's ten
+//   fp32 sums to the wave's row of fp64 accumulators in LDS (640 bytes of static LDS, these instantiations only).  After the last round
+//   the eight rows are added in wave order in fp64 and the workgroup writes ONE row of ten fp64 partials to the caller's workspace
+//   [nblocks][10]; naf_xna_head_reg_fwd's finishing kernel adds the rows in block order.  So the longest fp32 addition chain between a
+//   pixel's term and the fp64 sums is 2 + 4 = 6 additions (well inside the 64 the interface promises), counts are integers below 2^24
+//   in fp32 and exact in fp64, and the result is bit-reproducible.  Every output is optional (NULL: a wave-uniform branch).
 #pragma once
 #include "xna_mfma_kernel.h"
 
@@ -87,6 +105,23 @@ struct XnaHeadCMExtra {
 };
 template <typename... T> struct XnaHeadIsCM { static constexpr bool value = false; };
 template <> struct XnaHeadIsCM<XnaHeadCMExtra> { static constexpr bool value = true; };
+// the regression epilogue's arguments (see the header comment); read from the kernel-argument segment in the epilogue like XnaHeadCEExtra
+constexpr int XNA_HEAD_REG_STATS = 10;   // NAF_HEAD_REG_STATS of include/naf_hip.h
+struct XnaHeadRegExtra {
+    const float* target;     // [B, N, Ho, Wo] or nullptr
+    const uint8_t* valid;    // [B, Ho, Wo] or nullptr (every pixel valid)
+    float* loss;             // per-pixel sum over the channels, or nullptr
+    bf16_t* dlogits;         // [B, Ho, Wo, gc] gradient of that sum, or nullptr
+    double* partial;         // [nblocks][XNA_HEAD_REG_STATS] error statistics of the workgroups (N == 1, host), or nullptr
+    int64_t ts[4];           // {b, n, y, x} element strides of target
+    int64_t ms[3], ls[3], gs[3];   // {b, y, x} element strides of valid / loss / dlogits
+    int32_t gc;              // channels of a dlogits row the kernel writes (multiple of 8, >= npad)
+    int32_t kind;            // naf_head_reg_kind
+    float beta, clamp_lo, clamp_hi;
+};
+template <typename... T> struct XnaHeadIsReg { static constexpr bool value = false; };
+template <> struct XnaHeadIsReg<XnaHeadRegExtra> { static constexpr bool value = true; };
+static_assert(alignof(XnaHeadRegExtra) == alignof(XnaHeadCEExtra), "both epilogue structs follow XnaHeadParams at XNA_HEAD_CE_ARG_OFFSET");
 // they are the kernel's SECOND argument: it follows XnaHeadParams in the kernel-argument segment at its natural alignment
 constexpr size_t XNA_HEAD_CE_ARG_OFFSET = (sizeof(XnaHeadParams) + alignof(XnaHeadCEExtra) - 1) / alignof(XnaHeadCEExtra) * alignof(XnaHeadCEExtra);
 
@@ -97,12 +132,26 @@ constexpr int xna_head_nct(int npad) { return npad <= 32 ? 2 : npad <= 64 ? 4 : 
 constexpr int xna_head_tpw(int ks, int nct) { return (nct >= 10 && ks >= 11) ? 1 : 2; }
 constexpr size_t xna_head_lds_for(int ks, int nct) { return (size_t)(ks * ks) * (72 + nct * 16 + 16) * 2; }
 
+// sum over the 16 lanes of a row (col = lane & 15), every lane gets it: two quad permutes, then the mirrors of 8 and of 16 lanes (DPP);
+// a fixed four-level tree.  All lanes of the wave must be active.
+__device__ __forceinline__ float naf_cols_sum(float v) {
+    int b = __float_as_int(v);
+    v += __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0xB1, 0xf, 0xf, false));    // quad_perm [1, 0, 3, 2]
+    b = __float_as_int(v);
+    v += __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x4E, 0xf, 0xf, false));    // quad_perm [2, 3, 0, 1]
+    b = __float_as_int(v);
+    v += __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x141, 0xf, 0xf, false));   // row_half_mirror
+    b = __float_as_int(v);
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(b, b, 0x140, 0xf, 0xf, false));   // row_mirror
+}
+
 // CE = false: the logits kernel, one argument, the code it was before the classification epilogue existed (a parameter of another type, even
 // one that is the same struct, moves its instruction schedule).  CE = true: Extra = XnaHeadCEExtra, read through the segment pointer.
 template <int KS, int NCT, typename OutT, bool CE = false, typename... Extra>
 __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHeadParams p, const Extra... extra) {
     static_assert(sizeof...(Extra) == (CE ? 1 : 0), "the classification epilogue takes XnaHeadCEExtra as its second argument");
     constexpr bool CM = XnaHeadIsCM<Extra...>::value;   // ... or XnaHeadCMExtra: it counts into a confusion matrix as well
+    constexpr bool REG = XnaHeadIsReg<Extra...>::value; // ... or XnaHeadRegExtra: the regression epilogue in place of the classification one
     constexpr int NW = XNA_HEAD_NW, NT = NW * 64;
     constexpr int TPW = xna_head_tpw(KS, NCT);
     using G = XnaGeom<KS, 1>;
@@ -303,7 +352,121 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
             }
         }
 
-        if constexpr (CE) {
+        if constexpr (REG) {
+            // ---- regression epilogue (see the header comment): residual, loss map, its gradient, error statistics ----
+            static_assert(NCT == 2, "the regression epilogue is instantiated for N <= 32 only");
+            // the epilogue's arguments and the lane's coordinates are made opaque for the reasons given in the classification epilogue below
+            const char __attribute__((address_space(4)))* ka = (const char __attribute__((address_space(4)))*)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(ka));
+            int ecol = col, egrp = grp, elane = lane;
+            asm volatile("" : "+v"(ecol), "+v"(egrp), "+v"(elane));
+            const XnaHeadRegExtra __attribute__((address_space(4)))* x = reinterpret_cast<const XnaHeadRegExtra __attribute__((address_space(4)))*>(ka + XNA_HEAD_CE_ARG_OFFSET);
+            __shared__ double reg_acc[NW][XNA_HEAD_REG_STATS];   // each wave's sums over the rounds so far; only that wave touches its row
+            const bool have_t = x->target != nullptr, stats = x->partial != nullptr;   // wave-uniform
+            float es[XNA_HEAD_REG_STATS] = {};
+#pragma unroll
+            for (int u = 0; u < TPW; ++u) {
+                if (!livev[u]) continue;   // wave-uniform: the four-lane reduction below runs on whole waves
+                const bool inpx = tx0v[u] + ecol < p.dx;
+                const int64_t gy = cy * p.dy + tyv[u];
+                const int64_t gx = cx * p.dx + min(tx0v[u] + ecol, p.dx - 1);   // lanes past a partial last tile repeat its last pixel, store nothing
+                bool ok = true;
+                if (x->valid != nullptr) ok = x->valid[b * x->ms[0] + gy * x->ms[1] + gx * x->ms[2]] != 0;
+                const float* tp = x->target + b * x->ts[0] + gy * x->ts[2] + gx * x->ts[3];
+                float lsum = 0.f, tc0 = 0.f;
+                bf16x4_t gv[NCT];
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int ch = ct * 16 + egrp * 4 + r;
+                        float g = 0.f;
+                        if (ch < p.N) {
+                            // z = acc + bias: the expression of the logits epilogue, so a stored z is the logit naf_xna_head_fwd stores
+                            const float z = acc[u][ct][r] + (p.bias != nullptr ? p.bias[ch] : 0.f);
+                            acc[u][ct][r] = z;
+                            if (have_t) {
+                                const float t = tp[ch * x->ts[1]];
+                                if (ct == 0 && r == 0) tc0 = t;
+                                const float rr = z - t, a = fabsf(rr);
+                                const float sg = rr > 0.f ? 1.f : (rr < 0.f ? -1.f : 0.f);
+                                float term;
+                                if (x->kind == NAF_HEAD_REG_L1) {
+                                    term = a;
+                                    g = sg;
+                                } else if (x->kind == NAF_HEAD_REG_MSE) {
+                                    term = rr * rr;
+                                    g = 2.f * rr;
+                                } else {
+                                    const bool small = a < x->beta;
+                                    term = small ? (0.5f * rr) * rr / x->beta : a - 0.5f * x->beta;
+                                    g = small ? rr / x->beta : sg;
+                                }
+                                lsum += term;
+                            }
+                        }
+                        gv[ct][r] = (bf16_t)(ok ? g : 0.f);
+                    }
+                lsum = naf_rows_sum(lsum);
+                if (egrp == 0 && inpx && x->loss != nullptr) x->loss[b * x->ls[0] + gy * x->ls[1] + gx * x->ls[2]] = ok ? lsum : 0.f;
+                if (p.out != nullptr && inpx) {
+                    OutT* op = o_cell + (int64_t)tyv[u] * p.os[1] + (int64_t)(tx0v[u] + ecol) * p.os[2];
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const int ch = ct * 16 + egrp * 4 + r;
+                            if (ch < p.N) op[ch] = (OutT)acc[u][ct][r];
+                        }
+                }
+                if (x->dlogits != nullptr && inpx) {
+                    bf16_t* gp = x->dlogits + b * x->gs[0] + gy * x->gs[1] + gx * x->gs[2];
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct) {
+                        const int c0 = ct * 16 + egrp * 4;
+                        if (c0 >= x->gc) continue;   // gc is a multiple of 8: a lane's four channels are all inside or all outside
+                        *reinterpret_cast<bf16x4_t*>(gp + c0) = gv[ct];
+                    }
+                    // channels past the accumulators (gc > 32): plain zero stores
+                    for (int c0 = DVT + egrp * 4; c0 < x->gc; c0 += 16) *reinterpret_cast<bf16x4_t*>(gp + c0) = bf16x4_t{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+                }
+                if (stats) {
+                    // N == 1 (host): the pixel's one channel is in its grp = 0 lane.  What a lane that does not count computes is discarded.
+                    const float z = acc[u][0][0];
+                    const bool cnt = egrp == 0 && inpx && ok && tc0 > 0.f && tc0 < INFINITY && fabsf(z) < INFINITY;
+                    const float pz = fminf(fmaxf(z, x->clamp_lo), x->clamp_hi);
+                    const float e = pz - tc0, ae = fabsf(e), e2 = e * e;
+                    const float d = logf(pz) - logf(tc0);
+                    const float ratio = fmaxf(pz / tc0, tc0 / pz);
+                    es[0] += cnt ? 1.f : 0.f;
+                    es[1] += cnt ? ae : 0.f;
+                    es[2] += cnt ? e2 : 0.f;
+                    es[3] += cnt ? ae / tc0 : 0.f;
+                    es[4] += cnt ? e2 / tc0 : 0.f;
+                    es[5] += cnt ? d : 0.f;
+                    es[6] += cnt ? d * d : 0.f;
+                    es[7] += (cnt && ratio < 1.25f) ? 1.f : 0.f;
+                    es[8] += (cnt && ratio < 1.5625f) ? 1.f : 0.f;
+                    es[9] += (cnt && ratio < 1.953125f) ? 1.f : 0.f;
+                }
+            }
+            if (stats) {
+#pragma unroll
+                for (int i = 0; i < XNA_HEAD_REG_STATS; ++i) {
+                    const float v = naf_cols_sum(es[i]);   // lane 0: the sum over the grp = 0 lanes, which hold the pixels
+                    if (elane == 0) reg_acc[wave][i] = (t0 == 0 ? 0.0 : reg_acc[wave][i]) + (double)v;   // the first round starts the sums
+                }
+                if (t0 + NW * TPW >= ntile) {   // the last round (uniform over the workgroup): the eight rows in wave order, one row out
+                    __syncthreads();
+                    if (wave == 0 && elane < XNA_HEAD_REG_STATS) {
+                        double sum = 0.0;
+#pragma unroll
+                        for (int j = 0; j < NW; ++j) sum += reg_acc[j][elane];
+                        x->partial[(int64_t)blockIdx.x * XNA_HEAD_REG_STATS + elane] = sum;
+                    }
+                }
+            }
+        } else if constexpr (CE) {
             // ---- classification epilogue (see the header comment): softmax over the classes, loss, label, softmax - onehot ----
             constexpr float LOG2E = 1.4426950408889634f, LN2 = 0.6931471805599453f;
             // the epilogue's own arguments, fetched from the kernel-argument segment HERE: the empty asm makes the address opaque, so the
@@ -463,8 +626,8 @@ __global__ __launch_bounds__(XNA_HEAD_NW * 64) void xna_head_kernel(const XnaHea
     }
 }
 
-// One launcher for the three variants: no Extra = logits, XnaHeadCEExtra = classification epilogue, XnaHeadCMExtra = ... with a
-// confusion matrix.  The optional outputs of an epilogue are run-time NULL checks inside the kernel.
+// One launcher for the four variants: no Extra = logits, XnaHeadCEExtra = classification epilogue, XnaHeadCMExtra = ... with a
+// confusion matrix, XnaHeadRegExtra = regression epilogue.  The optional outputs of an epilogue are run-time NULL checks inside the kernel.
 template <int KS, int NCT, typename OutT, typename... Extra>
 static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s, const char* what, const Extra&... extra) {
     constexpr size_t lds = xna_head_lds_for(KS, NCT);
@@ -482,7 +645,7 @@ static int xna_head_launch_one(const XnaHeadParams& p, hipStream_t s, const char
 }
 
 // The window's entry point, one explicit instantiation per variant in xna_head_inst.hip.  `who` names the variant in the messages
-// ("xna_head", "xna_head_ce", "xna_head_cm"); the logits variant stores bf16 or float, the epilogues float only.
+// ("xna_head", "xna_head_ce", "xna_head_cm", "xna_head_reg"); the logits variant stores bf16 or float, the epilogues float only.
 template <int KS, typename... Extra>
 int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s, const char* who, const char* what, const Extra&... extra) {
     const int nct = xna_head_nct(p.npad);
@@ -493,16 +656,19 @@ int xna_head_launch_ks(const XnaHeadParams& p, int out_dtype, hipStream_t s, con
         return xna_head_launch_one<KS, C, float>(p, s, what, extra...);                                                \
     }
     NAF_HEAD_CASE(2)
-    NAF_HEAD_CASE(4)
-    NAF_HEAD_CASE(10)
-    NAF_HEAD_CASE(16)
+    if constexpr (!XnaHeadIsReg<Extra...>::value) {   // the regression epilogue serves N <= 32 only (the host refuses more)
+        NAF_HEAD_CASE(4)
+        NAF_HEAD_CASE(10)
+        NAF_HEAD_CASE(16)
+    }
 #undef NAF_HEAD_CASE
     naf_set_error("%s: no kernel for kernel_size=%d channel tiles=%d", who, KS, nct);
     return NAF_ERR_UNSUPPORTED;
 }
 
-// xna_head_inst.hip (-DNAF_KS=<KS>) defines these three, xna_head.hip declares them (extern) and dispatches on the window.
+// xna_head_inst.hip (-DNAF_KS=<KS>) defines these four, xna_head.hip declares them (extern) and dispatches on the window.
 #define NAF_XNA_HEAD_WINDOW(LINKAGE, KS)                                                                                                        \
     LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*);                              \
     LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadCEExtra&);       \
-    LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadCMExtra&);
+    LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadCMExtra&);       \
+    LINKAGE template int xna_head_launch_ks<KS>(const XnaHeadParams&, int, hipStream_t, const char*, const char*, const XnaHeadRegExtra&);

@@ -140,6 +140,22 @@ def reduce_confusion(cm: torch.Tensor) -> torch.Tensor:
     return cm
 
 
+def reduce_errors(acc: torch.Tensor) -> torch.Tensor:
+    """Sum the error sums of a depth evaluation (``naf(..., head=probe, dense_target=t, errors=acc)``, float64 [10]) over the ranks: ONE
+    ``all_reduce(SUM)`` of ten doubles, in place, returning ``acc`` -- what ``reduce_confusion`` is to the confusion matrix.  Each rank
+    accumulates over its own shard of the validation set and calls this once at the end; ``naf_amd.depth_metrics`` of the result are the
+    set's figures.  Without an initialised process group it returns its argument untouched."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return acc
+    if acc.is_contiguous():
+        dist.all_reduce(acc, op=dist.ReduceOp.SUM)
+        return acc
+    buf = acc.contiguous()
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    acc.copy_(buf)
+    return acc
+
+
 class ShardedNAF:
     """Runs ``model`` on this rank's slice of a batch, in micro-batches to bound the encoder's activations (bf16 guidance
     at full resolution: 1 GB per image in flight).  ``concat=False`` returns the list of micro-batch outputs instead of

@@ -1122,7 +1122,7 @@ class NAF(nn.Module):
     def forward(self, image, features, output_size, return_weights=False, *args, head=None, target=None, ignore_index=-100,
                 reduction="mean", predict=False, confusion=None, regress=None, regress_path="auto", cosine=False, logit_scale=1.0,
                 return_norms=False, cosine_path="auto", loss=None, masks=None, mask_reduce="mean", mask_path="auto",
-                return_attention=False, **kwargs):
+                return_attention=False, dense_target=None, dense_loss="l1", beta=1.0, valid=None, errors=None, clamp=None, **kwargs):
         """``naf(image, lr_features, target_size)`` (naf.py:104-116).  ``return_weights``: False, True (``(out, scores)``, the scores
         without a gradient) or "differentiable" (``(out, scores)`` with scores that carry a gradient to q and k on a gradient-enabled call,
         as the reference's always do; see ``forward_train``).  Outside a gradient-enabled call "differentiable" is the same as True.  The reference's forward is always differentiable;
@@ -1247,7 +1247,46 @@ class NAF(nn.Module):
         64 masks run in chunks of 64.  ``image`` may be a ``Guidance``.  ValueError, before any device work: ``masks`` together with ``head``,
         ``target``, ``predict``, ``confusion``, ``regress``, ``return_weights`` or ``cosine``; a wrong shape or device; ``mask_reduce`` outside
         the two values.  Not offered: integer label maps (pass ``labels[:, None] == torch.arange(K, device=labels.device)[None, :, None, None]``),
-        a gradient through the fused route, ``capture()`` of this call."""
+        a gradient through the fused route, ``capture()`` of this call.
+
+        ``dense_target``, ``dense_loss``, ``beta``, ``valid``, ``errors``, ``clamp`` (keyword only, with ``head``): DENSE REGRESSION with the
+        probe -- the other dense probing protocol: a 1x1 ``Conv2d(C, N)`` trained on depth (N = 1) or flow, normals, colour (N = 2, 3)
+        under a validity mask, and for depth scored with RMSE, abs-rel and delta < 1.25^k.  ``dense_target`` is a float tensor
+        [B, N, Ho, Wo] on the features' device (any strides; other float dtypes are converted to float32), ``valid`` a bool / uint8
+        [B, Ho, Wo] mask or None (a pixel is valid for all N channels alike; what lies under an invalid pixel, NaN included, reaches
+        nothing).  With ``sel`` = ``valid`` broadcast over the channels the call returns, for ``reduction`` "mean" / "sum",
+            ``F.l1_loss(head(naf(...)).float()[sel], dense_target.float()[sel], reduction=reduction)``        (``dense_loss="l1"``)
+        or ``F.mse_loss`` (``"mse"``) or ``F.smooth_l1_loss(..., beta=beta)`` (``"smooth_l1"``): a 0-dim fp32 tensor; ``reduction="none"`` returns
+        the [B, Ho, Wo] map of the channel sums of the elementwise loss, 0 where invalid; ``"mean"`` without a valid pixel is nan.
+        ``predict=True`` additionally returns the prediction ``head(naf(...))`` as fp32 [B, N, Ho, Wo] from the same launch:
+        ``(loss, prediction)``.  For N <= 32 the loss map, its gradient and the prediction come from the head-summed kernel's epilogue
+        (``ops.xna_head_regression``: the fp32 logits, the boolean gather and the loss's autograd graph never exist); more outputs, or a
+        geometry the kernel does not serve, compose the logits call with the same expressions.  ``errors`` (N = 1): the probe's
+        EVALUATION.  ``errors=True`` returns a fresh float64 [10] tensor of this call's error sums, ``errors=acc`` ADDS them to the
+        float64 [10] tensor ``acc`` and returns it, so a validation loop passes one accumulator for every batch and never synchronises
+        with the host: over the pixels that are valid, have ``dense_target > 0`` and a finite target and prediction, with
+        ``p = clamp(prediction, *clamp)`` (default ``clamp=(1e-3, inf)``; it applies to these statistics only) and ``d = ln p - ln t``:
+        ``n, sum |p - t|, sum (p - t)^2, sum |p - t| / t, sum (p - t)^2 / t, sum d, sum d^2`` and the counts of
+        ``max(p / t, t / p) < 1.25^k``, k = 1, 2, 3.  ``naf_amd.depth_metrics(acc)`` turns them into MAE, RMSE, abs-rel, sq-rel, RMSE-log,
+        SILog and delta_1..3, ``naf_amd.dist.reduce_errors(acc)`` sums them over ranks.  The call returns the sums IN PLACE OF the loss
+        (``(sums, prediction)`` with ``predict=True``), is never differentiable, adds without float atomics (bit-reproducible) and
+        runs the inference kernels whatever the gradient mode.  The gradient modes of the loss are those of ``target=``: frozen upsampler
+        and a probe that requires grad -- fused and differentiable with respect to the probe (``ops.XnaHeadRegFunction``); no gradient
+        wanted -- the kernel with rotate-on-load; a gradient for the upsampler, the image or the features -- the unfused composition on
+        ``forward_train``.  ``image`` may be a ``Guidance``.  ValueError, before any device work: ``dense_target`` without ``head`` or together
+        with ``target``, ``confusion``, ``regress``, ``cosine``, ``masks`` or ``return_weights``; ``valid``, ``errors`` or ``clamp`` without
+        ``dense_target``; a wrong shape or device; ``dense_loss`` outside the three values; ``beta <= 0``; ``errors`` with N != 1.
+        Not offered: scale-invariant log loss as a training loss (it is not separable per pixel), per-element masks, ``capture()`` of this call."""
+        if dense_target is not None:
+            if head is None:
+                raise ValueError("naf(..., dense_target=...) is the regression objective of a probe: pass head=probe as well")
+            if (target is not None or (confusion is not None and confusion is not False) or regress is not None or cosine or masks is not None
+                    or return_weights or loss is not None):
+                raise ValueError("naf(..., dense_target=...) does not combine with target / confusion / regress / cosine / masks / return_weights")
+            return self._forward_head_regression(image, features, output_size, head, dense_target, dense_loss, beta, valid, errors, clamp,
+                                                 reduction, bool(predict))
+        if valid is not None or (errors is not None and errors is not False) or clamp is not None:
+            raise ValueError("naf(..., valid= / errors= / clamp=) belong to the dense regression objective: pass head=probe and dense_target=... as well")
         if masks is not None:
             if (head is not None or target is not None or predict or (confusion is not None and confusion is not False) or regress is not None
                     or return_weights or cosine or loss is not None):
@@ -1888,9 +1927,10 @@ class NAF(nn.Module):
                     val = ops.reduce_head_loss(loss_map, target, ignore_index, N, reduction)
         return pack(val, None if labels is None else labels.long())
 
-    def _head_call(self, image, features, output_size, return_weights, head, reduction="mean", target=None, confusion=None):
-        """Host-side validation the three ``head=`` entries share, in the order they raise (nothing has touched the device yet):
-        -> (weight, bias, (ho, wo), target as int64).  ``target`` / ``confusion``: checked where the entry has one; the logits entry has no ``reduction``, the default passes."""
+    def _head_call(self, image, features, output_size, return_weights, head, reduction="mean", target=None, confusion=None, more=None):
+        """Host-side validation the ``head=`` entries share, in the order they raise (nothing has touched the device yet):
+        -> (weight, bias, (ho, wo), target as int64).  ``target`` / ``confusion``: checked where the entry has one; the logits entry has no ``reduction``, the default passes.
+        ``more(weight, ho, wo)``: an entry's further checks, run before CPU tensors are sent away."""
         if features.dim() != 4 or image.dim() != 4 or image.shape[0] != features.shape[0]:
             raise ValueError(f"expected image [B,3,H,W] and features [B,C,h,w], got {tuple(image.shape)} / {tuple(features.shape)}")
         weight, bias = _linear_head(head, features.shape[1])
@@ -1905,6 +1945,8 @@ class NAF(nn.Module):
             if not isinstance(confusion, torch.Tensor):
                 raise TypeError(f"confusion must be True or an int64 [N, N] tensor, got {type(confusion).__name__}")
             ops._check_confusion(confusion, weight.shape[0], features.device, "naf(..., confusion=...)")
+        if more is not None:
+            more(weight, ho, wo)
         if not (image.is_cuda and features.is_cuda and weight.is_cuda):
             raise _rocm_only(image=image, features=features, head=weight)
         return weight, bias, (ho, wo), target
@@ -1986,6 +2028,62 @@ class NAF(nn.Module):
                 _, labels, _, _ = ops.xna_head_objective(q5, k5, pv5, b32, self.upsampler.kernel_size, n_out=N, target=target, ignore_index=int(ignore_index),
                                                          want_labels=predict, scale=self.upsampler.scale, rope_tables=tabs, confusion=cm)
             return (cm, labels.long()) if predict else cm
+
+    def _forward_head_regression(self, image, features, output_size, head, dense_target, kind, beta, valid, errors, clamp, reduction, predict):
+        """``forward(..., head=head, dense_target=t)``: see ``forward``.  Every refusal comes before anything touches the device."""
+        who = "naf(..., dense_target=...)"
+        evaluation = errors is not None and errors is not False
+
+        def more(weight, ho, wo):
+            B, N, dev = image.shape[0], weight.shape[0], features.device
+            ops._check_reg_kind(who, kind, beta)
+            ops._check_dense_target(who, dense_target, (B, N, ho, wo), dev)
+            if valid is not None:
+                ops._check_valid_mask(who, valid, (B, ho, wo), dev)
+            ops._check_clamp(who, clamp)
+            if evaluation:
+                if N != 1:
+                    raise ValueError(f"naf(..., errors=...): the error statistics are defined for a head with one output, this one has {N}")
+                if errors is not True:
+                    ops._check_errors("naf(..., errors=...)", errors, dev)
+
+        weight, bias, (ho, wo), _ = self._head_call(image, features, output_size, False, head, reduction, more=more)
+        if isinstance(image, Guidance):
+            self._check_guidance_call(image, features, False, None, True if evaluation else None)
+        B, N = image.shape[0], weight.shape[0]
+        if features.shape[1] % self.upsampler.num_heads:
+            raise ValueError(f"feature channels {features.shape[1]} not divisible by {self.upsampler.num_heads} heads")
+        beta = float(beta)
+        if evaluation:
+            with torch.no_grad():
+                acc = torch.zeros(ops._lib.HEAD_REG_STATS, dtype=torch.float64, device=features.device) if errors is True else errors
+                if B == 0:
+                    return (acc, torch.empty((0, N, ho, wo), dtype=torch.float32, device=features.device)) if predict else acc
+                q5, k5, tabs, pv5, b32 = self._head_operands(image, features, weight, bias, (ho, wo), False)
+                with ops._Timed("attention"):
+                    _, _, pred = ops.xna_head_regression(q5, k5, pv5, b32, self.upsampler.kernel_size, n_out=N, target=dense_target, valid=valid,
+                                                         return_logits=predict, errors=acc, clamp=clamp, scale=self.upsampler.scale, rope_tables=tabs)
+                return (acc, pred) if predict else acc
+        grad = torch.is_grad_enabled()
+        if B == 0 or self._wants_grad(image, features):
+            # an empty batch, or a gradient for the upsampler or its inputs: the logits call (unfused there), then the objective as torch ops
+            logits = self._forward_head(image, features, output_size, False, head).float()
+            loss_map, _ = ops.head_regression_from_logits(logits, dense_target, valid, kind, beta, want_loss=True)
+            val = ops.reduce_regression_loss(loss_map, valid, N, reduction)
+            return (val, logits.detach()) if predict else val
+        head_grad = grad and (weight.requires_grad or (bias is not None and bias.requires_grad))
+        q5, k5, tabs, pv5, b32 = self._head_operands(image, features, weight, bias, (ho, wo), head_grad)
+        ksz = self.upsampler.kernel_size
+        with ops._Timed("attention"):
+            if head_grad:
+                res = ops.XnaHeadRegFunction.apply(q5, k5, pv5, b32, dense_target, valid, ksz, N, kind, beta, reduction, predict, "auto",
+                                                   self.upsampler.scale)
+                return res
+            with torch.no_grad():
+                loss_map, _, pred = ops.xna_head_regression(q5, k5, pv5, b32, ksz, n_out=N, target=dense_target, valid=valid, kind=kind, beta=beta,
+                                                            want_loss=True, return_logits=predict, scale=self.upsampler.scale, rope_tables=tabs)
+                val = ops.reduce_regression_loss(loss_map, valid, N, reduction)
+        return (val, pred) if predict else val
 
     def _forward_inference(self, image, features, output_size, return_weights=False):
         if not (image.is_cuda and features.is_cuda):

@@ -2183,6 +2183,296 @@ class XnaHeadCEFunction(torch.autograd.Function):
         return (None, None, dpv, dbias) + (None,) * 8
 
 
+# ---- ... or a dense regression objective in that epilogue's place (depth, flow, normals: L1 / MSE / smooth-L1, depth error statistics) ----
+_REG_KINDS = ("l1", "mse", "smooth_l1")
+HEAD_REG_MAX_N = 32                        # outputs the fused regression epilogue serves (naf_xna_head_reg_select)
+DEFAULT_DEPTH_CLAMP = (1e-3, math.inf)
+
+
+def _f32(v) -> float:
+    """``v`` rounded to float32: what the kernel receives in a float field."""
+    return C.c_float(float(v)).value
+
+
+def _check_reg_kind(who: str, kind, beta) -> None:
+    if kind not in _REG_KINDS:
+        raise ValueError(f"{who}: the loss must be one of {_REG_KINDS}, got {kind!r}")
+    if not float(beta) > 0.0:
+        raise ValueError(f"{who}: beta must be > 0, got {beta!r}")
+
+
+def _check_dense_target(who: str, target, shape, device) -> None:
+    if not isinstance(target, torch.Tensor) or not target.dtype.is_floating_point:
+        raise TypeError(f"{who}: the dense target must be a floating-point tensor, got {getattr(target, 'dtype', type(target).__name__)}")
+    if tuple(target.shape) != tuple(shape):
+        raise ValueError(f"{who}: the dense target must be [B, N, Ho, Wo] = {tuple(shape)}, got {tuple(target.shape)}")
+    if target.device != device:
+        raise ValueError(f"{who}: the dense target is on {target.device}, the features on {device}")
+
+
+def _check_valid_mask(who: str, valid, shape, device) -> None:
+    if not isinstance(valid, torch.Tensor) or valid.dtype not in (torch.bool, torch.uint8):
+        raise TypeError(f"{who}: valid must be a bool or uint8 tensor, got {getattr(valid, 'dtype', type(valid).__name__)}")
+    if tuple(valid.shape) != tuple(shape):
+        raise ValueError(f"{who}: valid must be [B, Ho, Wo] = {tuple(shape)}, got {tuple(valid.shape)}")
+    if valid.device != device:
+        raise ValueError(f"{who}: valid is on {valid.device}, the features on {device}")
+
+
+def _check_errors(who: str, errors, device) -> None:
+    if not isinstance(errors, torch.Tensor) or errors.dtype != torch.float64:
+        raise TypeError(f"{who}: errors must be a float64 [{_lib.HEAD_REG_STATS}] tensor, got {getattr(errors, 'dtype', type(errors).__name__)}")
+    if tuple(errors.shape) != (_lib.HEAD_REG_STATS,) or not errors.is_contiguous():
+        raise ValueError(f"{who}: errors must be a contiguous [{_lib.HEAD_REG_STATS}] tensor, got {tuple(errors.shape)}")
+    if errors.device != device:
+        raise ValueError(f"{who}: errors is on {errors.device}, the features on {device}")
+
+
+def _check_clamp(who: str, clamp) -> Tuple[float, float]:
+    lo, hi = (DEFAULT_DEPTH_CLAMP if clamp is None else clamp)
+    lo, hi = _f32(lo), _f32(hi)
+    if not lo > 0.0 or not hi >= lo:
+        raise ValueError(f"{who}: clamp must be (lo, hi) with 0 < lo <= hi, got {clamp!r}")
+    return lo, hi
+
+
+def _regression_terms(r: torch.Tensor, kind: str, beta: float):
+    """Elementwise loss and its derivative of the residual ``r``: (l(r), l'(r)), torch's definitions (``sign(0) = 0``)."""
+    if kind == "l1":
+        return r.abs(), torch.sign(r)
+    if kind == "mse":
+        return r * r, 2.0 * r
+    a = r.abs()
+    small = a < beta
+    return torch.where(small, 0.5 * r * r / beta, a - 0.5 * beta), torch.where(small, r / beta, torch.sign(r))
+
+
+def head_regression_from_logits(logits: torch.Tensor, target: torch.Tensor, valid: Optional[torch.Tensor] = None, kind: str = "l1",
+                                beta: float = 1.0, *, want_loss: bool = False, want_dlogits: bool = False,
+                                dlogits_channels: Optional[int] = None):
+    """The regression epilogue of ``naf_xna_head_reg_fwd`` as torch ops on materialised logits [B, N, Ho, Wo] (any device, CPU included):
+    what ``xna_head_regression`` composes where the kernel does not serve the call, with the same contract.  ``target`` [B, N, Ho, Wo]
+    float, ``valid`` [B, Ho, Wo] bool / uint8 or None (every pixel valid; a pixel is valid for all N channels alike).  Returns
+    ``(loss_map, dlogits)``, each None unless wanted: the sum over the channels of the elementwise loss (``kind``: "l1" ``|r|``, "mse"
+    ``r * r``, "smooth_l1" torch's with ``beta``; ``r = z - target``) [B, Ho, Wo], 0 where the pixel is not valid -- float64 for float64
+    logits, else float32, and differentiable with respect to the logits; and the derivative of that sum with respect to the logits, bf16
+    channels-last [B, Ho, Wo, dlogits_channels], zero rows for invalid pixels and zero pad channels.  Values under an invalid pixel (NaN
+    included) reach neither."""
+    _check_reg_kind("head regression", kind, beta)
+    B, N, Ho, Wo = logits.shape
+    z = logits if logits.dtype == torch.float64 else logits.float()
+    r = z - target.to(z.dtype)
+    if valid is not None:
+        r = torch.where((valid != 0).unsqueeze(1), r, torch.zeros_like(r))      # l(0) = l'(0) = 0 for the three losses
+    loss = g = None
+    if want_loss:
+        loss = _regression_terms(r, kind, float(beta))[0].sum(dim=1)
+    if want_dlogits:
+        gc = int(dlogits_channels) if dlogits_channels is not None else head_dlogits_channels(N)
+        if gc < N:
+            raise ValueError(f"head regression: dlogits_channels {gc} smaller than the {N} outputs")
+        d = _regression_terms(r.detach(), kind, float(beta))[1].permute(0, 2, 3, 1)
+        g = torch.nn.functional.pad(d, (0, gc - N)).to(torch.bfloat16)
+    return loss, g
+
+
+def reduce_regression_loss(loss_map: torch.Tensor, valid: Optional[torch.Tensor], n_out: int, reduction: str) -> torch.Tensor:
+    """``reduction`` of the per-pixel map of channel sums as ``F.l1_loss`` / ``F.mse_loss`` / ``F.smooth_l1_loss`` define it on the selected
+    elements: "none" the map, "sum" its sum, "mean" the sum over (number of valid pixels * n_out) -- counted on the device without a host
+    synchronisation; no valid pixel: nan, as an empty mean in torch."""
+    if reduction == "none":
+        return loss_map
+    total = loss_map.sum()
+    if reduction == "sum":
+        return total
+    return (total.double() / _regression_count(loss_map, valid, n_out)).to(total.dtype)
+
+
+def _regression_count(loss_map: torch.Tensor, valid: Optional[torch.Tensor], n_out: int) -> torch.Tensor:
+    """Number of selected elements (valid pixels * n_out) as a float64 device scalar: counted in int64, so exact at any batch size."""
+    pixels = (valid != 0).sum() if valid is not None else torch.full((), loss_map.numel(), dtype=torch.int64, device=loss_map.device)
+    return (pixels * int(n_out)).double()
+
+
+def head_errors_from_prediction(pred: torch.Tensor, target: torch.Tensor, valid: Optional[torch.Tensor] = None,
+                                clamp=None) -> torch.Tensor:
+    """The ten error sums of ``naf_xna_head_reg_fwd`` as torch ops in float64 (any device, CPU included): ``pred`` and ``target``
+    [B, 1, Ho, Wo] or [B, Ho, Wo], ``valid`` [B, Ho, Wo] bool / uint8 or None, ``clamp=(lo, hi)`` (default (1e-3, inf); the bounds are
+    rounded to float32, as the kernel receives them).  With ``p = min(max(pred, lo), hi)`` a pixel is counted when it is valid,
+    ``target > 0`` and ``target`` and ``pred`` are finite; with ``d = ln p - ln target`` the result is float64 [10]:
+    ``n, sum |p - t|, sum (p - t)^2, sum |p - t| / t, sum (p - t)^2 / t, sum d, sum d^2`` and the numbers of pixels with
+    ``max(p / t, t / p)`` below 1.25, 1.25^2, 1.25^3.  ``depth_metrics`` turns them into the usual depth figures."""
+    lo, hi = _check_clamp("head_errors_from_prediction", clamp)
+    z = (pred[:, 0] if pred.dim() == 4 else pred).double()
+    t = (target[:, 0] if target.dim() == 4 else target).double()
+    cnt = (t > 0) & torch.isfinite(t) & torch.isfinite(z)
+    if valid is not None:
+        cnt = cnt & (valid != 0)
+    one = torch.ones_like(t)
+    p = torch.where(cnt, z.clamp(lo, hi), one)
+    t = torch.where(cnt, t, one)
+    e, d, ratio = p - t, torch.log(p) - torch.log(t), torch.maximum(p / t, t / p)
+    c = cnt.double()
+    terms = (c, e.abs(), e * e, e.abs() / t, e * e / t, d, d * d, (ratio < 1.25).double(), (ratio < 1.25 ** 2).double(), (ratio < 1.25 ** 3).double())
+    return torch.stack([(x * c).sum() for x in terms])
+
+
+DepthMetrics = collections.namedtuple("DepthMetrics", ("mae", "rmse", "abs_rel", "sq_rel", "rmse_log", "silog", "d1", "d2", "d3", "n"))
+
+
+def depth_metrics(acc: torch.Tensor) -> "DepthMetrics":
+    """The usual depth-evaluation figures from the ten error sums (``naf(..., errors=acc)``, ``head_errors_from_prediction``), in float64
+    on the accumulator's device, without a host synchronisation.  ``DepthMetrics(mae, rmse, abs_rel, sq_rel, rmse_log, silog, d1, d2, d3, n)``:
+    means over the ``n`` counted pixels of ``|p - t|``, ``(p - t)^2`` (its root), ``|p - t| / t``, ``(p - t)^2 / t``, ``d^2`` (its root)
+    with ``d = ln p - ln t``; ``silog = sqrt(mean d^2 - (mean d)^2)``; ``d1, d2, d3`` the shares of pixels with ``max(p / t, t / p)`` below
+    1.25, 1.25^2, 1.25^3.  ``n == 0`` gives nan, as an empty mean does in torch."""
+    if not isinstance(acc, torch.Tensor) or tuple(acc.shape) != (_lib.HEAD_REG_STATS,):
+        raise ValueError(f"depth_metrics: the [{_lib.HEAD_REG_STATS}] error sums are expected, got "
+                         f"{tuple(getattr(acc, 'shape', ())) if isinstance(acc, torch.Tensor) else type(acc).__name__}")
+    a = acc.to(torch.float64)
+    n = a[0]
+    m = a[1:] / n
+    var = (m[5] - m[4] * m[4]).clamp_min(0.0)         # rounding can leave a constant ratio's variance below zero; nan stays nan
+    return DepthMetrics(m[0], m[1].sqrt(), m[2], m[3], m[5].sqrt(), var.sqrt(), m[6], m[7], m[8], n)
+
+
+def xna_head_regression(q: torch.Tensor, k_lr: torch.Tensor, pv_lr: torch.Tensor, bias: Optional[torch.Tensor], kernel_size, *,
+                        n_out: int, target: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, kind: str = "l1",
+                        beta: float = 1.0, want_loss: bool = False, want_dlogits: bool = False, return_logits: bool = False,
+                        errors: Optional[torch.Tensor] = None, clamp=None, path: str = "auto", scale: Optional[float] = None,
+                        rope_tables=None):
+    """``xna_head_forward`` with a dense regression objective in the kernel's epilogue (``naf_xna_head_reg_fwd``): one launch gives any of
+    the per-pixel loss, its gradient with respect to the logits, the logits and the error statistics of depth evaluation, without the
+    [B, N, Ho, Wo] logits having to be written.
+
+    Arguments as ``xna_head_forward``; ``target`` [B, n_out, Ho, Wo] float (any strides; other float dtypes are converted with
+    ``.float()``), ``valid`` [B, Ho, Wo] bool / uint8 (any strides) or None.  Returns ``(loss_map, dlogits, logits)``, each None unless asked
+    for, as ``head_regression_from_logits`` defines them: fp32 [B, Ho, Wo], 0 where invalid; bf16 [B, Ho, Wo, Gc] with
+    ``Gc = head_dlogits_channels(n_out)``, every channel written, NOT divided by anything -- the ``dout`` the attention backward takes for
+    all heads at once; fp32 logits as ``xna_head_forward(..., out_dtype=float32)`` returns them.  ``errors``: a float64 [10] device tensor
+    the call ADDS the ten error sums to (``head_errors_from_prediction``; ``n_out == 1`` only), ``clamp=(lo, hi)`` the bounds of the
+    prediction there (default (1e-3, inf)); bit-reproducible, no float atomics.  ``path="auto"`` composes
+    ``xna_head_forward(..., out_dtype=float32)`` with ``head_regression_from_logits`` / ``head_errors_from_prediction`` where the kernel
+    refuses (n_out > 32, geometry; same contract); ``path="fused"`` insists and raises; ``path="composed"`` is the A/B arm."""
+    ky, kx, B, heads, Ho, Wo, Dq, h, w, npad, n_out = _check_head_operands("xna_head_regression", q, k_lr, pv_lr, bias, kernel_size, n_out, path)
+    _check_reg_kind("xna_head_regression", kind, beta)
+    if not (want_loss or want_dlogits or return_logits or errors is not None):
+        raise ValueError("xna_head_regression: nothing asked for (want_loss / want_dlogits / return_logits / errors)")
+    dev = q.device
+    if (want_loss or want_dlogits or errors is not None) and target is None:
+        raise ValueError("xna_head_regression: the loss, its gradient and the error statistics need a target")
+    if target is not None:
+        _check_dense_target("xna_head_regression", target, (B, n_out, Ho, Wo), dev)
+        if target.dtype != torch.float32:
+            target = target.float()
+    if valid is not None:
+        _check_valid_mask("xna_head_regression", valid, (B, Ho, Wo), dev)
+        if valid.dtype == torch.bool:
+            valid = valid.view(torch.uint8)
+    lo, hi = _check_clamp("xna_head_regression", clamp)
+    if errors is not None:
+        if n_out != 1:
+            raise ValueError(f"xna_head_regression: the error statistics are defined for one output channel, got n_out = {n_out}")
+        _check_errors("xna_head_regression", errors, dev)
+    lib = _lib.load()
+    gc = head_dlogits_channels(n_out)
+    if path != "composed" and (n_out <= 256 or path == "fused"):
+        out = torch.empty((B, Ho, Wo, n_out), dtype=torch.float32, device=dev) if return_logits else None
+        loss = torch.empty((B, Ho, Wo), dtype=torch.float32, device=dev) if want_loss else None
+        g = torch.empty((B, Ho, Wo, gc), dtype=torch.bfloat16, device=dev) if want_dlogits else None     # the kernel writes every channel
+        a = _lib.XnaHeadRegArgs()
+        a.head = _fill_xna_head(q, k_lr, pv_lr, bias, out if out is not None else q, n_out, ky, kx, path, scale, rope_tables)
+        if out is None:
+            a.head.out, a.head.out_dtype = None, _lib.NAF_F32
+        a.kind, a.beta, a.dlogits_channels, a.clamp_lo, a.clamp_hi = _lib.HEAD_REG_KINDS[kind], float(beta), gc, lo, hi
+        if target is not None:
+            a.target, a.t_stride = target.data_ptr(), _strides4(target, (0, 1, 2, 3))
+        for t, ptr, st in ((valid, "valid", "valid_stride"), (loss, "loss", "loss_stride"), (g, "dlogits", "dlogits_stride")):
+            if t is not None:
+                setattr(a, ptr, t.data_ptr())
+                setattr(a, st, _strides3(t))
+        ws = None
+        if errors is not None:
+            a.errors = errors.data_ptr()
+        sel = lib.naf_xna_head_reg_select(C.byref(a))
+        if sel == _lib.XNA_HEAD_FUSED:
+            if errors is not None:
+                nbytes = int(lib.naf_xna_head_reg_workspace_bytes(C.byref(a)))
+                ws = torch.empty((max(nbytes, 8) + 7) // 8, dtype=torch.float64, device=dev)
+                a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+            with torch.cuda.device(dev), _Timed("xna_head_reg"):
+                rc = lib.naf_xna_head_reg_fwd(C.byref(a), _stream(q))
+            _lib.check(rc, "naf_xna_head_reg_fwd")
+            return loss, g, (None if out is None else out.permute(0, 3, 1, 2))
+        if path == "fused" or sel == -1:       # insisted, or arguments no kernel serves
+            _lib.check(-sel, "naf_xna_head_reg_select")
+        del out, loss, g
+    with _Timed("xna_head_reg_composed"):
+        logits = xna_head_forward(q, k_lr, pv_lr, bias, (ky, kx), n_out=n_out, out_dtype=torch.float32,
+                                  path="auto" if path == "auto" else "composed", scale=scale, rope_tables=rope_tables)
+        loss = g = None
+        if want_loss or want_dlogits:
+            loss, g = head_regression_from_logits(logits, target, valid, kind, beta, want_loss=want_loss, want_dlogits=want_dlogits,
+                                                  dlogits_channels=gc)
+        if errors is not None:
+            errors.add_(head_errors_from_prediction(logits, target, valid, (lo, hi)))
+        return loss, g, (logits if return_logits else None)
+
+
+class XnaHeadRegFunction(torch.autograd.Function):
+    """Differentiable dense regression loss of the head-summed attention's logits, with respect to the head (``pv_lr`` and ``bias`` only, as
+    ``XnaHeadCEFunction``): the forward is ONE launch (``xna_head_regression``) that leaves the loss map and its gradient ``g`` (bf16, the
+    attention backward's width, unnormalised); the backward hands ``g`` to ``xna_backward`` as the ``dout`` of every head (stride 0) and
+    scales the low-res result by the incoming gradient and, for "mean", by 1 / (number of valid pixels * n_out), a device scalar (no host
+    synchronisation) -- the backward is linear in ``g``.  ``dbias = sum over pixels of g`` times the same.  reduction="none": the incoming
+    gradient is a map, ``g`` is scaled per pixel first and rounded to bf16 a SECOND time (the attention backward reads bf16): exact for an
+    incoming map of ones or powers of two, one more 2^-9 relative rounding for a general map -- ``g`` itself is rounded once only in the
+    forward and for "mean" / "sum".  Returns the reduced loss, or ``(loss, logits)`` with ``return_logits`` (fp32
+    [B, n_out, Ho, Wo], without a gradient).  ``q`` holds materialised (rotated) queries."""
+
+    @staticmethod
+    def forward(ctx, q, k_lr, pv_lr, bias, target, valid, kernel_size, n_out, kind="l1", beta=1.0, reduction="mean", return_logits=False,
+                path="auto", scale=None):
+        if reduction not in _REDUCTIONS:
+            raise ValueError(f"reduction must be one of {_REDUCTIONS}, got {reduction!r}")
+        n_out = int(n_out)
+        loss_map, g, logits = xna_head_regression(q, k_lr, pv_lr, bias, kernel_size, n_out=n_out, target=target, valid=valid, kind=kind,
+                                                  beta=beta, want_loss=True, want_dlogits=True, return_logits=return_logits, path=path,
+                                                  scale=scale)
+        inv_count = None
+        if reduction == "mean":
+            inv_count = _regression_count(loss_map, valid, n_out).reciprocal().float()      # exact count, one rounding
+        ctx.save_for_backward(q, k_lr, pv_lr, g, *(() if inv_count is None else (inv_count,)))
+        ctx.kernel_size, ctx.n_out, ctx.scale, ctx.has_bias, ctx.reduction = kernel_size, n_out, scale, bias is not None, reduction
+        loss = reduce_regression_loss(loss_map, valid, n_out, reduction)
+        if return_logits:
+            ctx.mark_non_differentiable(logits)
+            return loss, logits
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss, *rest):
+        q, k_lr, pv_lr, g = ctx.saved_tensors[:4]
+        need_pv, need_b = ctx.needs_input_grad[2], ctx.has_bias and ctx.needs_input_grad[3]
+        N = ctx.n_out
+        dpv = dbias = None
+        if ctx.reduction == "none":
+            g = (g.float() * dloss.unsqueeze(-1)).to(torch.bfloat16)
+            factor = None
+        else:
+            factor = dloss.float() * ctx.saved_tensors[4] if ctx.reduction == "mean" else dloss.float()
+        if need_b:
+            dbias = g.float().sum(dim=(0, 1, 2))[:N]
+            if factor is not None:
+                dbias = dbias * factor
+        if need_pv:
+            dv = _head_values_grad(q, k_lr, pv_lr, g, ctx.kernel_size, ctx.scale)
+            if factor is not None:
+                dv = dv * factor
+            dpv = dv.to(pv_lr.dtype)
+        return (None, None, dpv, dbias) + (None,) * 10
+
+
 # ---- ... and the same objective on the cosine head's scaled cosines (cosine classifier, prompt tuning, learnable temperature) ----------
 def project_cosine_values(embeddings: torch.Tensor, v_lr: torch.Tensor) -> torch.Tensor:
     """The low-res half of the cosine head: ``PV_g = E^[:, g*Dv:(g+1)*Dv] @ V_g`` with ``E^ = normalize_embeddings(E)`` for v_lr
